@@ -1,11 +1,21 @@
 #!/usr/bin/env python3
 """Headline benchmark: fine-grid DOF/s per BoxMG V-cycle on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--workload NAME]
+    python bench.py --gpus N --steps K --warmup W [--workload NAME] [--dump-outputs DIR] [--full]
 
 One "step" = one V(2,1) cycle (`cycle->run(x,b)` of include/cedar/cycle/vcycle.h:57-115)
 on synthetic, HBM-resident data; set-up and the convergence-check residual are
 outside the timed region.  Prints ONE JSON line.
+
+A plain run does only what the headline needs: it builds the operator and the solver once, runs W warm-up
+and K timed steps on them and prints the line (`value`, `ms_per_step`: the K timed steps).  --full adds
+everything else listed below: the median over fresh allocations, the roofline and level-0 kernel timings,
+the set-up figures, the other workloads and the CPU baseline (--allocations, --no-cpu-baseline and
+--no-other-workloads shape a --full run).
+--dump-outputs DIR: after the timed steps, the iterate x of the last timed step (what a caller of the
+cycle receives; rank 0's block when N > 1) goes to DIR/x.npy in float64, or, when it exceeds 32 MB, a
+fixed, seeded sample of 4 Mi of its points to DIR/x_sample.npy.  The inputs are synthetic and seeded, so
+two runs with the same arguments compute on the same data.
 
 Workloads (BASELINE.json configs; synthetic operators built on the device):
   3d27   3D 27-pt gallery::fe,        512^3 per GPU, point 8-colour GS   (default; config 4 / 5,
@@ -13,21 +23,22 @@ Workloads (BASELINE.json configs; synthetic operators built on the device):
   2d9    2D 9-pt variable coefficient, 4096^2, point 4-colour GS          (config 2)
   2d9l   2D 9-pt anisotropic,          8192^2, zebra line relax x+y       (config 3)
   2d5    2D 5-pt Poisson,              512^2                              (config 1)
-Extra keys in the JSON line:
+Extra keys in the JSON line of a --full run:
   roofline     dominant kernel (the level-0 relax sweep): algorithmic bytes per launch
                / average launch duration measured live with HIP events on the library's stream
   cpu_baseline the oracle (C restatement of the reference, kind "port") timed on one host
                core on a bounded sample of the same workload
   level0_kernels   N = 1, 3d27: the other level-0 kernels of the cycle (residual27_rows, restrict3, interp_add3) against the
                HBM roofline: algorithmic bytes / launch time from HIP events (cedar_amd_solver_time_op)
-  other_workloads  N = 1, default run only: BASELINE configs 2 and 3 (2d9 4096^2 point, 2d9l 8192^2 line-xy) timed the same
+  other_workloads  N = 1, default workload and size only: BASELINE configs 2 and 3 (2d9 4096^2 point, 2d9l 8192^2 line-xy) timed the same
                way in this process after the 3D solver has been released: ms_per_step, DOF/s, relax launch time and frac;
                3d27_rank_of_2x2x2_loopback: one rank of config 5 (native distributed driver, loop-back transport: kernels,
                packs and copies of the 8-GPU run per rank, no links) and its ratio to the single-GPU cycle
   ms_per_step_per_allocation  N = 1: the W warm-up + K timed steps are run on every one of the fresh allocations the
                roofline launch time is taken over (default 3), and `value` / `ms_per_step` are the MEDIAN: where the
                operator lands in device memory moves a sweep by +-6 %, and the headline should
-               not be the luck of the first allocation.  --allocations 1: the first allocation only.
+               not be the luck of the first allocation.  --allocations 1: the first allocation only.  A plain run
+               lists its one allocation here.
 Multi-GPU (N > 1): one process per GPU.  Started as the driver does (torch.distributed.run sets RANK / LOCAL_RANK /
 WORLD_SIZE / MASTER_*) every process is a rank; started bare (`python bench.py --gpus N`) the parent spawns N fresh rank
 processes before it touches a GPU itself.  No workload imports torch: the distributed cycles run below the C ABI
@@ -220,6 +231,18 @@ def rank_of_grid(capi, pgrid=(2, 2, 2), n=512, steps=5, warmup=2):
     return out
 
 
+def dump_outputs(d, arrays, max_bytes=32 << 20):
+    """--dump-outputs: each array whole as DIR/<name>.npy, or above max_bytes a fixed, seeded sample of max_bytes / 8
+    of its points as DIR/<name>_sample.npy (float64; one array per workload keeps the total under 64 MB)"""
+    os.makedirs(d, exist_ok=True)
+    for name, a in arrays.items():
+        a = np.asarray(a, dtype=np.float64)
+        if a.nbytes > max_bytes:
+            idx = np.sort(np.random.default_rng(20261016).integers(0, a.size, max_bytes // 8))
+            a, name = a.reshape(-1)[idx], name + "_sample"
+        np.save(os.path.join(d, name + ".npy"), a)
+
+
 def visible_gpus():
     """number of GPUs this box shows, counted in a child process so that the caller stays free of any HIP state"""
     import subprocess
@@ -284,15 +307,22 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", default="3d27", choices=list(WORKLOADS))
     ap.add_argument("--size", type=int, default=0, help="override the per-GPU grid extent")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the iterate x of the last step to DIR (see the module docstring)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the figures beside the headline: median over allocations, roofline, level-0 kernels, "
+                         "set-up times, other workloads, CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--no-other-workloads", action="store_true",
-                    help="default 3d27 run: skip the 2d9 / 2d9l timings appended as other_workloads")
+                    help="--full, default 3d27 run: skip the 2d9 / 2d9l timings appended as other_workloads")
     ap.add_argument("--allocations", type=int, default=3,
-                    help="N=1: fresh operator allocations the roofline launch time is the median of")
+                    help="--full, N=1: fresh operator allocations the roofline launch time is the median of")
     ap.add_argument("--strong", action="store_true",
                     help="3D, N>1: keep the GLOBAL grid at --size^3 and split it over the ranks (strong scaling); "
                          "default is --size^3 per GPU (weak scaling, what the driver's scaling table uses)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     rehearsal = os.environ.get("CEDAR_AMD_DIST_BACKEND", "rccl") != "rccl"  # ranks share a GPU over a host-staged transport
     if "WORLD_SIZE" not in os.environ:
@@ -434,76 +464,79 @@ def main():
     elapsed = time.perf_counter() - t0
     if comm is not None:
         elapsed = comm.allreduce_max(elapsed)
-
-    # dominant kernel: the level-0 relax sweep, HIP events on the library's stream
-    nsw = 20 if nd == 3 else 40
-    solver.time_relax(x, b, 4)
-    ms = solver.time_relax(x, b, nsw)
-    per_alloc = [ms / (nsw * launches)]
     step_ms = [elapsed / args.steps * 1e3]
-    setups = [] if t_setup is None else [t_setup]
-    if world == 1 and args.allocations > 1:
-        # the sweep time depends on where the operator allocation lands in HBM (7-14 % between allocations of one
-        # process, profiles/r01_allocation_placement_variance.log): quote the MEDIAN over fresh allocations of the
-        # operator + hierarchy, not the luck of the first one
-        for _ in range(args.allocations - 1):
-            so2, b2 = build_problem(capi, args.workload, n)
-            capi.sync()
-            ts = time.perf_counter()
-            s2 = capi.Solver(so2, relax=relax, share_operator=True)
-            capi.sync()
-            setups.append(time.perf_counter() - ts)
-            x2 = capi.DeviceArray(b2.shape)
-            # the same W warm-up + K timed steps on this allocation: the headline is the median over the allocations too
-            for _ in range(args.warmup):
-                s2.vcycle(x2, b2)
-            barrier()
-            t0 = time.perf_counter()
-            for _ in range(args.steps):
-                s2.vcycle(x2, b2)
-            barrier()
-            step_ms.append((time.perf_counter() - t0) / args.steps * 1e3)
-            s2.time_relax(x2, b2, 4)
-            per_alloc.append(s2.time_relax(x2, b2, nsw) / (nsw * launches))
-            s2.close()
-            so2.free(); b2.free(); x2.free()
-    if world == 1 and setups and args.allocations > 1:
-        # a creation that maps device memory the process has not held before also pays the driver's clearing of it (hundreds
-        # of ms on a box other processes have used, profiles/r02_setup_time_allocations.log): ALWAYS two more create / release
-        # rounds on the resident operator, which reuse released blocks and show the set-up itself
-        for _ in range(2):
-            capi.sync()
-            ts = time.perf_counter()
-            s3 = capi.Solver(so, relax=relax, share_operator=True)
-            capi.sync()
-            setups.append(time.perf_counter() - ts)
-            s3.close()
-    level0 = None
-    if world == 1 and nd == 3 and hasattr(solver, "time_op"):
-        # the other level-0 kernels of the cycle against the same roofline (algorithmic bytes: SURVEY 8d / DESIGN section 5)
-        level0 = {}
-        for op, kname, bpd in (("residual", "residual27_rows", 136.0), ("restrict", "restrict3_kernel", 35.0),
-                               ("interp_add", "interp_add3_kernel", 67.0)):
-            solver.time_op(x, b, op, 2)
-            t = solver.time_op(x, b, op, 10) / 10
-            level0[kname] = {"launch_ms": t, "algorithmic_bytes_per_launch": bpd * dof,
-                             "achieved": bpd * dof / (t * 1e-3) / 1e9, "unit": "GB/s", "frac": bpd * dof / (t * 1e-3) / 8e12}
-    launch_ms = sorted(per_alloc)[len(per_alloc) // 2]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"x": (x if world == 1 else xt).numpy()})
+
+    if args.full:
+        # dominant kernel: the level-0 relax sweep, HIP events on the library's stream
+        nsw = 20 if nd == 3 else 40
+        solver.time_relax(x, b, 4)
+        ms = solver.time_relax(x, b, nsw)
+        per_alloc = [ms / (nsw * launches)]
+        setups = [] if t_setup is None else [t_setup]
+        if world == 1 and args.allocations > 1:
+            # the sweep time depends on where the operator allocation lands in HBM (7-14 % between allocations of one
+            # process, profiles/r01_allocation_placement_variance.log): quote the MEDIAN over fresh allocations of the
+            # operator + hierarchy, not the luck of the first one
+            for _ in range(args.allocations - 1):
+                so2, b2 = build_problem(capi, args.workload, n)
+                capi.sync()
+                ts = time.perf_counter()
+                s2 = capi.Solver(so2, relax=relax, share_operator=True)
+                capi.sync()
+                setups.append(time.perf_counter() - ts)
+                x2 = capi.DeviceArray(b2.shape)
+                # the same W warm-up + K timed steps on this allocation: the headline is the median over the allocations too
+                for _ in range(args.warmup):
+                    s2.vcycle(x2, b2)
+                barrier()
+                t0 = time.perf_counter()
+                for _ in range(args.steps):
+                    s2.vcycle(x2, b2)
+                barrier()
+                step_ms.append((time.perf_counter() - t0) / args.steps * 1e3)
+                s2.time_relax(x2, b2, 4)
+                per_alloc.append(s2.time_relax(x2, b2, nsw) / (nsw * launches))
+                s2.close()
+                so2.free(); b2.free(); x2.free()
+        if world == 1 and setups and args.allocations > 1:
+            # a creation that maps device memory the process has not held before also pays the driver's clearing of it (hundreds
+            # of ms on a box other processes have used, profiles/r02_setup_time_allocations.log): ALWAYS two more create / release
+            # rounds on the resident operator, which reuse released blocks and show the set-up itself
+            for _ in range(2):
+                capi.sync()
+                ts = time.perf_counter()
+                s3 = capi.Solver(so, relax=relax, share_operator=True)
+                capi.sync()
+                setups.append(time.perf_counter() - ts)
+                s3.close()
+        level0 = None
+        if world == 1 and nd == 3 and hasattr(solver, "time_op"):
+            # the other level-0 kernels of the cycle against the same roofline (algorithmic bytes: SURVEY 8d / DESIGN section 5)
+            level0 = {}
+            for op, kname, bpd in (("residual", "residual27_rows", 136.0), ("restrict", "restrict3_kernel", 35.0),
+                                   ("interp_add", "interp_add3_kernel", 67.0)):
+                solver.time_op(x, b, op, 2)
+                t = solver.time_op(x, b, op, 10) / 10
+                level0[kname] = {"launch_ms": t, "algorithmic_bytes_per_launch": bpd * dof,
+                                 "achieved": bpd * dof / (t * 1e-3) / 1e9, "unit": "GB/s", "frac": bpd * dof / (t * 1e-3) / 8e12}
+        launch_ms = sorted(per_alloc)[len(per_alloc) // 2]
+        alg_bytes_launch = bytes_per_dof * dof / launches
+        achieved = alg_bytes_launch / (launch_ms * 1e-3) / 1e9
+        traffic = None
+        try:
+            pmc = json.load(open(os.path.join(ROOT, "profiles", "pmc_traffic.json")))
+            if n == n_default:  # the PMC passes were taken at the benchmark size
+                traffic = pmc.get(args.workload + ("_psum_sweep" if psum else "_rows" if world > 4 else ""), {}).get("hbm_bytes_per_launch")
+        except Exception:
+            pass
+        roofline = {"bound": "hbm", "kernel": "relax sweep level 0 (%s)" % relax_kernel,
+                    "achieved": achieved, "peak": 8000.0, "unit": "GB/s", "frac": achieved / 8000.0,
+                    "traffic": traffic, "launch_ms": launch_ms, "algorithmic_bytes_per_launch": alg_bytes_launch,
+                    "launch_ms_per_allocation": per_alloc,
+                    "launch_ms_is": "median over %d fresh allocations of operator + hierarchy" % len(per_alloc)}
     ms_per_step = sorted(step_ms)[len(step_ms) // 2]
-    alg_bytes_launch = bytes_per_dof * dof / launches
-    achieved = alg_bytes_launch / (launch_ms * 1e-3) / 1e9
-    traffic = None
-    try:
-        pmc = json.load(open(os.path.join(ROOT, "profiles", "pmc_traffic.json")))
-        if n == n_default:  # the PMC passes were taken at the benchmark size
-            traffic = pmc.get(args.workload + ("_psum_sweep" if psum else "_rows" if world > 4 else ""), {}).get("hbm_bytes_per_launch")
-    except Exception:
-        pass
-    roofline = {"bound": "hbm", "kernel": "relax sweep level 0 (%s)" % relax_kernel,
-                "achieved": achieved, "peak": 8000.0, "unit": "GB/s", "frac": achieved / 8000.0,
-                "traffic": traffic, "launch_ms": launch_ms, "algorithmic_bytes_per_launch": alg_bytes_launch,
-                "launch_ms_per_allocation": per_alloc,
-                "launch_ms_is": "median over %d fresh allocations of operator + hierarchy" % len(per_alloc)}
 
     if rank == 0:
         out = {
@@ -530,24 +563,27 @@ def main():
                        ("x".join(map(str, topo.p[:nd])),
                         "x".join(str(int(v)) for v in ln) if nd == 3 else "%d^2" % n,
                         comm.name)},
-            "roofline": roofline,
-            # device-side interp + Galerkin + relax set-up + solve copies, host-timed around solver creation.  Quoted: the
-            # MINIMUM over the solver creations of this process.  A creation that maps device memory the process has not
-            # held before also pays the driver's clearing of that memory (~0.45 s for the 45 GB of a 512^3 solver on a
-            # box other processes have used: profiles/r02_setup_time_allocations.log) and, for the very first one,
-            # code-object loading; a creation that reuses released blocks shows the set-up itself.  All values are listed.
-            "setup_ms": None if not setups else min(setups) * 1e3,
-            "setup_ms_is": "minimum over %d solver creations in this process (setup_ms_first = the first creation, what a "
-                           "one-shot user pays incl. code-object loading and the driver's clearing of fresh device memory; "
-                           "setup_ms_median; all in setup_ms_per_allocation)" % len(setups),
-            "setup_ms_first": None if not setups else setups[0] * 1e3,
-            "setup_ms_median": None if not setups else sorted(setups)[len(setups) // 2] * 1e3,
-            "setup_ms_per_allocation": [v * 1e3 for v in setups],
         }
-        if level0:
+        if args.full:
+            out.update({
+                "roofline": roofline,
+                # device-side interp + Galerkin + relax set-up + solve copies, host-timed around solver creation.  Quoted: the
+                # MINIMUM over the solver creations of this process.  A creation that maps device memory the process has not
+                # held before also pays the driver's clearing of that memory (~0.45 s for the 45 GB of a 512^3 solver on a
+                # box other processes have used: profiles/r02_setup_time_allocations.log) and, for the very first one,
+                # code-object loading; a creation that reuses released blocks shows the set-up itself.  All values are listed.
+                "setup_ms": None if not setups else min(setups) * 1e3,
+                "setup_ms_is": "minimum over %d solver creations in this process (setup_ms_first = the first creation, what a "
+                               "one-shot user pays incl. code-object loading and the driver's clearing of fresh device memory; "
+                               "setup_ms_median; all in setup_ms_per_allocation)" % len(setups),
+                "setup_ms_first": None if not setups else setups[0] * 1e3,
+                "setup_ms_median": None if not setups else sorted(setups)[len(setups) // 2] * 1e3,
+                "setup_ms_per_allocation": [v * 1e3 for v in setups],
+            })
+        if args.full and level0:
             out["level0_kernels"] = level0
-        if world == 1 and args.workload == "3d27" and not args.size and not args.no_other_workloads:
-            # BASELINE configs 2 and 3 in the same line (the driver runs the default command only)
+        if args.full and world == 1 and args.workload == "3d27" and not args.size and not args.no_other_workloads:
+            # BASELINE configs 2 and 3 in the same line (one --full run of the default workload carries them all)
             solver.close()
             solver = None
             so.free(); b.free(); x.free()
@@ -559,7 +595,7 @@ def main():
             except Exception as e:  # noqa: BLE001 -- an aid beside the headline: its failure must not cost the line
                 rk = {"error": "%s: %s" % (type(e).__name__, e)}
             out["other_workloads"]["3d27_rank_of_2x2x2_loopback"] = rk
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(args.workload, relax)
         print(json.dumps(out), flush=True)
     if solver is not None:
