@@ -351,6 +351,19 @@ def gallery(name, n, params=None, with_rhs=True, device=True):
     return so, b
 
 
+class PcgSettings(C.Structure):
+    _fields_ = [("max_iter", C.c_int), ("tol", C.c_double), ("stop_test", C.c_int), ("precon", C.c_int),
+                ("nmg_cycles", C.c_int)]
+
+
+# BoxMG's numbering (src/{2d,3d}/ftn/BMG_PCG_parameters_f90.h)
+PCG_STOP = {"abs_l2": 0, "rel_l2": 1, "abs_m": 2, "rel_m": 3}
+PCG_PRECON = {"none": 1, "diag": 2, "mg": 3}
+lib.cedar_amd_solver_pcg.restype = C.c_int
+lib.cedar_amd_solver_pcg.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(PcgSettings), C.c_void_p]
+lib.cedar_amd_solver_precondition.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+
+
 class Solver:
     """cedar::cdr2::solver / cdr3::solver on the device (include/cedar_amd.h, handle API)."""
 
@@ -405,6 +418,20 @@ class Solver:
         rel = np.zeros(self.max_iter + 1)
         n = lib.cedar_amd_solver_solve(self.h, _vp(b), _vp(x), rel.ctypes.data)
         return rel[: n + 1]
+
+    def pcg(self, b, x, max_iter=50, tol=1e-8, stop="rel_l2", precon="mg", nmg_cycles=1):
+        """conjugate gradients preconditioned by the cycle (cedar_amd_solver_pcg): x updated in place; returns the
+        history [||r0||, ||r1||/||r0||, ...]; RuntimeError when the library refuses the settings (x untouched)"""
+        ps = PcgSettings(int(max_iter), float(tol), PCG_STOP[stop], PCG_PRECON[precon], int(nmg_cycles))
+        hist = np.zeros(max(int(max_iter), 0) + 1)
+        n = lib.cedar_amd_solver_pcg(self.h, _vp(b), _vp(x), C.byref(ps), hist.ctypes.data)
+        if n < 0:
+            raise RuntimeError("cedar_amd_solver_pcg refused the settings (see the printed reason)")
+        return hist[: n + 1]
+
+    def precondition(self, z, r):
+        """z = M^-1 r: one cycle from z = 0 (cedar_amd_solver_precondition)"""
+        lib.cedar_amd_solver_precondition(self.h, _vp(z), _vp(r))
 
     def time_vcycles(self, x, b, n):
         return lib.cedar_amd_solver_time_vcycles(self.h, x.ptr, b.ptr, n)

@@ -239,6 +239,18 @@ void solve_cg2(real_t *q, const real_t *qf, int II, int JJ, const real_t *abd, r
                Batch bt = Batch()); // bbd: nabd2 doubles per batch item
 void setup_cg3(const real_t *so, int II, int JJ, int KK, int nstncl, real_t *abd, int nabd1, int nabd2, int *info, hipStream_t st);
 void solve_cg3(real_t *q, const real_t *qf, int II, int JJ, int KK, const real_t *abd, real_t *bbd, int nabd1, int nabd2, hipStream_t st);
+// krylov.hip: the vector work of the preconditioned conjugate gradient (solver.cpp cedar_amd_solver_pcg).  The scalars
+// of a run live on the device in sc[PCG_NSC]; the kernels read alpha / beta from there and write them back.
+enum { PCG_RHO = 0, PCG_SIGMA = 1, PCG_ALPHA = 2, PCG_BETA = 3, PCG_RR = 4, PCG_RZ = 5, PCG_FLAG = 6, PCG_NSC = 8 };
+size_t pcg_slab_doubles(int nd, int nst, int II, int JJ, int KK); // partial-sum slab of the two launchers below
+// pn = z + beta p (first: pn = z), w = A pn, sigma = pn.w, alpha = rho / sigma (0 and PCG_FLAG = 1 when sigma <= 0 or
+// rho = 0); op27: the operator view of a 27-point level (nullptr: the Cedar planes of so)
+void pcg_direction(const real_t *so, const Op3 *op27, const real_t *z, const real_t *p, real_t *pn, real_t *w, int nd,
+                   int nst, int II, int JJ, int KK, bool first, real_t *slab, real_t *sc, hipStream_t st);
+// move: x += alpha p, r -= alpha w; then r.r and by zmode 0 (z = r) / 1 (z = r / diag, written) / 2 (z read) r.z with
+// the new rho and beta (first: beta = 0); zmode 3: r.r only.  diag: the operator's centre slot.  KK = 1 for 2D.
+void pcg_update(int zmode, bool move, real_t *x, real_t *r, const real_t *p, const real_t *w, real_t *z,
+                const real_t *diag, int II, int JJ, int KK, bool first, real_t *slab, real_t *sc, hipStream_t st);
 // gallery.hip (device-side generators of the reference's gallery operators)
 void gallery_fill(int which, real_t *so, real_t *b, int nx, int ny, int nz, const double *params, hipStream_t st);
 

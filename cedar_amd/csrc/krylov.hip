@@ -1,0 +1,384 @@
+// Krylov kernels of the multigrid-preconditioned conjugate gradient (solver.cpp cedar_amd_solver_pcg): the vector
+// work of one CG iteration in three streaming passes, with the scalars (alpha, beta) computed on the device.
+//
+//   pcg_direction  p' = z + beta p, w = A p', sigma = p'.w          (p' in the other buffer of a pair: p is read at
+//                  the stencil neighbours, so it cannot be overwritten in place)
+//   pcg_update     x += alpha p', r -= alpha w, r.r  [precon = diag: z = r / a_ii and r.z fused]
+//                  or, without the x / r update: r.r and r.z of the preconditioned residual
+//
+// Every pass streams the interior only, leaves one partial sum per workgroup in a slab and is followed by a
+// one-workgroup kernel that sums the slab in a fixed order and writes the scalars (pcg_* slots of `sc`).  No float
+// atomics anywhere: a solve is bitwise reproducible run to run.  A q = matvec2 / matvec3 of residual.hip term for term
+// (diagonal first, then the neighbours subtracted in the reference's order), so w equals what matvec would give for p'.
+//
+// Algorithmic bytes per interior point (FP64; operator planes read once, neighbour re-reads are cache hits):
+//   pcg_direction   27-pt: 14 slots x 8 = 112 (row-interleaved copy: 15 x 8 = 120, slot 14 = 1/diag is not read)
+//                          + z, p read 16 + p', w written 16                                   = 144 B (152 interleaved)
+//                   7-pt: 4 x 8 + 32 = 64 B;   2D 9-pt: 5 x 8 + 32 = 72 B;   5-pt: 3 x 8 + 32 = 56 B
+//                   first iteration (p' = z, p not read): 8 B less
+//   pcg_update      x, r read and written 32 + p', w read 16                                    = 48 B
+//                   precon = diag: + a_ii read 8 + z written 8                                  = 64 B
+//   pcg_dots        (pcg_update without the update) r, z read                                   = 16 B
+#include "common.h"
+#include "relax27_dev.h"
+#include <algorithm>
+
+namespace cedar_amd {
+
+namespace {
+
+constexpr int RED_BS = 1024; // the one-workgroup second stage
+
+// block-wide sum, fixed order (wave shuffles, then the waves in index order); valid in thread 0.  lds: BS / 64 doubles
+template <int BS>
+__device__ __forceinline__ real_t block_sum_k(real_t v, real_t *lds)
+{
+#pragma unroll
+	for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+	const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
+	if (l == 0) lds[w] = v;
+	__syncthreads();
+	real_t r = 0.0;
+	if (threadIdx.x == 0)
+		for (int t = 0; t < (int)(blockDim.x + 63) / 64; t++) r += lds[t];
+	__syncthreads(); // lds may be reused by a second sum
+	return r;
+}
+
+// matvec3's 27-point term order (residual.hip residual3_kernel<true, true>) on the row kernels' coefficient set
+__device__ __forceinline__ real_t mv27(real_t d, const C27 &c, const real_t (&qq)[3][3][3])
+{
+	real_t s = d * qq[1][1][1];
+	s = s - c.pw * qq[1][1][0];
+	s = s - c.pnw_n * qq[1][2][0];
+	s = s - c.ps_n * qq[1][2][1];
+	s = s - c.psw_ne * qq[1][2][2];
+	s = s - c.pw_e * qq[1][1][2];
+	s = s - c.pnw_e * qq[1][0][2];
+	s = s - c.ps * qq[1][0][1];
+	s = s - c.psw * qq[1][0][0];
+	s = s - c.b * qq[0][1][1];
+	s = s - c.bw * qq[0][1][0];
+	s = s - c.bnw_n * qq[0][2][0];
+	s = s - c.bn_n * qq[0][2][1];
+	s = s - c.bne_ne * qq[0][2][2];
+	s = s - c.be_e * qq[0][1][2];
+	s = s - c.bse_e * qq[0][0][2];
+	s = s - c.bs * qq[0][0][1];
+	s = s - c.bsw * qq[0][0][0];
+	s = s - c.b_t * qq[2][1][1];
+	s = s - c.be_t * qq[2][1][0];
+	s = s - c.bse_nt * qq[2][2][0];
+	s = s - c.bs_nt * qq[2][2][1];
+	s = s - c.bsw_net * qq[2][2][2];
+	s = s - c.bw_et * qq[2][1][2];
+	s = s - c.bnw_et * qq[2][0][2];
+	s = s - c.bn_t * qq[2][0][1];
+	s = s - c.bne_t * qq[2][0][0];
+	return s;
+}
+
+// ---------------------------------------------------------------- p' = z + beta p, w = A p', partial p'.w
+// 2D: one lane per point, one workgroup per 256-point segment of a row (residual2_kernel's layout)
+template <bool NINE, bool FIRST>
+__global__ __launch_bounds__(256) void pcg_dir2(const real_t *__restrict__ so, const real_t *__restrict__ z,
+                                                const real_t *__restrict__ p, real_t *__restrict__ pn,
+                                                real_t *__restrict__ w, const real_t *__restrict__ sc, int II, int JJ,
+                                                real_t *__restrict__ part)
+{
+	__shared__ real_t lds[4];
+	const int i = blockIdx.x * blockDim.x + threadIdx.x + 1;
+	const int j = blockIdx.y + 1;
+	const real_t beta = FIRST ? 0.0 : sc[PCG_BETA];
+	real_t acc = 0.0;
+	if (i <= II - 2) {
+		const size_t sj = II, PS = (size_t)II * JJ;
+		const size_t x = (size_t)i + sj * (size_t)j;
+		auto P = [&](size_t y) -> real_t { return FIRST ? z[y] : z[y] + beta * p[y]; };
+		const real_t pc = P(x);
+		real_t s = so[KO * PS + x] * pc;
+		s = s - so[KW * PS + x] * P(x - 1);
+		s = s - so[KW * PS + x + 1] * P(x + 1);
+		s = s - so[KS * PS + x] * P(x - sj);
+		s = s - so[KS * PS + x + sj] * P(x + sj);
+		if (NINE) {
+			s = s - so[KSW * PS + x] * P(x - 1 - sj);
+			s = s - so[KNW * PS + x + 1] * P(x + 1 - sj);
+			s = s - so[KNW * PS + x + sj] * P(x - 1 + sj);
+			s = s - so[KSW * PS + x + 1 + sj] * P(x + 1 + sj);
+		}
+		pn[x] = pc;
+		w[x] = s;
+		acc = pc * s;
+	}
+	const real_t t = block_sum_k<256>(acc, lds);
+	if (threadIdx.x == 0) part[blockIdx.x + (size_t)gridDim.x * blockIdx.y] = t;
+}
+
+// 3D 7-point: one workgroup per grid row (residual3_kernel's layout); partial of logical row L at part[L]
+template <bool FIRST>
+__global__ __launch_bounds__(256) void pcg_dir7(const real_t *__restrict__ so, const real_t *__restrict__ z,
+                                                const real_t *__restrict__ p, real_t *__restrict__ pn,
+                                                real_t *__restrict__ w, const real_t *__restrict__ sc, int II, int JJ,
+                                                int KK, unsigned nrows, real_t *__restrict__ part)
+{
+	__shared__ real_t lds[4];
+	const unsigned L = xcd_remap(blockIdx.x, nrows);
+	if (L >= nrows) return; // grid padding of xcd_grid: no slab entry
+	const int j = (int)(L % (unsigned)(JJ - 2)) + 1, k = (int)(L / (unsigned)(JJ - 2)) + 1;
+	const size_t sj = II, sk = (size_t)II * JJ, PS = sk * KK;
+	const real_t beta = FIRST ? 0.0 : sc[PCG_BETA];
+	auto P = [&](size_t y) -> real_t { return FIRST ? z[y] : z[y] + beta * p[y]; };
+	real_t acc = 0.0;
+	for (int i = threadIdx.x + 1; i <= II - 2; i += blockDim.x) {
+		const size_t x = (size_t)i + sj * (size_t)j + sk * (size_t)k;
+		const real_t pc = P(x);
+		real_t s = so[KP * PS + x] * pc;
+		s = s - so[KPW * PS + x] * P(x - 1);
+		s = s - so[KPS * PS + x + sj] * P(x + sj);
+		s = s - so[KPW * PS + x + 1] * P(x + 1);
+		s = s - so[KPS * PS + x] * P(x - sj);
+		s = s - so[KB * PS + x] * P(x - sk);
+		s = s - so[KB * PS + x + sk] * P(x + sk);
+		pn[x] = pc;
+		w[x] = s;
+		acc += pc * s;
+	}
+	const real_t t = block_sum_k<256>(acc, lds);
+	if (threadIdx.x == 0) part[L] = t;
+}
+
+// 3D 27-point: residual27_rows' layout -- lane p owns the pair (2p+1, 2p+2) of its row, 16-byte loads and stores,
+// rows walked in (j,k) tiles; the operator through an Op3 view (Cedar planes or the solver's row-interleaved copy)
+template <int BS, bool FIRST>
+__global__ __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(2))) void pcg_dir27(const Op3 A, const real_t *__restrict__ z, const real_t *__restrict__ p,
+                                                real_t *__restrict__ pn, real_t *__restrict__ w,
+                                                const real_t *__restrict__ sc, int II, int JJ, int KK, unsigned nblk,
+                                                TileShape ts, real_t *__restrict__ part)
+{
+	__shared__ real_t lds[(BS + 63) / 64];
+	const unsigned L = xcd_remap(blockIdx.x, nblk);
+	if (L >= nblk) return; // grid padding: no slab entry
+	unsigned jr, kr;
+	real_t acc = 0.0;
+	if (tile_rows(L, (unsigned)(JJ - 2), (unsigned)(KK - 2), ts, jr, kr)) {
+		const real_t beta = FIRST ? 0.0 : sc[PCG_BETA];
+		const size_t j = (size_t)jr + 1, k = (size_t)kr + 1;
+		const size_t sj = (size_t)II, sk = (size_t)II * JJ;
+		const size_t row = j * sj + k * sk, rowA = j * A.SJ + k * A.SK;
+		for (int q = threadIdx.x; 2 * q + 1 <= II - 2; q += BS) {
+			const int ie = 2 * q + 1, io = 2 * q + 2;
+			const bool o_ok = io <= II - 2, two = io + 1 <= II - 1;
+			C27 ce, co;
+			real_t qe[3][3][3], qo[3][3][3], zfe, zfo, de, dn;
+			// operator coefficients and the 3x3 windows of p (FIRST: of z); qf = z (own pair, a cache hit below)
+			load_pair27<false, false, false>(A, z, FIRST ? z : p, rowA, row, sj, sk, ie, io, two, ce, co, qe, qo, zfe, zfo);
+			ldpair(A.so + rowA + ie, true, de, dn); // KP plane
+			if (!FIRST) {
+#pragma unroll
+				for (int dk = 0; dk < 3; dk++)
+#pragma unroll
+					for (int dj = 0; dj < 3; dj++) {
+						const real_t *r = z + row + (ptrdiff_t)(dj - 1) * (ptrdiff_t)sj + (ptrdiff_t)(dk - 1) * (ptrdiff_t)sk;
+						real_t w0, w1, w2, w3;
+						ldpair(r + ie - 1, true, w0, w1);
+						ldpair(r + io, two, w2, w3);
+						qe[dk][dj][0] = w0 + beta * qe[dk][dj][0];
+						qe[dk][dj][1] = w1 + beta * qe[dk][dj][1];
+						qe[dk][dj][2] = w2 + beta * qe[dk][dj][2];
+						qo[dk][dj][0] = qe[dk][dj][1];
+						qo[dk][dj][1] = qe[dk][dj][2];
+						qo[dk][dj][2] = w3 + beta * qo[dk][dj][2];
+					}
+			}
+			const real_t we = mv27(de, ce, qe);
+			const real_t pe = qe[1][1][1];
+			acc += pe * we;
+			if (o_ok) {
+				const real_t wo = mv27(dn, co, qo);
+				const real_t po = qo[1][1][1];
+				acc += po * wo;
+				d2u v; v.x = we; v.y = wo;
+				*reinterpret_cast<d2u *>(w + row + ie) = v;
+				v.x = pe; v.y = po;
+				*reinterpret_cast<d2u *>(pn + row + ie) = v;
+			} else {
+				w[row + ie] = we;
+				pn[row + ie] = pe;
+			}
+		}
+	}
+	const real_t t = block_sum_k<BS>(acc, lds);
+	if (threadIdx.x == 0) part[L] = t;
+}
+
+// ---------------------------------------------------------------- x / r update and the dots
+// ZM (what z is): 0 = r itself (no preconditioner), 1 = r / a_ii written here (diagonal), 2 = read (multigrid, after
+// the preconditioner), 3 = not involved (multigrid, before it: r.r only).  MOVE: x += alpha p', r -= alpha w first.
+// Rows dealt to a fixed number of workgroups in a fixed pattern; lane q owns the pair (2q+1, 2q+2) of a row.
+template <int ZM, bool MOVE>
+__global__ __launch_bounds__(256) void pcg_upd(real_t *__restrict__ x, real_t *__restrict__ r,
+                                               const real_t *__restrict__ p, const real_t *__restrict__ w,
+                                               real_t *__restrict__ z, const real_t *__restrict__ diag,
+                                               const real_t *__restrict__ sc, int II, int JJ, int KK,
+                                               real_t *__restrict__ part)
+{
+	__shared__ real_t lds[4];
+	const int nj = JJ - 2, nk = KK == 1 ? 1 : KK - 2;
+	const size_t nrows = (size_t)nj * nk;
+	const real_t a = MOVE ? sc[PCG_ALPHA] : 0.0;
+	const bool mv = MOVE && a != 0.0; // alpha = 0 (breakdown): x and r stay as they are
+	real_t rr = 0.0, rz = 0.0;
+	for (size_t t = blockIdx.x; t < nrows; t += gridDim.x) {
+		const size_t j = t % nj + 1, k = KK == 1 ? 0 : t / nj + 1;
+		const size_t row = (size_t)II * (j + (size_t)JJ * k);
+		for (int q = threadIdx.x; 2 * q + 1 <= II - 2; q += blockDim.x) {
+			const size_t ie = row + 2 * q + 1;
+			const bool two = 2 * q + 2 <= II - 2;
+			real_t r0, r1;
+			ldpair(r + ie, two, r0, r1);
+			if (mv) {
+				real_t x0, x1, p0, p1, w0, w1;
+				ldpair(x + ie, two, x0, x1);
+				ldpair(p + ie, two, p0, p1);
+				ldpair(w + ie, two, w0, w1);
+				x0 = x0 + a * p0; x1 = x1 + a * p1;
+				r0 = r0 - a * w0; r1 = r1 - a * w1;
+				if (two) {
+					d2u v; v.x = x0; v.y = x1; *reinterpret_cast<d2u *>(x + ie) = v;
+					v.x = r0; v.y = r1; *reinterpret_cast<d2u *>(r + ie) = v;
+				} else {
+					x[ie] = x0; r[ie] = r0;
+				}
+			}
+			rr += r0 * r0;
+			if (two) rr += r1 * r1;
+			if (ZM == 1) {
+				real_t d0, d1;
+				ldpair(diag + ie, two, d0, d1);
+				const real_t z0 = r0 / d0, z1 = two ? r1 / d1 : 0.0;
+				if (two) { d2u v; v.x = z0; v.y = z1; *reinterpret_cast<d2u *>(z + ie) = v; }
+				else z[ie] = z0;
+				rz += r0 * z0;
+				if (two) rz += r1 * z1;
+			} else if (ZM == 2) {
+				real_t z0, z1;
+				ldpair(z + ie, two, z0, z1);
+				rz += r0 * z0;
+				if (two) rz += r1 * z1;
+			}
+		}
+	}
+	const real_t s0 = block_sum_k<256>(rr, lds);
+	const real_t s1 = (ZM == 1 || ZM == 2) ? block_sum_k<256>(rz, lds) : 0.0;
+	if (threadIdx.x == 0) {
+		part[blockIdx.x] = s0;
+		part[gridDim.x + blockIdx.x] = s1;
+	}
+}
+
+// ---------------------------------------------------------------- second stages (one workgroup)
+__device__ __forceinline__ real_t slab_sum(const real_t *__restrict__ part, unsigned n, real_t *lds)
+{
+	real_t acc = 0.0;
+	for (unsigned i = threadIdx.x; i < n; i += RED_BS) acc += part[i];
+	return block_sum_k<RED_BS>(acc, lds);
+}
+
+// sigma = sum of the slab; alpha = rho / sigma, or 0 with the breakdown flag when sigma <= 0 (or not finite) or rho = 0
+__global__ __launch_bounds__(RED_BS) void pcg_alpha(const real_t *__restrict__ part, unsigned n, real_t *__restrict__ sc)
+{
+	__shared__ real_t lds[RED_BS / 64];
+	const real_t sigma = slab_sum(part, n, lds);
+	if (threadIdx.x == 0) {
+		const real_t rho = sc[PCG_RHO];
+		const bool ok = sigma > 0.0 && sigma <= 1.7976931348623157e308 && rho != 0.0;
+		sc[PCG_SIGMA] = sigma;
+		sc[PCG_ALPHA] = ok ? rho / sigma : 0.0;
+		if (!ok) sc[PCG_FLAG] = 1.0;
+	}
+}
+
+// r.r (slab 0) and, when has_rz, r.z (slab 1; zm0: r.z = r.r): the new rho, beta = rho_new / rho_old (first: 0)
+__global__ __launch_bounds__(RED_BS) void pcg_rho(const real_t *__restrict__ part, unsigned n, int has_rz, int first,
+                                                  real_t *__restrict__ sc)
+{
+	__shared__ real_t lds[RED_BS / 64];
+	const real_t rr = slab_sum(part, n, lds);
+	const real_t rz = has_rz == 1 ? slab_sum(part + n, n, lds) : rr;
+	if (threadIdx.x == 0) {
+		sc[PCG_RR] = rr;
+		if (has_rz) {
+			const real_t rho = sc[PCG_RHO];
+			sc[PCG_RZ] = rz;
+			sc[PCG_BETA] = first || rho == 0.0 ? 0.0 : rz / rho;
+			sc[PCG_RHO] = rz;
+		}
+	}
+}
+
+constexpr unsigned UPD_NB = 2048;
+
+} // namespace
+
+size_t pcg_slab_doubles(int nd, int nst, int II, int JJ, int KK)
+{
+	size_t n = 2 * (size_t)UPD_NB;
+	if (nd == 2) n = std::max(n, (size_t)((II - 2 + 255) / 256) * (size_t)(JJ - 2));
+	else if (nst == 14) n = std::max(n, (size_t)tile_blocks((unsigned)(JJ - 2), (unsigned)(KK - 2), tile_shape_resid()));
+	else n = std::max(n, (size_t)(JJ - 2) * (size_t)(KK - 2));
+	return n;
+}
+
+void pcg_direction(const real_t *so, const Op3 *op27, const real_t *z, const real_t *p, real_t *pn, real_t *w, int nd,
+                   int nst, int II, int JJ, int KK, bool first, real_t *slab, real_t *sc, hipStream_t st)
+{
+	unsigned n = 0;
+	if (nd == 2) {
+		dim3 grid((II - 2 + 255) / 256, JJ - 2);
+		n = grid.x * grid.y;
+#define L2_(NINE, F) hipLaunchKernelGGL((pcg_dir2<NINE, F>), grid, dim3(256), 0, st, so, z, p, pn, w, sc, II, JJ, slab)
+		if (nst == 5) { if (first) L2_(true, true); else L2_(true, false); }
+		else { if (first) L2_(false, true); else L2_(false, false); }
+#undef L2_
+	} else if (nst == 4) {
+		n = (unsigned)(JJ - 2) * (unsigned)(KK - 2);
+		const int bs = II - 2 >= 256 ? 256 : (II - 2 > 64 ? 128 : 64);
+		if (first) hipLaunchKernelGGL(pcg_dir7<true>, dim3(xcd_grid(n)), dim3(bs), 0, st, so, z, p, pn, w, sc, II, JJ, KK, n, slab);
+		else hipLaunchKernelGGL(pcg_dir7<false>, dim3(xcd_grid(n)), dim3(bs), 0, st, so, z, p, pn, w, sc, II, JJ, KK, n, slab);
+	} else {
+		const Op3 A = op27 ? *op27 : op3_cedar(so, nullptr, II, JJ, KK);
+		const TileShape ts = tile_shape_resid();
+		n = tile_blocks((unsigned)(JJ - 2), (unsigned)(KK - 2), ts);
+		const int npairs = (II - 2 + 1) / 2;
+#define L27_(BS, F) hipLaunchKernelGGL((pcg_dir27<BS, F>), dim3(xcd_grid(n)), dim3(BS), 0, st, A, z, p, pn, w, sc, II, JJ, KK, n, ts, slab)
+		if (npairs <= 64) { if (first) L27_(64, true); else L27_(64, false); }
+		else if (npairs <= 128) { if (first) L27_(128, true); else L27_(128, false); }
+		else { if (first) L27_(256, true); else L27_(256, false); }
+#undef L27_
+	}
+	hipLaunchKernelGGL(pcg_alpha, dim3(1), dim3(RED_BS), 0, st, slab, n, sc);
+}
+
+void pcg_update(int zmode, bool move, real_t *x, real_t *r, const real_t *p, const real_t *w, real_t *z,
+                const real_t *diag, int II, int JJ, int KK, bool first, real_t *slab, real_t *sc, hipStream_t st)
+{
+	const size_t nrows = (size_t)(JJ - 2) * (KK == 1 ? 1 : KK - 2);
+	const unsigned nb = (unsigned)std::min<size_t>(UPD_NB, nrows);
+#define LU_(ZM, MV) hipLaunchKernelGGL((pcg_upd<ZM, MV>), dim3(nb), dim3(256), 0, st, x, r, p, w, z, diag, sc, II, JJ, KK, slab)
+	switch (zmode * 2 + (move ? 1 : 0)) {
+	case 0: LU_(0, false); break;
+	case 1: LU_(0, true); break;
+	case 2: LU_(1, false); break;
+	case 3: LU_(1, true); break;
+	case 4: LU_(2, false); break;
+	case 5: LU_(2, true); break;
+	case 6: LU_(3, false); break;
+	default: LU_(3, true); break;
+	}
+#undef LU_
+	const int has_rz = zmode == 3 ? 0 : zmode == 0 ? 2 : 1; // 2: r.z = r.r
+	hipLaunchKernelGGL(pcg_rho, dim3(1), dim3(RED_BS), 0, st, slab, nb, has_rz, first ? 1 : 0, sc);
+}
+
+} // namespace cedar_amd

@@ -111,6 +111,10 @@ struct cedar_amd_solver {
 	std::vector<hipStream_t> pstreams;
 	std::vector<hipEvent_t> pevents;
 	hipEvent_t pfork = nullptr;
+	// preconditioned conjugate gradient (cedar_amd_solver_pcg), allocated on the first call: level-0 vectors r, z, w and
+	// the pair of directions (p is read at the stencil neighbours while p' is written), partial-sum slab, device scalars
+	real_t *kr = nullptr, *kz = nullptr, *kw = nullptr, *kp[2] = {nullptr, nullptr};
+	real_t *kslab = nullptr, *ksc = nullptr;
 };
 
 namespace {
@@ -775,6 +779,8 @@ void cedar_amd_solver_destroy(cedar_amd_solver *s)
 		(void)hipFree(L.res); (void)hipFree(L.yscr); (void)hipFree(L.bt); (void)hipFree(L.xt); (void)hipFree(L.T);
 		if (l > 0) { (void)hipFree(L.x); (void)hipFree(L.b); }
 	}
+	(void)hipFree(s->kr); (void)hipFree(s->kz); (void)hipFree(s->kw); (void)hipFree(s->kp[0]); (void)hipFree(s->kp[1]);
+	(void)hipFree(s->kslab); (void)hipFree(s->ksc);
 	if (!s->shared_abd) (void)hipFree(s->ABD);
 	(void)hipFree(s->bbd); (void)hipFree(s->red); (void)hipFree(s->dinfo);
 	for (auto t : s->pstreams) (void)hipStreamDestroy(t);
@@ -883,6 +889,143 @@ int cedar_amd_solver_solve(cedar_amd_solver *s, const real_t *b, real_t *x, real
 	}
 	launch_check("cedar_amd_solver_solve");
 	return it;
+}
+
+// ---- preconditioned conjugate gradient (BoxMG's PCG: src/{2d,3d}/ftn/BMG_PCG_parameters_f90.h) on the resident
+// hierarchy.  The multigrid preconditioner z = M^-1 r is nmg_cycles cycles from z = 0 on the solver's own (z, r) pair,
+// so its captured graph is recorded once.  The vector work is krylov.hip; per iteration the host reads the device
+// scalars once (PCG_NSC doubles) for the stop test.
+void cedar_amd_default_pcg_settings(cedar_amd_pcg_settings *p)
+{
+	p->max_iter = 50;
+	p->tol = 1e-8;
+	p->stop_test = CEDAR_AMD_PCG_STOP_REL_RES_L2;
+	p->precon = CEDAR_AMD_PCG_PRECON_BMG;
+	p->nmg_cycles = 1;
+}
+
+// settings the solver cannot honour: reported, and the caller's vectors are left alone
+static bool pcg_refused(const cedar_amd_solver *s, const cedar_amd_pcg_settings &p, const char *who)
+{
+	const char *why = nullptr;
+	if (s->st.ibc != 0) why = "periodic boundary conditions (ibc != 0) are not supported";
+	else if (p.stop_test < CEDAR_AMD_PCG_STOP_ABS_RES_L2 || p.stop_test > CEDAR_AMD_PCG_STOP_REL_RES_M2) why = "stop_test must be 0..3";
+	else if (p.precon < CEDAR_AMD_PCG_PRECON_NONE || p.precon > CEDAR_AMD_PCG_PRECON_BMG) why = "precon must be 1..3";
+	else if (p.max_iter < 0) why = "max_iter must not be negative";
+	else if (p.precon == CEDAR_AMD_PCG_PRECON_BMG) {
+		if (s->st.cycle != 0) why = "the multigrid preconditioner must be a V-cycle (an F-cycle is not symmetric)";
+		else if (s->st.nrelax_pre != s->st.nrelax_post) why = "the multigrid preconditioner needs nrelax_pre == nrelax_post (symmetric V-cycle)";
+		else if (s->st.relaxation >= CEDAR_AMD_RELAX_PLANE_XY && s->st.plane_nrelax_pre != s->st.plane_nrelax_post)
+			why = "plane relaxation in the preconditioner needs plane_nrelax_pre == plane_nrelax_post (symmetric plane solves)";
+		else if (p.nmg_cycles < 1) why = "nmg_cycles must be at least 1";
+	}
+	if (!why) return false;
+	char msg[256];
+	snprintf(msg, sizeof(msg), "%s: %s; nothing done", who, why);
+	print_error(msg);
+	return true;
+}
+
+static void pcg_alloc(cedar_amd_solver *s)
+{
+	if (s->kr) return;
+	const Level &L = s->lv[0];
+	// zero-filled: ghost entries stay zero (the kernels write interiors only)
+	s->kr = dalloc(L.npts); s->kz = dalloc(L.npts); s->kw = dalloc(L.npts);
+	s->kp[0] = dalloc(L.npts); s->kp[1] = dalloc(L.npts);
+	s->kslab = dalloc_raw(pcg_slab_doubles(s->nd, L.nst, L.II, L.JJ, L.KK));
+	s->ksc = dalloc(PCG_NSC);
+}
+
+// z = M^-1 r on the solver's own vectors: z = 0, then nmg V-cycles
+static void pcg_precondition(cedar_amd_solver *s, int nmg, hipStream_t st)
+{
+	clear(s->kz, s->lv[0].npts, st);
+	for (int c = 0; c < nmg; c++) cycle_on(s, s->kz, s->kr, st);
+}
+
+static void pcg_scalars(cedar_amd_solver *s, double *sc, hipStream_t st)
+{
+	CEDAR_HIP_CHECK(hipMemcpyAsync(sc, s->ksc, PCG_NSC * sizeof(double), hipMemcpyDeviceToHost, st));
+	CEDAR_HIP_CHECK(hipStreamSynchronize(st));
+}
+
+int cedar_amd_solver_pcg(cedar_amd_solver *s, const real_t *b, real_t *x, const cedar_amd_pcg_settings *settings, real_t *hist)
+{
+	if (null_handle(s, "cedar_amd_solver_pcg")) return -1;
+	cedar_amd_pcg_settings p;
+	if (settings) p = *settings;
+	else cedar_amd_default_pcg_settings(&p);
+	if (pcg_refused(s, p, "cedar_amd_solver_pcg")) return -1;
+	pcg_alloc(s);
+	Level &L = s->lv[0];
+	hipStream_t st = current_stream();
+	Staged sx(x, L.npts, true, true), sb(b, L.npts, true, false);
+	real_t *X = sx.get();
+	const int zm = p.precon == CEDAR_AMD_PCG_PRECON_NONE ? 0 : p.precon == CEDAR_AMD_PCG_PRECON_DIAG ? 1 : 2;
+	real_t *Z = zm == 0 ? s->kr : s->kz;
+	const Op3 ilv = L.Ailv ? op3_ilv(L.Ailv, L.II, L.JJ, L.KK) : Op3{};
+	const bool mnorm = p.stop_test >= CEDAR_AMD_PCG_STOP_ABS_RES_M2;
+	const bool rel = p.stop_test == CEDAR_AMD_PCG_STOP_REL_RES_L2 || p.stop_test == CEDAR_AMD_PCG_STOP_REL_RES_M2;
+	double sc[PCG_NSC];
+
+	// r0 = b - A x0, z0 = M^-1 r0, rho0 = r0.z0 (pcg_update without the update)
+	zero_fill(s->ksc, PCG_NSC, st);
+	residual(s, L, X, sb.get(), s->kr, st);
+	if (zm == 2) pcg_precondition(s, p.nmg_cycles, st);
+	pcg_update(zm, false, X, s->kr, nullptr, nullptr, Z, L.A, L.II, L.JJ, L.KK, true, s->kslab, s->ksc, st);
+	pcg_scalars(s, sc, st);
+	const double r0 = std::sqrt(sc[PCG_RR]), m0 = std::sqrt(sc[PCG_RZ] > 0 ? sc[PCG_RZ] : 0.0);
+	if (hist) hist[0] = r0;
+	auto stop = [&](double rr, double rz) {
+		const double v = mnorm ? std::sqrt(rz > 0 ? rz : 0.0) : std::sqrt(rr);
+		return (rel ? v / (mnorm ? m0 : r0) : v) < p.tol;
+	};
+	// b = A x0 exactly, r0.z0 <= 0 (M not positive definite on r0), or already converged
+	if (r0 == 0.0 || !(sc[PCG_RZ] > 0) || stop(sc[PCG_RR], sc[PCG_RZ])) {
+		launch_check("cedar_amd_solver_pcg");
+		return 0;
+	}
+	int it = 0;
+	for (int k = 0; k < p.max_iter; k++) {
+		real_t *pold = s->kp[(k + 1) & 1], *pn = s->kp[k & 1];
+		pcg_direction(L.A, L.Ailv ? &ilv : nullptr, Z, pold, pn, s->kw, s->nd, L.nst, L.II, L.JJ, L.KK, k == 0, s->kslab,
+		              s->ksc, st);
+		pcg_update(zm == 2 ? 3 : zm, true, X, s->kr, pn, s->kw, Z, L.A, L.II, L.JJ, L.KK, false, s->kslab, s->ksc, st);
+		const bool last = k + 1 == p.max_iter;
+		if (zm == 2 && mnorm) { // the M-norm of the new residual needs its preconditioned form first
+			pcg_precondition(s, p.nmg_cycles, st);
+			pcg_update(2, false, X, s->kr, nullptr, nullptr, Z, L.A, L.II, L.JJ, L.KK, false, s->kslab, s->ksc, st);
+		}
+		pcg_scalars(s, sc, st);
+		if (sc[PCG_FLAG] != 0) break; // breakdown (p.Ap <= 0 or rho = 0): alpha was 0, x is as it was
+		it = k + 1;
+		if (hist) hist[it] = std::sqrt(sc[PCG_RR]) / r0;
+		if (stop(sc[PCG_RR], sc[PCG_RZ])) break;
+		if (zm == 2 && !mnorm && !last) {
+			pcg_precondition(s, p.nmg_cycles, st);
+			pcg_update(2, false, X, s->kr, nullptr, nullptr, Z, L.A, L.II, L.JJ, L.KK, false, s->kslab, s->ksc, st);
+		}
+	}
+	launch_check("cedar_amd_solver_pcg");
+	return it;
+}
+
+void cedar_amd_solver_precondition(cedar_amd_solver *s, real_t *z, const real_t *r)
+{
+	if (null_handle(s, "cedar_amd_solver_precondition")) return;
+	cedar_amd_pcg_settings p;
+	cedar_amd_default_pcg_settings(&p);
+	if (pcg_refused(s, p, "cedar_amd_solver_precondition")) return;
+	pcg_alloc(s);
+	const Level &L = s->lv[0];
+	hipStream_t st = current_stream();
+	Staged sz(z, L.npts, false, true), sr(r, L.npts, true, false);
+	CEDAR_HIP_CHECK(hipMemcpyAsync(s->kr, sr.get(), L.npts * sizeof(real_t), hipMemcpyDeviceToDevice, st));
+	pcg_precondition(s, 1, st);
+	CEDAR_HIP_CHECK(hipMemcpyAsync(sz.get(), s->kz, L.npts * sizeof(real_t), hipMemcpyDeviceToDevice, st));
+	CEDAR_HIP_CHECK(hipStreamSynchronize(st));
+	launch_check("cedar_amd_solver_precondition");
 }
 
 // ---- plane relaxation as a kernel of its own: kernels::plane_relax<stypes, rdir>::setup / run

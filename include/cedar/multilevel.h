@@ -14,6 +14,7 @@
 #ifndef CEDAR_MULTILEVEL_H
 #define CEDAR_MULTILEVEL_H
 #include <cmath>
+#include <cstdlib>
 #include <cstring>
 #include <functional>
 #include <memory>
@@ -104,6 +105,40 @@ public:
 			history.push_back(rel_l2);
 			if (rel_l2 < settings.tol) break;
 		}
+	}
+
+	// conjugate gradients preconditioned by the cycle (cedar_amd_solver_pcg), configured by the keys pcg.max-iter,
+	// pcg.tol, pcg.stop-test (BoxMG's 0..3 or abs-l2 / rel-l2 / abs-m / rel-m), pcg.precon (1..3 or none / diag / mg) and
+	// pcg.nmg-cycles; `history` as after solve().  Resident path only.
+	void pcg(const grid_func & b, grid_func & x)
+	{
+		history.clear();
+		if (!resident()) {
+			log::error << "pcg: needs the device-resident solver (every kernel \"hip\")" << std::endl;
+			return;
+		}
+		cedar_amd_pcg_settings ps;
+		cedar_amd_default_pcg_settings(&ps);
+		auto pick = [this](const char * key, int dflt, const char * const * names, int first) {
+			const std::string v = conf->get<std::string>(key, "");
+			if (v.empty()) return dflt;
+			for (int i = 0; names[i]; i++)
+				if (v == names[i]) return first + i;
+			return std::atoi(v.c_str());
+		};
+		static const char * const stops[] = {"abs-l2", "rel-l2", "abs-m", "rel-m", nullptr};
+		static const char * const precons[] = {"none", "diag", "mg", nullptr};
+		ps.max_iter = conf->get<int>("pcg.max-iter", ps.max_iter);
+		ps.tol = conf->get<real_t>("pcg.tol", ps.tol);
+		ps.stop_test = pick("pcg.stop-test", ps.stop_test, stops, CEDAR_AMD_PCG_STOP_ABS_RES_L2);
+		ps.precon = pick("pcg.precon", ps.precon, precons, CEDAR_AMD_PCG_PRECON_NONE);
+		ps.nmg_cycles = conf->get<int>("pcg.nmg-cycles", ps.nmg_cycles);
+		std::vector<real_t> rel(ps.max_iter > 0 ? ps.max_iter + 1 : 1);
+		int n = cedar_amd_solver_pcg(h, b.data(), x.data(), &ps, rel.data());
+		if (n < 0) return;
+		log::info << "Initial residual l2 norm: " << rel[0] << std::endl;
+		for (int i = 0; i < n; i++) log::status << "PCG iteration " << i << " relative l2 norm: " << rel[i + 1] << std::endl;
+		history.assign(rel.begin(), rel.begin() + n + 1);
 	}
 
 	void vcycle(grid_func & x, const grid_func & b)

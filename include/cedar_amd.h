@@ -324,6 +324,37 @@ float cedar_amd_solver_time_relax(cedar_amd_solver *s, real_t *x_dev, const real
  * returns elapsed milliseconds (HIP events on the library's stream) */
 float cedar_amd_solver_time_op(cedar_amd_solver *s, real_t *x_dev, const real_t *b_dev, int op, int n);
 
+/* Conjugate gradients preconditioned by the solver's multigrid cycle (BoxMG's PCG).  The numbering is BoxMG's,
+ * src/{2d,3d}/ftn/BMG_PCG_parameters_f90.h:
+ *   stop_test  BMG_PCG_STOP_ABS_RES_L2 = 0, BMG_PCG_STOP_REL_RES_L2 = 1 (||r||_2 absolute / relative to ||r0||_2),
+ *              BMG_PCG_STOP_ABS_RES_M2 = 2, BMG_PCG_STOP_REL_RES_M2 = 3 (the M-norm sqrt(r.z), z = M^-1 r);
+ *   precon     BMG_PCG_PRECON_NONE = 1, BMG_PCG_PRECON_DIAG = 2 (z = r / a_ii), BMG_PCG_PRECON_BMG = 3 (z = nmg_cycles
+ *              cycles of the solver from z = 0).
+ * The multigrid preconditioner must be symmetric: a V-cycle with nrelax_pre == nrelax_post (any relaxation; plane
+ * relaxation also plane_nrelax_pre == plane_nrelax_post).  F-cycles, V(m,n) with m != n and periodic boundaries
+ * (ibc != 0) are refused: print_error, x untouched, return -1.  Plane relaxation builds every plane solver of a level
+ * from the coefficients of its last plane (as the reference does), so the preconditioner is exactly symmetric only
+ * where the planes of each smoothed level share their coefficients. */
+enum { CEDAR_AMD_PCG_STOP_ABS_RES_L2 = 0, CEDAR_AMD_PCG_STOP_REL_RES_L2 = 1,
+       CEDAR_AMD_PCG_STOP_ABS_RES_M2 = 2, CEDAR_AMD_PCG_STOP_REL_RES_M2 = 3 };
+enum { CEDAR_AMD_PCG_PRECON_NONE = 1, CEDAR_AMD_PCG_PRECON_DIAG = 2, CEDAR_AMD_PCG_PRECON_BMG = 3 };
+typedef struct {
+	int max_iter;     /* MAX_ITERS (50) */
+	double tol;       /* STOP_TOL (1e-8) */
+	int stop_test;    /* STOP_TEST (1: relative L2) */
+	int precon;       /* PRECON (3: multigrid) */
+	int nmg_cycles;   /* NMG_CYCLES (1) */
+} cedar_amd_pcg_settings;
+void cedar_amd_default_pcg_settings(cedar_amd_pcg_settings *p);
+/* Solve A x = b from the x given.  hist (max_iter + 1 entries, may be NULL): hist[0] = ||r0||_2,
+ * hist[i] = ||r_i||_2 / ||r0||_2 (as cedar_amd_solver_solve).  b, x host or device; p NULL = the defaults.
+ * Returns the iterations run, -1 when refused.  Stops early on breakdown (p.Ap <= 0 or r.z = 0) with x finite.
+ * The first call allocates five level-0 vectors that the handle keeps until cedar_amd_solver_destroy. */
+int cedar_amd_solver_pcg(cedar_amd_solver *s, const real_t *b, real_t *x, const cedar_amd_pcg_settings *p, real_t *hist);
+/* z = M^-1 r: one cycle of the solver from z = 0 (the preconditioner of cedar_amd_solver_pcg with nmg_cycles = 1);
+ * z, r host or device.  Refused (z untouched) on the settings cedar_amd_solver_pcg refuses for precon = 3. */
+void cedar_amd_solver_precondition(cedar_amd_solver *s, real_t *z, const real_t *r);
+
 /* plane relaxation as a kernel of its own -- kernels::plane_relax<stypes, rdir>::setup(so) / run(so, x, b, dir)
  * (include/cedar/kernels/plane_relax.h:10-33; include/cedar/3d/relax_planes.h:164-246, src/3d/relax_planes.cc).
  * dir 0 = xy planes, 1 = xz, 2 = yz; plane_settings = the 2D solvers' configuration (NULL: the reference's default
