@@ -77,6 +77,8 @@ static inline Op3 op3_ilv(const real_t *a, int II, int JJ, int KK)
 // returns 1 when a copy was built (levels with at least min_rows rows that fit the card's free memory)
 int relax3_prepare(const real_t *so, const real_t *sor, int II, int JJ, int KK, int min_rows, hipStream_t st);
 void relax3_release(const real_t *so);
+// the operator view the sweeps of a registered operator read: its row-interleaved copy where there is one, else the planes
+Op3 relax3_op_view(const real_t *so, int II, int JJ, int KK);
 // build the row-interleaved copy from the Cedar-layout operator (14 slots) and 1/diag plane (relax3d.hip)
 void ilv_build(const real_t *so, const real_t *sor_msor, real_t *ilv, int II, int JJ, int KK, hipStream_t st);
 
@@ -246,11 +248,27 @@ size_t pcg_slab_doubles(int nd, int nst, int II, int JJ, int KK); // partial-sum
 // pn = z + beta p (first: pn = z), w = A pn, sigma = pn.w, alpha = rho / sigma (0 and PCG_FLAG = 1 when sigma <= 0 or
 // rho = 0); op27: the operator view of a 27-point level (nullptr: the Cedar planes of so)
 void pcg_direction(const real_t *so, const Op3 *op27, const real_t *z, const real_t *p, real_t *pn, real_t *w, int nd,
-                   int nst, int II, int JJ, int KK, bool first, real_t *slab, real_t *sc, hipStream_t st);
+                   int nst, int II, int JJ, int KK, bool first, real_t *slab, real_t *sc, hipStream_t st,
+                   real_t *partial = nullptr);
 // move: x += alpha p, r -= alpha w; then r.r and by zmode 0 (z = r) / 1 (z = r / diag, written) / 2 (z read) r.z with
 // the new rho and beta (first: beta = 0); zmode 3: r.r only.  diag: the operator's centre slot.  KK = 1 for 2D.
 void pcg_update(int zmode, bool move, real_t *x, real_t *r, const real_t *p, const real_t *w, real_t *z,
-                const real_t *diag, int II, int JJ, int KK, bool first, real_t *slab, real_t *sc, hipStream_t st);
+                const real_t *diag, int II, int JJ, int KK, bool first, real_t *slab, real_t *sc, hipStream_t st,
+                real_t *partial = nullptr);
+// On a rank grid (dist_common.h dist_pcg) the two launchers above get `partial`: instead of the one-rank second stage they
+// leave this rank's slab sums there (direction: sigma; update: r.r, and r.z unless zmode 0; zmode 3: nothing -- r.r is
+// gathered with r.z after the preconditioner).  After the all-gather of `stride` doubles per rank, the _ranks kernels
+// sum the partials in rank order and set the scalars as the one-rank stages do (world = 1: the same values bit for bit).
+void pcg_ranks_alpha(const real_t *gathered, int world, int stride, real_t *sc, hipStream_t st);
+void pcg_ranks_rho(int zmode, const real_t *gathered, int world, int stride, bool first, real_t *sc, hipStream_t st);
+// pn = z + beta p (first: pn = z) on up to 26 boxes (i0, j0, k0, ni, nj, nk) of a box of II x JJ rows: the ghost cells
+// of a rank box that its neighbours own
+struct ShellBoxes {
+	int n = 0;
+	int box[26 * 6];
+};
+void pcg_ghost_shell(const real_t *z, const real_t *p, real_t *pn, const real_t *sc, const ShellBoxes &bx, int II, int JJ,
+                     bool first, hipStream_t st);
 // gallery.hip (device-side generators of the reference's gallery operators)
 void gallery_fill(int which, real_t *so, real_t *b, int nx, int ny, int nz, const double *params, hipStream_t st);
 

@@ -438,6 +438,7 @@ void cedar_amd_dist2_destroy(cedar_amd_dist2 *d)
 	}
 	for (auto &kv : d->gbuf) { cedar_amd_free(kv.second.first); cedar_amd_free(kv.second.second); }
 	cedar_amd_free(d->gA); cedar_amd_free(d->gx); cedar_amd_free(d->gb); cedar_amd_free(d->cs_tmp); cedar_amd_free(d->scal);
+	krylov_free(d);
 	if (d->side) cedar_amd_stream_destroy(d->side);
 	delete d;
 }
@@ -469,6 +470,33 @@ int cedar_amd_dist2_solve(cedar_amd_dist2 *d, real_t *b, real_t *x, real_t *rel)
 	}
 	launch_check("cedar_amd_dist2_solve");
 	return it;
+}
+
+// preconditioned conjugate gradient on the rank grid (dist_common.h dist_pcg): the 5- / 9-point level-0 box (one plane),
+// the distributed V-cycle with its point or line smoother as the preconditioner
+int cedar_amd_dist2_pcg(cedar_amd_dist2 *d, real_t *b, real_t *x, const cedar_amd_pcg_settings *p, real_t *hist)
+{
+	if (!d) return -1;
+	DLevel2 &L = d->lv[0];
+	const PcgBox B{2, L.nst, L.II, L.JJ, 1, L.npts, L.A, nullptr, &L.halo};
+	const int it = dist_pcg(d, B, d->pre, d->post, b, x, p, hist, "cedar_amd_dist2_pcg",
+	                        [&](real_t *xx, const real_t *bb, real_t *r) {
+		                        int k = 0, kf = 0, ifd = L.nst == 3, nst = L.nst, zero = 0;
+		                        len_t II = (len_t)L.II, JJ = (len_t)L.JJ;
+		                        BMG2_SymStd_residual(&k, L.A, const_cast<real_t *>(bb), xx, r, &II, &JJ, &kf, &ifd, &nst, &zero, &zero, &zero, &zero);
+	                        },
+	                        [&](real_t *xx, real_t *bb) { vcycle(d, xx, bb); });
+	launch_check("cedar_amd_dist2_pcg");
+	return it;
+}
+
+void cedar_amd_dist2_precondition(cedar_amd_dist2 *d, real_t *z, real_t *r)
+{
+	if (!d) return;
+	DLevel2 &L = d->lv[0];
+	const PcgBox B{2, L.nst, L.II, L.JJ, 1, L.npts, L.A, nullptr, &L.halo};
+	dist_precondition(d, B, d->pre, d->post, z, r, "cedar_amd_dist2_precondition", [&](real_t *xx, real_t *bb) { vcycle(d, xx, bb); });
+	launch_check("cedar_amd_dist2_precondition");
 }
 
 float cedar_amd_dist2_time_relax(cedar_amd_dist2 *d, real_t *x, real_t *b, int n)

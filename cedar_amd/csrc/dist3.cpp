@@ -511,6 +511,7 @@ void cedar_amd_dist3_destroy(cedar_amd_dist3 *d)
 	}
 	for (auto &kv : d->gbuf) { cedar_amd_free(kv.second.first); cedar_amd_free(kv.second.second); }
 	cedar_amd_free(d->gA); cedar_amd_free(d->gx); cedar_amd_free(d->gb); cedar_amd_free(d->cs_tmp); cedar_amd_free(d->scal);
+	krylov_free(d);
 	if (d->side) cedar_amd_stream_destroy(d->side);
 	delete d;
 }
@@ -551,6 +552,32 @@ int cedar_amd_dist3_solve(cedar_amd_dist3 *d, real_t *b, real_t *x, real_t *rel)
 	}
 	launch_check("cedar_amd_dist3_solve");
 	return it;
+}
+
+// preconditioned conjugate gradient on the rank grid (dist_common.h dist_pcg): the 7- / 27-point level-0 box, the
+// distributed V-cycle as the preconditioner; the 27-point pass reads the row-interleaved copy where setup registered one
+int cedar_amd_dist3_pcg(cedar_amd_dist3 *d, real_t *b, real_t *x, const cedar_amd_pcg_settings *p, real_t *hist)
+{
+	if (!d) return -1;
+	DLevel &L = d->lv[0];
+	const Op3 view = L.nst == 14 ? relax3_op_view(L.A, L.II, L.JJ, L.KK) : Op3{};
+	const PcgBox B{3, L.nst, L.II, L.JJ, L.KK, L.npts, L.A, L.nst == 14 ? &view : nullptr, &L.halo};
+	const int it = dist_pcg(d, B, d->pre, d->post, b, x, p, hist, "cedar_amd_dist3_pcg",
+	                        [&](real_t *xx, const real_t *bb, real_t *r) {
+		                        BMG3_SymStd_residual(1, 1, L.nst == 4, xx, const_cast<real_t *>(bb), L.A, r, L.II, L.JJ, L.KK, L.nst);
+	                        },
+	                        [&](real_t *xx, real_t *bb) { vcycle(d, xx, bb); });
+	launch_check("cedar_amd_dist3_pcg");
+	return it;
+}
+
+void cedar_amd_dist3_precondition(cedar_amd_dist3 *d, real_t *z, real_t *r)
+{
+	if (!d) return;
+	DLevel &L = d->lv[0];
+	const PcgBox B{3, L.nst, L.II, L.JJ, L.KK, L.npts, L.A, nullptr, &L.halo};
+	dist_precondition(d, B, d->pre, d->post, z, r, "cedar_amd_dist3_precondition", [&](real_t *xx, real_t *bb) { vcycle(d, xx, bb); });
+	launch_check("cedar_amd_dist3_precondition");
 }
 
 // n level-0 relax sweeps alternating DOWN / UP with their halo exchanges (the roofline microbenchmark of the

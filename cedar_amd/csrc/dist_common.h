@@ -34,6 +34,14 @@ struct Halo {
 	std::map<long, std::pair<real_t *, real_t *>> bufs;
 };
 
+// the level-0 vectors of the preconditioned conjugate gradient (dist_pcg), allocated on its first call
+struct Krylov {
+	real_t *r = nullptr, *z = nullptr, *w = nullptr, *p[2] = {nullptr, nullptr};
+	real_t *slab = nullptr, *sc = nullptr;
+	real_t *part = nullptr, *gath = nullptr; // this rank's partial sums (2 doubles) and every rank's (2 x world), rank order
+	ShellBoxes shell;                        // the ghost cells the neighbours own
+};
+
 // what a rank knows about itself and how it talks to the others
 struct RankCtx {
 	cedar_amd_comm *comm = nullptr;
@@ -43,6 +51,7 @@ struct RankCtx {
 	void *side = nullptr; // non-blocking side stream of the overlapped y/z halo
 	bool pending = false;
 	real_t *scal = nullptr;
+	Krylov kry;
 };
 
 static inline real_t *dmalloc(size_t n)
@@ -255,6 +264,149 @@ static inline void side_wait(RankCtx *d)
 	if (!d->pending) return;
 	cedar_amd_stream_wait(cedar_amd_get_stream(), d->side);
 	d->pending = false;
+}
+
+// ---- preconditioned conjugate gradient on a rank grid (cedar_amd_dist3_pcg / cedar_amd_dist2_pcg).
+// The serial iteration (solver.cpp cedar_amd_solver_pcg) on the rank's level-0 box with krylov.hip's passes, plus:
+//  - z's ghosts by one halo exchange once z is formed; p' = z + beta p on the ghost shell by pcg_ghost_shell (the value
+//    the owning neighbour forms, beta being the same everywhere), so the direction pass reads current ghosts of both;
+//  - every scalar from this rank's slab sums, all-gathered and summed in rank order on the device: the same bits on every
+//    rank, hence the same stop / breakdown decision.  Two all-gathers per iteration: p'.w, then r.r with r.z after the
+//    preconditioner (the serial stop test reads r.r before it; here the stop test waits for the preconditioned residual).
+struct PcgBox { // what the driver needs of level 0
+	int nd, nst, II, JJ, KK;
+	size_t npts;
+	const real_t *A;
+	const Op3 *op27;
+	Halo *halo;
+};
+
+// settings a rank grid cannot honour, decided from the handle's settings and p alone (every rank decides alike, before
+// any communication)
+static inline bool dist_pcg_refused(int pre, int post, const cedar_amd_pcg_settings &p, const char *who)
+{
+	const char *why = nullptr;
+	if (p.stop_test < CEDAR_AMD_PCG_STOP_ABS_RES_L2 || p.stop_test > CEDAR_AMD_PCG_STOP_REL_RES_M2) why = "stop_test must be 0..3";
+	else if (p.precon < CEDAR_AMD_PCG_PRECON_NONE || p.precon > CEDAR_AMD_PCG_PRECON_BMG) why = "precon must be 1..3";
+	else if (p.max_iter < 0) why = "max_iter must not be negative";
+	else if (p.precon == CEDAR_AMD_PCG_PRECON_BMG) {
+		if (pre != post) why = "the multigrid preconditioner needs nrelax_pre == nrelax_post (symmetric V-cycle)";
+		else if (p.nmg_cycles < 1) why = "nmg_cycles must be at least 1";
+	}
+	if (!why) return false;
+	char msg[256];
+	snprintf(msg, sizeof(msg), "%s: %s; nothing done", who, why);
+	print_error(msg);
+	return true;
+}
+
+static inline void krylov_alloc(RankCtx *d, const PcgBox &B)
+{
+	Krylov &K = d->kry;
+	if (K.r) return;
+	// zero-filled: the physical-boundary ghosts of every vector stay zero (the kernels write interiors and the shell)
+	K.r = dmalloc(B.npts); K.z = dmalloc(B.npts); K.w = dmalloc(B.npts);
+	K.p[0] = dmalloc(B.npts); K.p[1] = dmalloc(B.npts);
+	K.slab = dmalloc(pcg_slab_doubles(B.nd, B.nst, B.II, B.JJ, B.KK));
+	K.sc = dmalloc(PCG_NSC);
+	K.part = dmalloc(2);
+	K.gath = dmalloc(2 * (size_t)d->world);
+	// the halo's receive boxes, cut to the owned range along the directions the message does not cross
+	const Halo &h = *B.halo;
+	K.shell.n = 0;
+	for (const HaloEntry &e : h.nb) {
+		int *o = K.shell.box + 6 * K.shell.n++;
+		for (int t = 0; t < 3; t++) {
+			o[t] = e.rbox[t]; o[3 + t] = e.rbox[3 + t];
+			if (e.o[t] == 0 && h.n[t] >= 1) { o[t] = 1; o[3 + t] = h.n[t]; }
+		}
+	}
+}
+
+static inline void krylov_free(RankCtx *d)
+{
+	Krylov &K = d->kry;
+	cedar_amd_free(K.r); cedar_amd_free(K.z); cedar_amd_free(K.w); cedar_amd_free(K.p[0]); cedar_amd_free(K.p[1]);
+	cedar_amd_free(K.slab); cedar_amd_free(K.sc); cedar_amd_free(K.part); cedar_amd_free(K.gath);
+	K = Krylov();
+}
+
+// resid(x, b, r): r = b - A x on the interior (x's ghosts current); vcycle(x, b): one cycle of the rank grid
+template <class Resid, class Cycle>
+int dist_pcg(RankCtx *d, const PcgBox &B, int pre, int post, const real_t *b, real_t *x, const cedar_amd_pcg_settings *settings,
+             real_t *hist, const char *who, Resid resid, Cycle vcycle)
+{
+	cedar_amd_pcg_settings p;
+	if (settings) p = *settings;
+	else cedar_amd_default_pcg_settings(&p);
+	if (dist_pcg_refused(pre, post, p, who)) return -1;
+	krylov_alloc(d, B);
+	Krylov &K = d->kry;
+	hipStream_t st = current_stream();
+	const int zm = p.precon == CEDAR_AMD_PCG_PRECON_NONE ? 0 : p.precon == CEDAR_AMD_PCG_PRECON_DIAG ? 1 : 2;
+	real_t *Z = zm == 0 ? K.r : K.z;
+	const bool mnorm = p.stop_test >= CEDAR_AMD_PCG_STOP_ABS_RES_M2;
+	const bool rel = p.stop_test == CEDAR_AMD_PCG_STOP_REL_RES_L2 || p.stop_test == CEDAR_AMD_PCG_STOP_REL_RES_M2;
+	auto exch = [&](real_t *a) { halo_exchange(d, *B.halo, B.II, B.JJ, B.KK, a, 1, 0); };
+	auto precondition = [&]() {
+		CEDAR_HIP_CHECK(hipMemsetAsync(K.z, 0, B.npts * sizeof(real_t), st));
+		for (int c = 0; c < p.nmg_cycles; c++) vcycle(K.z, K.r);
+	};
+	// r.r and r.z of the current residual over all ranks (rho, beta on the device), z's ghosts, then the one host read
+	double sc[PCG_NSC];
+	auto dots = [&](int zmode, bool move, const real_t *pn, bool first) {
+		pcg_update(zmode, move, x, K.r, pn, K.w, Z, B.A, B.II, B.JJ, B.KK, first, K.slab, K.sc, st, K.part);
+		tp_allgather(d, K.part, K.gath, 2);
+		pcg_ranks_rho(zmode, K.gath, d->world, 2, first, K.sc, st);
+		exch(Z);
+		CEDAR_HIP_CHECK(hipMemcpyAsync(sc, K.sc, PCG_NSC * sizeof(double), hipMemcpyDeviceToHost, st));
+		CEDAR_HIP_CHECK(hipStreamSynchronize(st));
+	};
+
+	CEDAR_HIP_CHECK(hipMemsetAsync(K.sc, 0, PCG_NSC * sizeof(real_t), st));
+	exch(x);
+	resid(x, b, K.r);
+	if (zm == 2) precondition();
+	dots(zm, false, nullptr, true);
+	const double r0 = std::sqrt(sc[PCG_RR]), m0 = std::sqrt(sc[PCG_RZ] > 0 ? sc[PCG_RZ] : 0.0);
+	if (hist) hist[0] = r0;
+	auto stop = [&](double rr, double rz) {
+		const double v = mnorm ? std::sqrt(rz > 0 ? rz : 0.0) : std::sqrt(rr);
+		return (rel ? v / (mnorm ? m0 : r0) : v) < p.tol;
+	};
+	int it = 0;
+	if (!(r0 == 0.0 || !(sc[PCG_RZ] > 0) || stop(sc[PCG_RR], sc[PCG_RZ])))
+		for (int k = 0; k < p.max_iter; k++) {
+			real_t *pold = K.p[(k + 1) & 1], *pn = K.p[k & 1];
+			pcg_direction(B.A, B.op27, Z, pold, pn, K.w, B.nd, B.nst, B.II, B.JJ, B.KK, k == 0, K.slab, K.sc, st, K.part);
+			tp_allgather(d, K.part, K.gath, 1);
+			pcg_ranks_alpha(K.gath, d->world, 1, K.sc, st);
+			pcg_ghost_shell(Z, pold, pn, K.sc, K.shell, B.II, B.JJ, k == 0, st); // before the update changes z (zm 0, 1)
+			if (zm == 2) {
+				pcg_update(3, true, x, K.r, pn, K.w, Z, B.A, B.II, B.JJ, B.KK, false, K.slab, K.sc, st, K.part);
+				precondition();
+				dots(2, false, nullptr, false);
+			} else
+				dots(zm, true, pn, false);
+			if (sc[PCG_FLAG] != 0) break; // breakdown (p.Ap <= 0 or rho = 0): alpha was 0, x is as it was
+			it = k + 1;
+			if (hist) hist[it] = std::sqrt(sc[PCG_RR]) / r0;
+			if (stop(sc[PCG_RR], sc[PCG_RZ])) break;
+		}
+	exch(x); // the caller's box as cedar_amd_dist*_solve leaves it: ghosts current
+	return it;
+}
+
+// z = M^-1 r: one cycle of the rank grid from z = 0, z's ghosts exchanged
+template <class Cycle>
+void dist_precondition(RankCtx *d, const PcgBox &B, int pre, int post, real_t *z, real_t *r, const char *who, Cycle vcycle)
+{
+	cedar_amd_pcg_settings p;
+	cedar_amd_default_pcg_settings(&p);
+	if (dist_pcg_refused(pre, post, p, who)) return;
+	CEDAR_HIP_CHECK(hipMemsetAsync(z, 0, B.npts * sizeof(real_t), current_stream()));
+	vcycle(z, r);
+	halo_exchange(d, *B.halo, B.II, B.JJ, B.KK, z, 1, 0);
 }
 
 

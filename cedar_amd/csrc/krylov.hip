@@ -285,18 +285,34 @@ __device__ __forceinline__ real_t slab_sum(const real_t *__restrict__ part, unsi
 	return block_sum_k<RED_BS>(acc, lds);
 }
 
-// sigma = sum of the slab; alpha = rho / sigma, or 0 with the breakdown flag when sigma <= 0 (or not finite) or rho = 0
+// the scalars of a second stage, thread 0 only: sigma -> alpha (0 with the breakdown flag when sigma <= 0 or not
+// finite, or rho = 0); r.r / r.z -> rho, beta (first: 0)
+__device__ __forceinline__ void set_alpha(real_t sigma, real_t *__restrict__ sc)
+{
+	const real_t rho = sc[PCG_RHO];
+	const bool ok = sigma > 0.0 && sigma <= 1.7976931348623157e308 && rho != 0.0;
+	sc[PCG_SIGMA] = sigma;
+	sc[PCG_ALPHA] = ok ? rho / sigma : 0.0;
+	if (!ok) sc[PCG_FLAG] = 1.0;
+}
+
+__device__ __forceinline__ void set_rho(real_t rr, real_t rz, int has_rz, int first, real_t *__restrict__ sc)
+{
+	sc[PCG_RR] = rr;
+	if (has_rz) {
+		const real_t rho = sc[PCG_RHO];
+		sc[PCG_RZ] = rz;
+		sc[PCG_BETA] = first || rho == 0.0 ? 0.0 : rz / rho;
+		sc[PCG_RHO] = rz;
+	}
+}
+
+// sigma = sum of the slab, then alpha
 __global__ __launch_bounds__(RED_BS) void pcg_alpha(const real_t *__restrict__ part, unsigned n, real_t *__restrict__ sc)
 {
 	__shared__ real_t lds[RED_BS / 64];
 	const real_t sigma = slab_sum(part, n, lds);
-	if (threadIdx.x == 0) {
-		const real_t rho = sc[PCG_RHO];
-		const bool ok = sigma > 0.0 && sigma <= 1.7976931348623157e308 && rho != 0.0;
-		sc[PCG_SIGMA] = sigma;
-		sc[PCG_ALPHA] = ok ? rho / sigma : 0.0;
-		if (!ok) sc[PCG_FLAG] = 1.0;
-	}
+	if (threadIdx.x == 0) set_alpha(sigma, sc);
 }
 
 // r.r (slab 0) and, when has_rz, r.z (slab 1; zm0: r.z = r.r): the new rho, beta = rho_new / rho_old (first: 0)
@@ -306,14 +322,60 @@ __global__ __launch_bounds__(RED_BS) void pcg_rho(const real_t *__restrict__ par
 	__shared__ real_t lds[RED_BS / 64];
 	const real_t rr = slab_sum(part, n, lds);
 	const real_t rz = has_rz == 1 ? slab_sum(part + n, n, lds) : rr;
-	if (threadIdx.x == 0) {
-		sc[PCG_RR] = rr;
-		if (has_rz) {
-			const real_t rho = sc[PCG_RHO];
-			sc[PCG_RZ] = rz;
-			sc[PCG_BETA] = first || rho == 0.0 ? 0.0 : rz / rho;
-			sc[PCG_RHO] = rz;
-		}
+	if (threadIdx.x == 0) set_rho(rr, rz, has_rz, first, sc);
+}
+
+// ---------------------------------------------------------------- the same second stages on a rank grid
+// (a) this rank's slab sums (the sums pcg_alpha / pcg_rho form, same order) into out[0 .. nslab-1], the send buffer of
+// the all-gather; (b) after it, one thread sums the world ranks' partials (stride doubles per rank) in rank order and
+// sets the scalars as the one-rank stages do.  world = 1: (b) takes the partial as it is, the one-rank values bit for bit.
+__global__ __launch_bounds__(RED_BS) void pcg_partial(const real_t *__restrict__ part, unsigned n, int nslab,
+                                                      real_t *__restrict__ out)
+{
+	__shared__ real_t lds[RED_BS / 64];
+	for (int t = 0; t < nslab; t++) {
+		const real_t v = slab_sum(part + (size_t)t * n, n, lds);
+		if (threadIdx.x == 0) out[t] = v;
+	}
+}
+
+__device__ __forceinline__ real_t rank_sum(const real_t *__restrict__ g, int world, int stride, int t)
+{
+	real_t v = g[t];
+	for (int r = 1; r < world; r++) v += g[(size_t)r * stride + t];
+	return v;
+}
+
+__global__ void pcg_alpha_ranks(const real_t *__restrict__ g, int world, int stride, real_t *__restrict__ sc)
+{
+	if (threadIdx.x == 0) set_alpha(rank_sum(g, world, stride, 0), sc);
+}
+
+__global__ void pcg_rho_ranks(const real_t *__restrict__ g, int world, int stride, int has_rz, int first,
+                              real_t *__restrict__ sc)
+{
+	if (threadIdx.x != 0) return;
+	const real_t rr = rank_sum(g, world, stride, 0);
+	set_rho(rr, has_rz == 1 ? rank_sum(g, world, stride, 1) : rr, has_rz, first, sc);
+}
+
+// ---------------------------------------------------------------- p' = z + beta p on the ghost shell of a rank box
+// The ghost cells a neighbouring rank owns (boxes of the halo's receive side, without the physical-boundary ghosts): the
+// value that neighbour's pcg_direction forms for its own point (same expression, same beta on every rank, no FMA
+// contraction in this build), so the next direction pass finds p current at its stencil neighbours without an exchange.
+template <bool FIRST>
+__global__ __launch_bounds__(256) void pcg_shell(const real_t *__restrict__ z, const real_t *__restrict__ p,
+                                                 real_t *__restrict__ pn, const real_t *__restrict__ sc, ShellBoxes bx,
+                                                 int II, int JJ)
+{
+	const int b = blockIdx.y;
+	const int *B = bx.box + 6 * b;
+	const size_t cnt = (size_t)B[3] * B[4] * B[5];
+	const real_t beta = FIRST ? 0.0 : sc[PCG_BETA];
+	for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < cnt; t += (size_t)gridDim.x * blockDim.x) {
+		const size_t i = B[0] + t % B[3], j = B[1] + (t / B[3]) % B[4], k = B[2] + t / ((size_t)B[3] * B[4]);
+		const size_t y = i + (size_t)II * (j + (size_t)JJ * k);
+		pn[y] = FIRST ? z[y] : z[y] + beta * p[y];
 	}
 }
 
@@ -331,7 +393,8 @@ size_t pcg_slab_doubles(int nd, int nst, int II, int JJ, int KK)
 }
 
 void pcg_direction(const real_t *so, const Op3 *op27, const real_t *z, const real_t *p, real_t *pn, real_t *w, int nd,
-                   int nst, int II, int JJ, int KK, bool first, real_t *slab, real_t *sc, hipStream_t st)
+                   int nst, int II, int JJ, int KK, bool first, real_t *slab, real_t *sc, hipStream_t st,
+                   real_t *partial)
 {
 	unsigned n = 0;
 	if (nd == 2) {
@@ -357,11 +420,13 @@ void pcg_direction(const real_t *so, const Op3 *op27, const real_t *z, const rea
 		else { if (first) L27_(256, true); else L27_(256, false); }
 #undef L27_
 	}
-	hipLaunchKernelGGL(pcg_alpha, dim3(1), dim3(RED_BS), 0, st, slab, n, sc);
+	if (partial) hipLaunchKernelGGL(pcg_partial, dim3(1), dim3(RED_BS), 0, st, slab, n, 1, partial);
+	else hipLaunchKernelGGL(pcg_alpha, dim3(1), dim3(RED_BS), 0, st, slab, n, sc);
 }
 
 void pcg_update(int zmode, bool move, real_t *x, real_t *r, const real_t *p, const real_t *w, real_t *z,
-                const real_t *diag, int II, int JJ, int KK, bool first, real_t *slab, real_t *sc, hipStream_t st)
+                const real_t *diag, int II, int JJ, int KK, bool first, real_t *slab, real_t *sc, hipStream_t st,
+                real_t *partial)
 {
 	const size_t nrows = (size_t)(JJ - 2) * (KK == 1 ? 1 : KK - 2);
 	const unsigned nb = (unsigned)std::min<size_t>(UPD_NB, nrows);
@@ -378,7 +443,30 @@ void pcg_update(int zmode, bool move, real_t *x, real_t *r, const real_t *p, con
 	}
 #undef LU_
 	const int has_rz = zmode == 3 ? 0 : zmode == 0 ? 2 : 1; // 2: r.z = r.r
-	hipLaunchKernelGGL(pcg_rho, dim3(1), dim3(RED_BS), 0, st, slab, nb, has_rz, first ? 1 : 0, sc);
+	if (!partial) hipLaunchKernelGGL(pcg_rho, dim3(1), dim3(RED_BS), 0, st, slab, nb, has_rz, first ? 1 : 0, sc);
+	else if (zmode != 3) hipLaunchKernelGGL(pcg_partial, dim3(1), dim3(RED_BS), 0, st, slab, nb, has_rz == 1 ? 2 : 1, partial);
+}
+
+void pcg_ranks_alpha(const real_t *gathered, int world, int stride, real_t *sc, hipStream_t st)
+{
+	hipLaunchKernelGGL(pcg_alpha_ranks, dim3(1), dim3(64), 0, st, gathered, world, stride, sc);
+}
+
+void pcg_ranks_rho(int zmode, const real_t *gathered, int world, int stride, bool first, real_t *sc, hipStream_t st)
+{
+	const int has_rz = zmode == 3 ? 0 : zmode == 0 ? 2 : 1;
+	hipLaunchKernelGGL(pcg_rho_ranks, dim3(1), dim3(64), 0, st, gathered, world, stride, has_rz, first ? 1 : 0, sc);
+}
+
+void pcg_ghost_shell(const real_t *z, const real_t *p, real_t *pn, const real_t *sc, const ShellBoxes &bx, int II, int JJ,
+                     bool first, hipStream_t st)
+{
+	if (bx.n == 0) return;
+	size_t most = 0;
+	for (int b = 0; b < bx.n; b++) most = std::max(most, (size_t)bx.box[6 * b + 3] * bx.box[6 * b + 4] * bx.box[6 * b + 5]);
+	const dim3 grid((unsigned)std::min<size_t>((most + 255) / 256, 1024), (unsigned)bx.n);
+	if (first) hipLaunchKernelGGL(pcg_shell<true>, grid, dim3(256), 0, st, z, p, pn, sc, bx, II, JJ);
+	else hipLaunchKernelGGL(pcg_shell<false>, grid, dim3(256), 0, st, z, p, pn, sc, bx, II, JJ);
 }
 
 } // namespace cedar_amd

@@ -148,6 +148,8 @@ static Op3 op3_lookup(const real_t *so, const real_t *sor, int II, int JJ, int K
 	return op3_cedar(so, sor, II, JJ, KK);
 }
 
+Op3 relax3_op_view(const real_t *so, int II, int JJ, int KK) { return op3_lookup(so, nullptr, II, JJ, KK); }
+
 // direct-from-memory evaluation at one point (generic path; x = vector offset of (i,j,k), xa = operator offset)
 __device__ __forceinline__ real_t offdiag27_mem(const Op3 &A, const real_t *__restrict__ qf,
                                                 const real_t *q, size_t II, size_t JJ, // (q: relax27_cols reads what it wrote)

@@ -41,6 +41,9 @@ lib.cedar_amd_dist3_solve.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_vo
 lib.cedar_amd_dist3_time_relax.restype = C.c_float
 lib.cedar_amd_dist3_time_relax.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
 lib.cedar_amd_dist3_rank_grid.argtypes = [C.c_int, C.POINTER(C.c_int)]
+lib.cedar_amd_dist3_pcg.restype = C.c_int
+lib.cedar_amd_dist3_pcg.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(capi.PcgSettings), C.c_void_p]
+lib.cedar_amd_dist3_precondition.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
 
 
 lib.cedar_amd_dist2_create.restype = C.c_void_p
@@ -53,6 +56,9 @@ lib.cedar_amd_dist2_solve.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_vo
 lib.cedar_amd_dist2_time_relax.restype = C.c_float
 lib.cedar_amd_dist2_time_relax.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
 lib.cedar_amd_dist2_rank_grid.argtypes = [C.c_int, C.POINTER(C.c_int)]
+lib.cedar_amd_dist2_pcg.restype = C.c_int
+lib.cedar_amd_dist2_pcg.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(capi.PcgSettings), C.c_void_p]
+lib.cedar_amd_dist2_precondition.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
 
 
 def rank_grid2(world):
@@ -65,6 +71,15 @@ def rank_grid(world):
     p = (C.c_int * 3)()
     lib.cedar_amd_dist3_rank_grid(world, p)
     return tuple(p)
+
+
+def _pcg(fn, h, b, x, max_iter, tol, stop, precon, nmg_cycles):
+    ps = capi.PcgSettings(int(max_iter), float(tol), capi.PCG_STOP[stop], capi.PCG_PRECON[precon], int(nmg_cycles))
+    hist = np.zeros(max(int(max_iter), 0) + 1)
+    n = fn(h, b.ptr, x.ptr, C.byref(ps), hist.ctypes.data)
+    if n < 0:
+        raise RuntimeError(f"{fn.__name__} refused the settings (see the printed reason)")
+    return hist[: n + 1]
 
 
 class _Raw:
@@ -147,6 +162,16 @@ class DistSolver3:
         n = lib.cedar_amd_dist3_solve(self.h, b.ptr, x.ptr, rel.ctypes.data)
         return [float(v) for v in rel[: n + 1]]
 
+    def pcg(self, b, x, max_iter=50, tol=1e-8, stop="rel_l2", precon="mg", nmg_cycles=1):
+        """conjugate gradients preconditioned by the distributed V-cycle (cedar_amd_dist3_pcg), collective: x (local
+        device box) updated in place; returns the history [||r0||, ||r1||/||r0||, ...] with global norms, the same on
+        every rank; RuntimeError on every rank when the library refuses the settings (x untouched)"""
+        return _pcg(lib.cedar_amd_dist3_pcg, self.h, b, x, max_iter, tol, stop, precon, nmg_cycles)
+
+    def precondition(self, z, r):
+        """z = M^-1 r: one distributed V-cycle from z = 0 (cedar_amd_dist3_precondition), collective"""
+        lib.cedar_amd_dist3_precondition(self.h, z.ptr, r.ptr)
+
     def time_relax(self, x, b, n):
         return float(lib.cedar_amd_dist3_time_relax(self.h, x.ptr, b.ptr, n))
 
@@ -201,6 +226,16 @@ class DistSolver2:
         rel = np.zeros(self.max_iter + 1)
         n = lib.cedar_amd_dist2_solve(self.h, b.ptr, x.ptr, rel.ctypes.data)
         return [float(v) for v in rel[: n + 1]]
+
+    def pcg(self, b, x, max_iter=50, tol=1e-8, stop="rel_l2", precon="mg", nmg_cycles=1):
+        """conjugate gradients preconditioned by the distributed V-cycle (cedar_amd_dist2_pcg), collective: x (local
+        device box) updated in place; returns the history [||r0||, ||r1||/||r0||, ...] with global norms, the same on
+        every rank; RuntimeError on every rank when the library refuses the settings (x untouched)"""
+        return _pcg(lib.cedar_amd_dist2_pcg, self.h, b, x, max_iter, tol, stop, precon, nmg_cycles)
+
+    def precondition(self, z, r):
+        """z = M^-1 r: one distributed V-cycle from z = 0 (cedar_amd_dist2_precondition), collective"""
+        lib.cedar_amd_dist2_precondition(self.h, z.ptr, r.ptr)
 
     def time_relax(self, x, b, n):
         return float(lib.cedar_amd_dist2_time_relax(self.h, x.ptr, b.ptr, n))

@@ -460,6 +460,19 @@ void cedar_amd_dist3_vcycle(cedar_amd_dist3 *d, real_t *x_dev, real_t *b_dev);
 int cedar_amd_dist3_solve(cedar_amd_dist3 *d, real_t *b_dev, real_t *x_dev, real_t *rel);
 /* n level-0 sweeps (alternating DOWN / UP) with their halo exchanges; elapsed ms by HIP events */
 float cedar_amd_dist3_time_relax(cedar_amd_dist3 *d, real_t *x_dev, real_t *b_dev, int n);
+/* Conjugate gradients preconditioned by the distributed V-cycle (cedar_amd_solver_pcg on a rank grid).
+ * Collective, on this rank's device-resident local boxes (ghost layer included) as cedar_amd_dist3_solve.  p as for
+ * cedar_amd_solver_pcg (NULL: the defaults); hist (p->max_iter + 1 entries, may be NULL): hist[0] = ||r0||_2,
+ * hist[i] = ||r_i||_2 / ||r0||_2 with global norms.  Every scalar is summed over the ranks in rank order, so hist, the
+ * return value (the iterations run) and every stop or breakdown decision are the same bits on every rank, and a run
+ * repeats bit for bit.  Refused with precon = 3 and nrelax_pre != nrelax_post (the drivers run V-cycles only), or on
+ * settings out of range: every rank refuses before any communication, print_error, x untouched, -1.  Breakdown
+ * (p.Ap <= 0 or r.z = 0) stops early with x finite.  x's ghosts are current on return.  The first call allocates five
+ * level-0 vectors that the handle keeps until cedar_amd_dist3_destroy. */
+int cedar_amd_dist3_pcg(cedar_amd_dist3 *d, real_t *b_dev, real_t *x_dev, const cedar_amd_pcg_settings *p, real_t *hist);
+/* z = M^-1 r: one distributed V-cycle from z = 0, z's ghosts exchanged (collective; local device boxes).  Refused
+ * (z untouched) when nrelax_pre != nrelax_post. */
+void cedar_amd_dist3_precondition(cedar_amd_dist3 *d, real_t *z_dev, real_t *r_dev);
 
 /* ------------------------------------------------------------------ 4b. the domain-decomposed 2D solver
  * cdr2::mpi::solver of the reference (include/cedar/2d/mpi/solver.h) for Dirichlet problems on a px x py rank grid
@@ -479,6 +492,9 @@ int cedar_amd_dist2_nlevels(const cedar_amd_dist2 *d);
 void cedar_amd_dist2_vcycle(cedar_amd_dist2 *d, real_t *x_dev, real_t *b_dev);
 int cedar_amd_dist2_solve(cedar_amd_dist2 *d, real_t *b_dev, real_t *x_dev, real_t *rel);
 float cedar_amd_dist2_time_relax(cedar_amd_dist2 *d, real_t *x_dev, real_t *b_dev, int n);
+/* cedar_amd_dist3_pcg / _precondition for the 2D driver: same contract, any of its smoothers in the preconditioner */
+int cedar_amd_dist2_pcg(cedar_amd_dist2 *d, real_t *b_dev, real_t *x_dev, const cedar_amd_pcg_settings *p, real_t *hist);
+void cedar_amd_dist2_precondition(cedar_amd_dist2 *d, real_t *z_dev, real_t *r_dev);
 
 /* Cedar's C interface (include/cedar/capi.h: bmg2_* / bmg3_*) with nprocx * nprocy [* nprocz] > 1 runs on the two drivers
  * above, as the reference runs it on its MPI solvers (src/2d/interface/c/solver.cc:10-60).  The MPI_Comm argument is not
