@@ -295,6 +295,42 @@ class Kernels:
         lib.cedar_amd_planes_run(h, _p(so), _p(x), _p(b), updown)
         lib.cedar_amd_planes_destroy(h)
 
+    # ---- the passes of a CG iteration (krylov.hip), one launcher each; sc: the PCG_NSC scalar block, in and out
+    @staticmethod
+    def _dims(a):
+        shp = a.shape
+        return (u(shp[-1]), u(shp[-2]), u(shp[0] if len(shp) == 3 else 1))
+
+    def pcg_direction(self, so, z, p, pn, w, first, sc, partial=None):
+        """pn = z + beta p (first: z), w = A pn, sigma = pn.w -> sc (or partial[0], sc untouched)"""
+        assert tuple(so.shape[1:]) == tuple(z.shape) and all(a is None or a.shape == z.shape for a in (p, pn, w))
+        assert sc.size == 8 and (partial is None or partial.size >= 1)
+        if lib.cedar_amd_pcg_direction(_p(so), _p(z), _p(p), _p(pn), _p(w), *self._dims(z), so.shape[0], int(first),
+                                       _p(sc), _p(partial)) != 0:
+            raise RuntimeError("cedar_amd_pcg_direction refused")
+
+    def pcg_update(self, zmode, move, x, r, p, w, z, diag, first, sc, partial=None):
+        """x += alpha p, r -= alpha w (move), r.r and r.z by zmode -> sc (or partial[0:2], sc untouched)"""
+        assert all(a is None or a.shape == r.shape for a in (x, p, w, z, diag))
+        assert sc.size == 8 and (partial is None or partial.size >= 2)
+        if lib.cedar_amd_pcg_update(int(zmode), int(move), _p(x), _p(r), _p(p), _p(w), _p(z), _p(diag), *self._dims(r),
+                                    int(first), _p(sc), _p(partial)) != 0:
+            raise RuntimeError("cedar_amd_pcg_update refused")
+
+    def pcg_rank_scalars(self, which, zmode, gathered, world, stride, first, sc):
+        """which 0: alpha from the ranks' sigma; 1: rho / beta from their r.r (and r.z); summed in rank order"""
+        assert sc.size == 8 and gathered.size >= world * stride
+        if lib.cedar_amd_pcg_rank_scalars(int(which), int(zmode), _p(gathered), int(world), int(stride), int(first), _p(sc)) != 0:
+            raise RuntimeError("cedar_amd_pcg_rank_scalars refused")
+
+    def pcg_ghost_shell(self, z, p, pn, first, sc, boxes):
+        """pn = z + beta p (first: z) on boxes = [(i0, j0, k0, ni, nj, nk), ...]"""
+        bx = np.ascontiguousarray(boxes, dtype=np.int32).reshape(-1, 6)
+        assert len(z.shape) == 3 and sc.size == 8 and all(a is None or a.shape == z.shape for a in (p, pn))
+        if lib.cedar_amd_pcg_ghost_shell(_p(z), _p(p), _p(pn), *self._dims(z), int(first), _p(sc),
+                                         bx.ctypes.data_as(C.POINTER(C.c_int)), len(bx)) != 0:
+            raise RuntimeError("cedar_amd_pcg_ghost_shell refused")
+
     def l2(self, v):
         return l2norm(v)
 

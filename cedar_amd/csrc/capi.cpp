@@ -610,6 +610,123 @@ void cedar_amd_box_copy_strided(real_t *arr, len_t ii, len_t jj, len_t kk, int n
 	box_copy(arr, (int)ii, (int)jj, (int)kk, nplanes, nboxes, boxes, offsets, buf, unpack, current_stream(), 1);
 }
 
+// ------------------------------------------------------------------ the passes of a CG iteration (krylov.hip)
+static_assert(CEDAR_AMD_PCG_RHO == PCG_RHO && CEDAR_AMD_PCG_SIGMA == PCG_SIGMA && CEDAR_AMD_PCG_ALPHA == PCG_ALPHA
+                  && CEDAR_AMD_PCG_BETA == PCG_BETA && CEDAR_AMD_PCG_RR == PCG_RR && CEDAR_AMD_PCG_RZ == PCG_RZ
+                  && CEDAR_AMD_PCG_FLAG == PCG_FLAG && CEDAR_AMD_PCG_NSC == PCG_NSC,
+              "the scalar slots of include/cedar_amd.h are those of common.h");
+
+namespace {
+
+bool pcg_shape_refused(len_t ii, len_t jj, len_t kk, const char *who)
+{
+	if (ii >= 3 && jj >= 3 && (kk == 1 || kk >= 3) && (size_t)ii * jj * kk < ((size_t)1 << 31)) return false;
+	char buf[200];
+	snprintf(buf, sizeof(buf), "%s: extents %u x %u x %u (ghosts included) are not served; nothing done", who, (unsigned)ii,
+	         (unsigned)jj, (unsigned)kk);
+	report(buf);
+	return true;
+}
+
+bool pcg_refuse(const char *who, const char *why)
+{
+	char buf[200];
+	snprintf(buf, sizeof(buf), "%s: %s; nothing done", who, why);
+	report(buf);
+	return true;
+}
+
+// the partial-sum slab of one call: from the pool, every double a NaN (all bits set) before the launch
+struct NanSlab {
+	size_t n;
+	real_t *dev;
+	std::vector<uint64_t> host;
+	explicit NanSlab(size_t doubles) : n(doubles), dev(static_cast<real_t *>(pool_get(doubles * sizeof(real_t)))), host(doubles, ~(uint64_t)0)
+	{
+		CEDAR_HIP_CHECK(hipMemcpyAsync(dev, host.data(), n * sizeof(real_t), hipMemcpyHostToDevice, current_stream()));
+	}
+	~NanSlab()
+	{
+		CEDAR_HIP_CHECK(hipStreamSynchronize(current_stream()));
+		pool_put(dev, n * sizeof(real_t));
+	}
+};
+
+} // namespace
+
+int cedar_amd_pcg_direction(const real_t *so, const real_t *z, const real_t *p, real_t *pn, real_t *w, len_t ii, len_t jj,
+                            len_t kk, int nstncl, int first, real_t *sc, real_t *partial)
+{
+	const char *who = "cedar_amd_pcg_direction";
+	if (pcg_shape_refused(ii, jj, kk, who)) return -1;
+	const int nd = kk == 1 ? 2 : 3;
+	if (nd == 2 ? (nstncl != 3 && nstncl != 5) : (nstncl != 4 && nstncl != 14)) return pcg_refuse(who, "nstncl must be 3|5 (2D), 4|14 (3D)"), -1;
+	if (!so || !z || !pn || !w || !sc || (!first && !p)) return pcg_refuse(who, "a required array is NULL"), -1;
+	const size_t P = (size_t)ii * jj * kk;
+	NanSlab slab(pcg_slab_doubles(nd, nstncl, (int)ii, (int)jj, (int)kk));
+	Staged sso(so, P * nstncl, true, false), sz(z, P, true, false), sp(first ? nullptr : p, P, true, false),
+	    spn(pn, P, true, true), sw(w, P, true, true), ssc(sc, PCG_NSC, true, partial == nullptr), spart(partial, 1, true, true);
+	// the view the solvers hand over: the row-interleaved copy of a registered 27-point operator, else the planes
+	const Op3 view = nstncl == 14 ? relax3_op_view(sso.get(), (int)ii, (int)jj, (int)kk) : Op3{};
+	pcg_direction(sso.get(), nstncl == 14 ? &view : nullptr, sz.get(), sp.get(), spn.get(), sw.get(), nd, nstncl, (int)ii,
+	              (int)jj, (int)kk, first != 0, slab.dev, ssc.get(), current_stream(), spart.get());
+	return 0;
+}
+
+int cedar_amd_pcg_update(int zmode, int move, real_t *x, real_t *r, const real_t *p, const real_t *w, real_t *z,
+                         const real_t *diag, len_t ii, len_t jj, len_t kk, int first, real_t *sc, real_t *partial)
+{
+	const char *who = "cedar_amd_pcg_update";
+	if (pcg_shape_refused(ii, jj, kk, who)) return -1;
+	if (zmode < 0 || zmode > 3) return pcg_refuse(who, "zmode must be 0..3"), -1;
+	if (!r || !sc || (move && (!x || !p || !w)) || ((zmode == 1 || zmode == 2) && !z) || (zmode == 1 && !diag))
+		return pcg_refuse(who, "a required array is NULL"), -1;
+	const size_t P = (size_t)ii * jj * kk;
+	NanSlab slab(pcg_slab_doubles(kk == 1 ? 2 : 3, kk == 1 ? 3 : 4, (int)ii, (int)jj, (int)kk)); // any stencil: at least the update's share
+	const bool mv = move != 0;
+	Staged sx(mv ? x : nullptr, P, true, true), sr(r, P, true, mv), sp(mv ? p : nullptr, P, true, false),
+	    sw(mv ? w : nullptr, P, true, false), sz(zmode == 1 || zmode == 2 ? z : nullptr, P, true, zmode == 1),
+	    sd(zmode == 1 ? diag : nullptr, P, true, false), ssc(sc, PCG_NSC, true, partial == nullptr), spart(partial, 2, true, true);
+	pcg_update(zmode, mv, sx.get(), sr.get(), sp.get(), sw.get(), sz.get(), sd.get(), (int)ii, (int)jj, (int)kk, first != 0,
+	           slab.dev, ssc.get(), current_stream(), spart.get());
+	return 0;
+}
+
+int cedar_amd_pcg_rank_scalars(int which, int zmode, const real_t *gathered, int world, int stride, int first, real_t *sc)
+{
+	const char *who = "cedar_amd_pcg_rank_scalars";
+	if (which < 0 || which > 1 || zmode < 0 || zmode > 3) return pcg_refuse(who, "which must be 0|1 and zmode 0..3"), -1;
+	const int need = which == 1 && (zmode == 1 || zmode == 2) ? 2 : 1; // doubles read per rank
+	if (!gathered || !sc || world < 1 || stride < need) return pcg_refuse(who, "world must be at least 1 and stride cover the partials"), -1;
+	Staged sg(gathered, (size_t)world * stride, true, false), ssc(sc, PCG_NSC, true, true);
+	if (which == 0) pcg_ranks_alpha(sg.get(), world, stride, ssc.get(), current_stream());
+	else pcg_ranks_rho(zmode, sg.get(), world, stride, first != 0, ssc.get(), current_stream());
+	return 0;
+}
+
+int cedar_amd_pcg_ghost_shell(const real_t *z, const real_t *p, real_t *pn, len_t ii, len_t jj, len_t kk, int first,
+                              const real_t *sc, const int *boxes, int nboxes)
+{
+	const char *who = "cedar_amd_pcg_ghost_shell";
+	if (pcg_shape_refused(ii, jj, kk, who)) return -1;
+	if (!z || !pn || !sc || (!first && !p) || nboxes < 0 || nboxes > 26 || (nboxes && !boxes))
+		return pcg_refuse(who, "a required array is NULL or there are more than 26 boxes"), -1;
+	ShellBoxes bx;
+	const long ext[3] = { (long)ii, (long)jj, (long)kk };
+	for (int b = 0; b < nboxes; b++)
+		for (int t = 0; t < 3; t++) {
+			const long lo = boxes[6 * b + t], n = boxes[6 * b + 3 + t];
+			if (lo < 0 || n < 1 || lo + n > ext[t]) return pcg_refuse(who, "a box reaches outside the array"), -1;
+			bx.box[6 * b + t] = (int)lo;
+			bx.box[6 * b + 3 + t] = (int)n;
+		}
+	bx.n = nboxes;
+	const size_t P = (size_t)ii * jj * kk;
+	Staged sz(z, P, true, false), sp(first ? nullptr : p, P, true, false), spn(pn, P, true, true), ssc(sc, PCG_NSC, true, false);
+	pcg_ghost_shell(sz.get(), sp.get(), spn.get(), ssc.get(), bx, (int)ii, (int)jj, first != 0, current_stream());
+	return 0;
+}
+
 // ------------------------------------------------------------------ 3D drop-ins
 void BMG3_SymStd_SETUP_recip(real_t *so, real_t *sor, len_t nx, len_t ny, len_t nz, int nstencl, int nsorv)
 {

@@ -262,6 +262,39 @@ void cedar_amd_box_copy(real_t *arr, len_t ii, len_t jj, len_t kk, int nplanes, 
 void cedar_amd_box_copy_strided(real_t *arr, len_t ii, len_t jj, len_t kk, int nplanes, int nboxes,
                                 const int *boxes, const unsigned long long *offsets, real_t *buf, int unpack);
 
+/* The passes of one conjugate-gradient iteration (krylov.hip), exactly as cedar_amd_solver_pcg and cedar_amd_dist{2,3}_pcg
+ * launch them, on caller arrays: host or device pointers, Cedar layout incl. one ghost layer, kk = 1 for 2D.  They read
+ * and write interiors only (the ghost shell pass: its boxes only); every other cell of an output array stays as given.
+ * sc: the scalar block of a run, CEDAR_AMD_PCG_NSC doubles, slots below.  Each call takes its partial-sum slab from the
+ * library's pool and fills it with NaN bit patterns first, so a slab entry that the second stage sums but no workgroup
+ * wrote shows in the scalars.  All return 0, or -1 (nothing done, reported through print_error) on arguments they do
+ * not serve. */
+enum { CEDAR_AMD_PCG_RHO = 0, CEDAR_AMD_PCG_SIGMA = 1, CEDAR_AMD_PCG_ALPHA = 2, CEDAR_AMD_PCG_BETA = 3, CEDAR_AMD_PCG_RR = 4,
+       CEDAR_AMD_PCG_RZ = 5, CEDAR_AMD_PCG_FLAG = 6, CEDAR_AMD_PCG_NSC = 8 };
+/* pn = z + beta p (first != 0: pn = z, p is not read and may be NULL), w = A pn with the terms of cedar_amd_matvec2 / 3
+ * in their order, sigma = pn.w; nstncl = 3|5 (2D), 4|14 (3D).  beta = sc[BETA]; the neighbours of a point are
+ * z + beta p of the input arrays, ghost cells included.  partial == NULL: the one-rank second stage -- sc[SIGMA] = sigma,
+ * sc[ALPHA] = sc[RHO] / sigma, or 0 with sc[FLAG] = 1 (breakdown) when sigma <= 0, sigma is not finite or sc[RHO] = 0.
+ * partial != NULL (rank grids): partial[0] = sigma and sc is only read.  A 27-point operator registered with
+ * cedar_amd_relax3_prepare is read through its row-interleaved copy where it has one, as the solvers do. */
+int cedar_amd_pcg_direction(const real_t *so, const real_t *z, const real_t *p, real_t *pn, real_t *w, len_t ii, len_t jj,
+                            len_t kk, int nstncl, int first, real_t *sc, real_t *partial);
+/* move != 0: x += alpha p, r -= alpha w with alpha = sc[ALPHA] (alpha = 0, the breakdown value: x and r are not touched,
+ * whatever p and w hold); then r.r and r.z by zmode: 0 z = r (r.z = r.r), 1 z = r / diag written here (diag: the
+ * operator's centre plane), 2 z read, 3 r.r only.  partial == NULL: sc[RR] = r.r and, unless zmode 3, sc[RZ] = r.z,
+ * sc[BETA] = r.z / sc[RHO] (0 when first != 0 or sc[RHO] = 0), then sc[RHO] = r.z.  partial != NULL: partial[0] = r.r,
+ * zmode 1 | 2 also partial[1] = r.z, zmode 3 nothing; sc is only read.  Arrays a mode does not use may be NULL. */
+int cedar_amd_pcg_update(int zmode, int move, real_t *x, real_t *r, const real_t *p, const real_t *w, real_t *z,
+                         const real_t *diag, len_t ii, len_t jj, len_t kk, int first, real_t *sc, real_t *partial);
+/* the second stages of a rank grid: the ranks' partials (gathered[rank * stride + t], t = 0: sigma or r.r, t = 1: r.z)
+ * summed in rank order, then the scalars as above; which = 0: alpha from sigma, 1: rho / beta by zmode.  world = 1 gives
+ * the one-rank values bit for bit. */
+int cedar_amd_pcg_rank_scalars(int which, int zmode, const real_t *gathered, int world, int stride, int first, real_t *sc);
+/* pn = z + beta p (first != 0: pn = z) on up to 26 boxes {i0,j0,k0,ni,nj,nk} (0-based incl. ghost; host ints) of the
+ * array: the ghost cells of a rank box that neighbouring ranks own */
+int cedar_amd_pcg_ghost_shell(const real_t *z, const real_t *p, real_t *pn, len_t ii, len_t jj, len_t kk, int first,
+                              const real_t *sc, const int *boxes, int nboxes);
+
 /* ------------------------------------------------------------------ 2. handle API */
 typedef struct cedar_amd_solver cedar_amd_solver;
 

@@ -40,7 +40,21 @@ PARITY = [
     ("poisson3-v22", lambda: pb.poisson3(23, 21, 19), dict(nrelax_pre=2, nrelax_post=2)),
     ("fe3-v11", lambda: pb.fe3(25, 22, 19), dict(nrelax_pre=1, nrelax_post=1)),
     ("fe3-164rows", lambda: pb.fe3(24, 164, 12), dict(nrelax_pre=1, nrelax_post=1)),
+    # rows long enough for the wider launch variants of krylov.hip: pcg_dir27<128> / <256>, pcg_dir7 with 128 / 256 lanes,
+    # pcg_dir2 with several workgroups per row, a second trip of pcg_upd's pair loop
+    ("fe3-nx140", lambda: pb.fe3(140, 12, 10), dict(nrelax_pre=1, nrelax_post=1)),
+    ("fe3-nx300", lambda: pb.fe3(300, 9, 8), dict(nrelax_pre=1, nrelax_post=1)),
+    ("poisson3-nx140", lambda: pb.poisson3(140, 10, 9), dict(nrelax_pre=1, nrelax_post=1)),
+    ("poisson3-nx300", lambda: pb.poisson3(300, 9, 8), dict(nrelax_pre=1, nrelax_post=1)),
+    ("poisson2-nx600", lambda: pb.poisson2(600, 9), dict(nrelax_pre=1, nrelax_post=1)),
+    ("poisson2-nx600-linexy", lambda: pb.poisson2(600, 9), dict(relax="line-xy", nrelax_pre=1, nrelax_post=1)),
+    ("varcoef9-nx300", lambda: pb.varcoef9(300, 40), dict(nrelax_pre=1, nrelax_post=1)),
 ]
+# The gallery's Poisson operators are scaled by the mesh widths: at these extents the x coupling is over a hundred times
+# the others, point relaxation does not smooth that, and the numpy statement itself is at 2e-6 .. 7e-4 after 40
+# iterations.  These cases compare the 40 iterations entry by entry (same criterion) and require of the device exactly
+# what the statement does: that it has not converged either.
+SLOW = {"poisson3-nx140", "poisson3-nx300", "poisson2-nx600"}
 
 
 @pytest.mark.parametrize("name,mk,st", PARITY, ids=[c[0] for c in PARITY])
@@ -57,7 +71,10 @@ def test_pcg_parity_with_statement(capi, oracle, name, mk, st):
         xs = x0.copy()
         ns, hs = ps.pcg(oracle, so, b, xs, ml=ml, tol=1e-10, max_iter=40)
         compare_hist(h, hs, len(h) - 1, ns)
-        assert h[-1] < 1e-10
+        if name in SLOW:
+            assert ns == 40 and len(h) == 41 and hs[-1] >= 1e-10 and h[-1] >= 1e-10
+        else:
+            assert h[-1] < 1e-10
     finally:
         s.close()
         ml.close()
