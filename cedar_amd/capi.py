@@ -295,6 +295,40 @@ class Kernels:
         lib.cedar_amd_planes_run(h, _p(so), _p(x), _p(b), updown)
         lib.cedar_amd_planes_destroy(h)
 
+    # ---- the batched 3D kernels (many3d.hip): vectors of shape (nrhs,) + grid, item-major; operator arrays are shared.
+    # nrhs: work on the first nrhs items only (default: all the arrays hold)
+    @staticmethod
+    def _many(name, rc):
+        if rc != 0:
+            raise RuntimeError(f"{name} refused")
+
+    def relax3_many(self, so, qf, q, sor, updown, nrhs=None):
+        nst, KK, JJ, II = so.shape
+        assert qf.shape == q.shape and tuple(q.shape[1:]) == (KK, JJ, II)
+        self._many("cedar_amd_relax3_gs_many",
+                   lib.cedar_amd_relax3_gs_many(q.shape[0] if nrhs is None else nrhs, _p(so), _p(qf), _p(q), _p(sor), u(II), u(JJ), u(KK), nst, updown))
+
+    def residual3_many(self, so, qf, q, res, nrhs=None):
+        nst, KK, JJ, II = so.shape
+        assert qf.shape == q.shape == res.shape and tuple(q.shape[1:]) == (KK, JJ, II)
+        self._many("cedar_amd_residual3_many",
+                   lib.cedar_amd_residual3_many(q.shape[0] if nrhs is None else nrhs, _p(so), _p(qf), _p(q), _p(res), u(II), u(JJ), u(KK), nst))
+
+    def restrict3_many(self, q, qc, ci, nrhs=None):
+        n, KK, JJ, II = q.shape
+        nc, KKC, JJC, IIC = qc.shape
+        assert n == nc
+        self._many("cedar_amd_restrict3_many",
+                   lib.cedar_amd_restrict3_many(n if nrhs is None else nrhs, _p(q), _p(qc), _p(ci), u(II), u(JJ), u(KK), u(IIC), u(JJC), u(KKC)))
+
+    def interp_add3_many(self, q, qc, so, res, ci, nrhs=None):
+        n, KK, JJ, II = q.shape
+        nc, KKC, JJC, IIC = qc.shape
+        assert n == nc and res.shape == q.shape
+        self._many("cedar_amd_interp_add3_many",
+                   lib.cedar_amd_interp_add3_many(n if nrhs is None else nrhs, _p(q), _p(qc), _p(so), _p(res), _p(ci), u(IIC), u(JJC), u(KKC),
+                                                  u(II), u(JJ), u(KK), so.shape[0]))
+
     # ---- the passes of a CG iteration (krylov.hip), one launcher each; sc: the PCG_NSC scalar block, in and out
     @staticmethod
     def _dims(a):
@@ -354,6 +388,15 @@ lib.cedar_amd_solver_time_relax.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, 
 lib.cedar_amd_solver_time_op.restype = C.c_float
 lib.cedar_amd_solver_time_op.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int]
 lib.cedar_amd_gallery.argtypes = [C.c_int, C.c_void_p, C.c_void_p, u, u, u, C.c_void_p]
+lib.cedar_amd_solver_create_many.restype = C.c_void_p
+lib.cedar_amd_solver_create_many.argtypes = [C.c_int, u, u, u, C.c_int, C.c_void_p, C.c_int, C.POINTER(Settings), C.c_int]
+lib.cedar_amd_solver_max_rhs.argtypes = [C.c_void_p]
+lib.cedar_amd_solver_vcycle_many.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+lib.cedar_amd_solver_solve_many.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
+lib.cedar_amd_solver_time_vcycles_many.restype = C.c_float
+lib.cedar_amd_solver_time_vcycles_many.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
+for _f in (lib.cedar_amd_relax3_gs_many, lib.cedar_amd_residual3_many, lib.cedar_amd_restrict3_many, lib.cedar_amd_interp_add3_many):
+    _f.restype = C.c_int
 
 
 def _vp(a):
@@ -404,7 +447,7 @@ class Solver:
     """cedar::cdr2::solver / cdr3::solver on the device (include/cedar_amd.h, handle API)."""
 
     def __init__(self, so, relax="point", nrelax_pre=2, nrelax_post=1, num_levels=-1,
-                 max_iter=10, tol=1e-8, min_coarse=3, share_operator=False, cycle="v", ibc=0, plane=None):
+                 max_iter=10, tol=1e-8, min_coarse=3, share_operator=False, cycle="v", ibc=0, plane=None, max_rhs=1):
         shp = so.shape
         self.nd = len(shp) - 1
         nst = shp[0]
@@ -416,9 +459,48 @@ class Solver:
         plane_settings(st, plane)
         self.max_iter = max_iter
         self._so = so if share_operator else None  # keep the shared operator alive
-        self.h = lib.cedar_amd_solver_create(self.nd, nx, ny, nz, nst, _vp(so), int(share_operator), C.byref(st))
+        if max_rhs == 1:
+            self.h = lib.cedar_amd_solver_create(self.nd, nx, ny, nz, nst, _vp(so), int(share_operator), C.byref(st))
+        else:  # room for max_rhs right-hand sides on every level (vcycle_many / solve_many)
+            self.h = lib.cedar_amd_solver_create_many(self.nd, nx, ny, nz, nst, _vp(so), int(share_operator), C.byref(st),
+                                                      int(max_rhs))
         if not self.h:
             raise RuntimeError("cedar_amd_solver_create failed")
+
+    def max_rhs(self):
+        return lib.cedar_amd_solver_max_rhs(self.h)
+
+    def _nrhs(self, x, b):
+        assert tuple(x.shape) == tuple(b.shape) and tuple(x.shape[1:]) == self.shape, (x.shape, b.shape, self.shape)
+        return int(x.shape[0])
+
+    def vcycle_many(self, x, b):
+        """one cycle on every item of x, b of shape (nrhs,) + grid (cedar_amd_solver_vcycle_many); RuntimeError when
+        the library refuses (x untouched)"""
+        if lib.cedar_amd_solver_vcycle_many(self.h, self._nrhs(x, b), _vp(x), _vp(b)) != 0:
+            raise RuntimeError("cedar_amd_solver_vcycle_many refused (see the printed reason)")
+
+    def solve_many(self, b, x, rel=None):
+        """multilevel::solve for the items of b, x of shape (nrhs,) + grid in lockstep (cedar_amd_solver_solve_many).
+        Returns (rel, iters): rel a list of the items' histories cut to the cycles run, iters[m] the cycles after which
+        item m first met tol.  rel: optional (nrhs, max_iter + 1) array the library writes into.  RuntimeError when the
+        library refuses (x and rel untouched)."""
+        nrhs = self._nrhs(x, b)
+        if rel is None:
+            rel = np.zeros((nrhs, self.max_iter + 1))
+        assert rel.shape == (nrhs, self.max_iter + 1) and rel.dtype == np.float64 and rel.flags["C_CONTIGUOUS"]
+        iters = np.zeros(nrhs, dtype=np.int32)
+        n = lib.cedar_amd_solver_solve_many(self.h, nrhs, _vp(b), _vp(x), rel.ctypes.data, iters.ctypes.data_as(C.POINTER(C.c_int)))
+        if n < 0:
+            raise RuntimeError("cedar_amd_solver_solve_many refused (see the printed reason)")
+        return [rel[m, : n + 1] for m in range(nrhs)], [int(v) for v in iters]
+
+    def time_vcycles_many(self, x, b, n):
+        """n cycles on the items of the DeviceArrays x, b of shape (nrhs,) + grid; elapsed ms"""
+        ms = lib.cedar_amd_solver_time_vcycles_many(self.h, self._nrhs(x, b), x.ptr, b.ptr, n)
+        if ms < 0:
+            raise RuntimeError("cedar_amd_solver_time_vcycles_many refused (see the printed reason)")
+        return ms
 
     def nlevels(self):
         return lib.cedar_amd_solver_nlevels(self.h)

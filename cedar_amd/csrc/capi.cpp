@@ -727,6 +727,68 @@ int cedar_amd_pcg_ghost_shell(const real_t *z, const real_t *p, real_t *pn, len_
 	return 0;
 }
 
+// ------------------------------------------------------------------ the batched 3D kernels (many3d.hip), one launcher each
+static bool many_args_refused(int nrhs, bool arrays_ok, bool nst_ok, const char *who)
+{
+	const char *why = nrhs < 1 || nrhs > CEDAR_AMD_MAX_RHS ? "nrhs must be 1 .. 32" : !nst_ok ? "nstncl must be 4 or 14"
+	                  : !arrays_ok ? "a required array is NULL" : nullptr;
+	if (!why) return false;
+	char msg[200];
+	snprintf(msg, sizeof(msg), "%s: %s; nothing done", who, why);
+	print_error(msg);
+	return true;
+}
+
+int cedar_amd_relax3_gs_many(int nrhs, real_t *so, real_t *qf, real_t *q, real_t *sor, len_t ii, len_t jj, len_t kk, int nstncl,
+                             int updown)
+{
+	if (many_args_refused(nrhs, so && qf && q && sor, nstncl == 4 || nstncl == 14, "cedar_amd_relax3_gs_many")) return -1;
+	const size_t P = (size_t)ii * jj * kk;
+	Staged sso(so, P * nstncl, true, false), sqf(qf, P * nrhs, true, false), sq(q, P * nrhs, true, true), ssor(sor, P * 2, true, false);
+	const Batch bt{nrhs, P};
+	if (nstncl == 14)
+		relax3_gs27_many(op3_cedar(sso.get(), ssor.get(), (int)ii, (int)jj, (int)kk), sqf.get(), sq.get(), (int)ii, (int)jj, (int)kk,
+		                 updown, current_stream(), bt);
+	else relax3_gs7_many(sso.get(), sqf.get(), sq.get(), ssor.get(), (int)ii, (int)jj, (int)kk, updown, current_stream(), bt);
+	return 0;
+}
+
+int cedar_amd_residual3_many(int nrhs, real_t *so, real_t *qf, real_t *q, real_t *res, len_t ii, len_t jj, len_t kk, int nstncl)
+{
+	if (many_args_refused(nrhs, so && qf && q && res, nstncl == 4 || nstncl == 14, "cedar_amd_residual3_many")) return -1;
+	const size_t P = (size_t)ii * jj * kk;
+	Staged sso(so, P * nstncl, true, false), sqf(qf, P * nrhs, true, false), sq(q, P * nrhs, true, false), sr(res, P * nrhs, true, true);
+	const Batch bt{nrhs, P};
+	if (nstncl == 14)
+		residual27_many(op3_cedar(sso.get(), nullptr, (int)ii, (int)jj, (int)kk), sqf.get(), sq.get(), sr.get(), (int)ii, (int)jj,
+		                (int)kk, current_stream(), bt);
+	else residual7_many(sso.get(), sqf.get(), sq.get(), sr.get(), (int)ii, (int)jj, (int)kk, current_stream(), bt);
+	return 0;
+}
+
+int cedar_amd_restrict3_many(int nrhs, real_t *q, real_t *qc, real_t *ci, len_t ii, len_t jj, len_t kk, len_t iic, len_t jjc,
+                             len_t kkc)
+{
+	if (many_args_refused(nrhs, q && qc && ci, true, "cedar_amd_restrict3_many")) return -1;
+	const size_t P = (size_t)ii * jj * kk, PC = (size_t)iic * jjc * kkc;
+	Staged sq(q, P * nrhs, true, false), sqc(qc, PC * nrhs, true, true), sci(ci, PC * 26, true, false);
+	restrict3_many(sq.get(), sqc.get(), sci.get(), (int)ii, (int)jj, (int)kk, (int)iic, (int)jjc, (int)kkc, current_stream(),
+	               Batch{nrhs, P}, Batch{nrhs, PC});
+	return 0;
+}
+
+int cedar_amd_interp_add3_many(int nrhs, real_t *q, real_t *qc, real_t *so, real_t *res, real_t *ci, len_t iic, len_t jjc,
+                               len_t kkc, len_t iif, len_t jjf, len_t kkf, int nstncl)
+{
+	if (many_args_refused(nrhs, q && qc && so && res && ci, nstncl == 4 || nstncl == 14, "cedar_amd_interp_add3_many")) return -1;
+	const size_t P = (size_t)iif * jjf * kkf, PC = (size_t)iic * jjc * kkc;
+	Staged sq(q, P * nrhs, true, true), sqc(qc, PC * nrhs, true, false), sso(so, P * nstncl, true, false),
+	    sr(res, P * nrhs, true, true), sci(ci, PC * 26, true, false);
+	interp_add3_many(sq.get(), sqc.get(), sso.get(), sr.get(), sci.get(), (int)iic, (int)jjc, (int)kkc, (int)iif, (int)jjf,
+	                 (int)kkf, current_stream(), Batch{nrhs, P}, Batch{nrhs, PC});
+	return 0;
+}
+
 // ------------------------------------------------------------------ 3D drop-ins
 void BMG3_SymStd_SETUP_recip(real_t *so, real_t *sor, len_t nx, len_t ny, len_t nz, int nstencl, int nsorv)
 {

@@ -198,13 +198,15 @@ __global__ __launch_bounds__(256) void setup_cg3_kernel(const real_t *__restrict
 }
 
 __global__ __launch_bounds__(64) void solve_cg3_kernel(real_t *__restrict__ q, const real_t *__restrict__ qf, int II, int JJ, int KK,
-                                                        const real_t *__restrict__ abd, real_t *__restrict__ bbd, int nabd1, int use_lds)
+                                                        const real_t *__restrict__ abd, real_t *__restrict__ bbd, int nabd1, int use_lds,
+                                                        size_t bstride, int nabd2)
 {
 	extern __shared__ __attribute__((aligned(16))) real_t lds[];
 	const int i1 = II - 1, j1 = JJ - 1, k1 = KK - 1, i2 = i1 - 1;
 	const int ibw = i2 * j1 + 1;
 	const int nxy = i2 * (j1 - 1), n = nxy * (k1 - 1);
 	const size_t sj = II, sk = (size_t)II * JJ;
+	q += bstride * blockIdx.x; qf += bstride * blockIdx.x; bbd += (size_t)nabd2 * blockIdx.x; // batch item (common.h Batch)
 	for (int t = threadIdx.x; t < n; t += blockDim.x) {
 		const int i = t % i2 + 1, j = (t / i2) % (j1 - 1) + 1, k = t / nxy + 1; // 0-based
 		bbd[t] = qf[(size_t)i + sj * j + sk * k];
@@ -223,11 +225,13 @@ void setup_cg3(const real_t *so, int II, int JJ, int KK, int nstncl, real_t *abd
 	hipLaunchKernelGGL(setup_cg3_kernel, dim3(1), dim3(256), 0, st, so, II, JJ, KK, nstncl, abd, nabd1, nabd2, info);
 }
 
-void solve_cg3(real_t *q, const real_t *qf, int II, int JJ, int KK, const real_t *abd, real_t *bbd, int nabd1, int nabd2, hipStream_t st)
+void solve_cg3(real_t *q, const real_t *qf, int II, int JJ, int KK, const real_t *abd, real_t *bbd, int nabd1, int nabd2, hipStream_t st,
+               Batch bt)
 {
 	size_t shm = ((size_t)nabd1 * nabd2 + nabd2 + 2) * sizeof(real_t);
 	int use_lds = shm <= 60 * 1024;
-	hipLaunchKernelGGL(solve_cg3_kernel, dim3(1), dim3(64), use_lds ? shm : 0, st, q, qf, II, JJ, KK, abd, bbd, nabd1, use_lds);
+	hipLaunchKernelGGL(solve_cg3_kernel, dim3(bt.n), dim3(64), use_lds ? shm : 0, st, q, qf, II, JJ, KK, abd, bbd, nabd1, use_lds,
+	                   bt.stride, nabd2);
 }
 
 } // namespace cedar_amd

@@ -170,6 +170,8 @@ void matvec2(const real_t *so, const real_t *q, real_t *qf, int II, int JJ, int 
 void matvec3(const real_t *so, const real_t *q, real_t *qf, int II, int JJ, int KK, int nstncl, hipStream_t st);
 // sum of squares over the interior -> *out (deterministic two-stage tree); scratch >= 4096 doubles
 void sumsq_interior(const real_t *v, int II, int JJ, int KK, real_t *scratch, real_t *out, hipStream_t st);
+// the same for each item of a batch, one after the other on `st` (each item in sumsq_interior's order): out[m]
+void sumsq_interior_many(const real_t *v, int II, int JJ, int KK, real_t *scratch, real_t *out, hipStream_t st, Batch bt);
 // transfer.hip
 void restrict2(const real_t *q, real_t *qc, const real_t *ci, int II, int JJ, int IIC, int JJC, hipStream_t st,
                Batch bf = Batch(), Batch bc = Batch()); // batch strides of the fine / coarse vectors
@@ -240,7 +242,8 @@ void setup_cg2(const real_t *so, int II, int JJ, int nstncl, real_t *abd, int na
 void solve_cg2(real_t *q, const real_t *qf, int II, int JJ, const real_t *abd, real_t *bbd, int nabd1, int nabd2, hipStream_t st,
                Batch bt = Batch()); // bbd: nabd2 doubles per batch item
 void setup_cg3(const real_t *so, int II, int JJ, int KK, int nstncl, real_t *abd, int nabd1, int nabd2, int *info, hipStream_t st);
-void solve_cg3(real_t *q, const real_t *qf, int II, int JJ, int KK, const real_t *abd, real_t *bbd, int nabd1, int nabd2, hipStream_t st);
+void solve_cg3(real_t *q, const real_t *qf, int II, int JJ, int KK, const real_t *abd, real_t *bbd, int nabd1, int nabd2, hipStream_t st,
+               Batch bt = Batch()); // bbd: nabd2 doubles per batch item
 // krylov.hip: the vector work of the preconditioned conjugate gradient (solver.cpp cedar_amd_solver_pcg).  The scalars
 // of a run live on the device in sc[PCG_NSC]; the kernels read alpha / beta from there and write them back.
 enum { PCG_RHO = 0, PCG_SIGMA = 1, PCG_ALPHA = 2, PCG_BETA = 3, PCG_RR = 4, PCG_RZ = 5, PCG_FLAG = 6, PCG_NSC = 8 };
@@ -269,6 +272,18 @@ struct ShellBoxes {
 };
 void pcg_ghost_shell(const real_t *z, const real_t *p, real_t *pn, const real_t *sc, const ShellBoxes &bx, int II, int JJ,
                      bool first, hipStream_t st);
+// many3d.hip: the 3D solve-phase kernels on a batch of right-hand sides (cedar_amd_solver_*_many): the operator entries of a
+// workgroup task are fetched once and applied to every item from registers; reference term order, so item m has the bits
+// of the single-vector reference-order kernels on item m alone.  bf / bc: batch strides of the fine / coarse vectors.
+void relax3_gs27_many(const Op3 &A, const real_t *qf, real_t *q, int II, int JJ, int KK, int updown, hipStream_t st, Batch bt);
+void residual27_many(const Op3 &A, const real_t *qf, const real_t *q, real_t *res, int II, int JJ, int KK, hipStream_t st, Batch bt);
+void relax3_gs7_many(const real_t *so, const real_t *qf, real_t *q, const real_t *sor, int II, int JJ, int KK, int updown,
+                     hipStream_t st, Batch bt);
+void residual7_many(const real_t *so, const real_t *qf, const real_t *q, real_t *res, int II, int JJ, int KK, hipStream_t st, Batch bt);
+void restrict3_many(const real_t *q, real_t *qc, const real_t *ci, int II, int JJ, int KK, int IIC, int JJC, int KKC,
+                    hipStream_t st, Batch bf, Batch bc);
+void interp_add3_many(real_t *q, const real_t *qc, const real_t *so, real_t *res, const real_t *ci,
+                      int IIC, int JJC, int KKC, int IIF, int JJF, int KKF, hipStream_t st, Batch bf, Batch bc);
 // gallery.hip (device-side generators of the reference's gallery operators)
 void gallery_fill(int which, real_t *so, real_t *b, int nx, int ny, int nz, const double *params, hipStream_t st);
 

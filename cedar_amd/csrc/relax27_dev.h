@@ -89,16 +89,13 @@ __device__ __forceinline__ void ldpair_so(const real_t *__restrict__ p, bool two
 // slot-rows of plane k+1 read from plane k, bit 2 = every inter-plane slot read from KPW -- the loads then hit
 // the caches and the timing shows what removing that traffic would be worth.  8 = the k-pair walk of relax27_plane.
 #define WI_SLOT(slot) ((size_t)(((WI & 4) && ((slot) == KB || (slot) >= KBW)) ? KPW : (slot)))
+// the operator part: the 26 coefficients of both points (shared by every right-hand side of a batch, many3d.hip)
 template <bool NT, bool NTP = NT, bool NTO = NT, int WI = 0>
-__device__ __forceinline__ void load_pair27(const Op3 &A, const real_t *__restrict__ qf,
-                                            const real_t *__restrict__ q, size_t rowA, size_t row, size_t sj, size_t sk,
-                                            int ie, int io, bool two, C27 &ce, C27 &co,
-                                            real_t (&qe)[3][3][3], real_t (&qo)[3][3][3], real_t &qfe, real_t &qfo)
+__device__ __forceinline__ void load_coef27(const Op3 &A, size_t rowA, int ie, int io, bool two, C27 &ce, C27 &co)
 {
-	// operator entry (slot, i, j+dj, k+dk) = A.so[slot*A.SS + rowA + dj*A.SJ + dk*A.SK + i]; vectors use row, sj, sk
+	// operator entry (slot, i, j+dj, k+dk) = A.so[slot*A.SS + rowA + dj*A.SJ + dk*A.SK + i]
 	const real_t *__restrict__ so = A.so;
 	const size_t PS = A.SS, aj = A.SJ, ak = (WI & 2) ? 0 : A.SK;
-	if (WI & 1) { sj = 0; sk = 0; }
 	// ---- [i]-pattern streams: (value at ie, value at io)
 #define LD_I_(N, slot, off, fe, fo)                                                    \
 {                                                                                  \
@@ -140,6 +137,15 @@ __device__ __forceinline__ void load_pair27(const Op3 &A, const real_t *__restri
 #undef LD_IPS
 #undef LD_IPSO
 #undef LD_IP_
+}
+
+// the vector part: qf of both points and the nine q row windows; vectors use row, sj, sk
+template <int WI = 0>
+__device__ __forceinline__ void load_vec27(const real_t *__restrict__ qf, const real_t *__restrict__ q, size_t row, size_t sj,
+                                           size_t sk, int ie, int io, bool two,
+                                           real_t (&qe)[3][3][3], real_t (&qo)[3][3][3], real_t &qfe, real_t &qfo)
+{
+	if (WI & 1) { sj = 0; sk = 0; }
 	{
 		real_t a_, b_;
 		ldpair(qf + row + ie, true, a_, b_); qfe = a_; qfo = b_;
@@ -156,6 +162,16 @@ __device__ __forceinline__ void load_pair27(const Op3 &A, const real_t *__restri
 			qe[dk][dj][0] = w0; qe[dk][dj][1] = w1; qe[dk][dj][2] = w2;
 			qo[dk][dj][0] = w1; qo[dk][dj][1] = w2; qo[dk][dj][2] = w3;
 		}
+}
+
+template <bool NT, bool NTP = NT, bool NTO = NT, int WI = 0>
+__device__ __forceinline__ void load_pair27(const Op3 &A, const real_t *__restrict__ qf,
+                                            const real_t *__restrict__ q, size_t rowA, size_t row, size_t sj, size_t sk,
+                                            int ie, int io, bool two, C27 &ce, C27 &co,
+                                            real_t (&qe)[3][3][3], real_t (&qo)[3][3][3], real_t &qfe, real_t &qfo)
+{
+	load_coef27<NT, NTP, NTO, WI>(A, rowA, ie, io, two, ce, co);
+	load_vec27<WI>(qf, q, row, sj, sk, ie, io, two, qe, qo, qfe, qfo);
 }
 
 // Points a launch leaves as they are (already relaxed by the boundary-first chain of this k-parity, dist3.cpp): `skm`

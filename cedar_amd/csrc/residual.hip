@@ -263,4 +263,9 @@ void sumsq_interior(const real_t *v, int II, int JJ, int KK, real_t *scratch, re
 	hipLaunchKernelGGL(sumsq_stage2, dim3(1), dim3(256), 0, st, scratch, SUMSQ_NB, out);
 }
 
+void sumsq_interior_many(const real_t *v, int II, int JJ, int KK, real_t *scratch, real_t *out, hipStream_t st, Batch bt)
+{
+	for (int m = 0; m < bt.n; m++) sumsq_interior(v + (size_t)m * bt.stride, II, JJ, KK, scratch, out + m, st);
+}
+
 } // namespace cedar_amd

@@ -100,8 +100,10 @@ struct cedar_amd_solver {
 	int gnb = 1; // batch count the graph was captured for
 	hipStream_t gstream = nullptr;
 	bool use_graph = true;
-	// batch of independent right-hand sides on this one hierarchy (2D, Dirichlet, V-cycle; plane relaxation runs the
-	// planes of a colour as one batch): every level's vectors hold nb_alloc items, a cycle works on the first nb
+	// batch of independent right-hand sides on this one hierarchy (Dirichlet, V-cycle; 2D, and 3D point relaxation;
+	// plane relaxation runs the planes of a colour as one batch, cedar_amd_solver_*_many the caller's right-hand sides):
+	// every level's vectors hold nb_alloc items, a cycle works on the first nb.  3D with nb > 1: the kernels of many3d.hip
+	// in the reference order; nb == 1: the single-vector kernels, whatever nb_alloc is
 	int nb_alloc = 1, nb = 1;
 	// a second captured cycle: the two colours of a plane sweep may differ by one plane
 	hipGraphExec_t gexec2 = nullptr;
@@ -191,6 +193,10 @@ bool ilv_wanted(const Level &L)
 void residual(const cedar_amd_solver *s, const Level &L, const real_t *x, const real_t *b, real_t *r, hipStream_t st)
 {
 	if (s->nd == 2) residual2(L.A, b, x, r, L.II, L.JJ, L.nst, st, Batch{s->nb, L.npts});
+	else if (s->nb > 1 && L.nst == 14)
+		residual27_many(L.Ailv ? op3_ilv(L.Ailv, L.II, L.JJ, L.KK) : op3_cedar(L.A, L.SOR0, L.II, L.JJ, L.KK), b, x, r, L.II, L.JJ,
+		                L.KK, st, Batch{s->nb, L.npts});
+	else if (s->nb > 1) residual7_many(L.A, b, x, r, L.II, L.JJ, L.KK, st, Batch{s->nb, L.npts});
 	else if (L.Ailv) residual27_op(op3_ilv(L.Ailv, L.II, L.JJ, L.KK), b, x, r, L.II, L.JJ, L.KK, st);
 	else residual3(L.A, b, x, r, L.II, L.JJ, L.KK, L.nst, st);
 }
@@ -366,6 +372,14 @@ void smooth(const cedar_amd_solver *s, const Level &L, real_t *x, const real_t *
 			relax3_gs_per(L.A, b, x, L.SOR0, L.II, L.JJ, L.KK, L.nst, updown, s->st.ibc, st, consistent);
 			continue;
 		}
+		if (s->nd == 3 && s->nb > 1) { // a batch of right-hand sides: reference order, operator fetched once (many3d.hip)
+			const Batch bt{s->nb, L.npts};
+			if (L.nst == 14)
+				relax3_gs27_many(L.Ailv ? op3_ilv(L.Ailv, L.II, L.JJ, L.KK) : op3_cedar(L.A, L.SOR0, L.II, L.JJ, L.KK), b, x, L.II,
+				                 L.JJ, L.KK, updown, st, bt);
+			else relax3_gs7_many(L.A, b, x, L.SOR0, L.II, L.JJ, L.KK, updown, st, bt);
+			continue;
+		}
 		if (s->nd == 3) {
 			if (L.Ailv) relax3_gs27_op(op3_ilv(L.Ailv, L.II, L.JJ, L.KK), b, x, L.II, L.JJ, L.KK, updown, st, L.T);
 			else if (L.T) relax3_gs27_op(op3_cedar(L.A, L.SOR0, L.II, L.JJ, L.KK), b, x, L.II, L.JJ, L.KK, updown, st, L.T);
@@ -404,7 +418,7 @@ void coarse_solve(cedar_amd_solver *s, real_t *x, const real_t *b, hipStream_t s
 	if (s->nd == 2 && s->st.ibc) solve_cg2_per(x, b, C.II, C.JJ, s->ABD, s->bbd, s->nabd1, s->st.ibc, st);
 	else if (s->nd == 2) solve_cg2(x, b, C.II, C.JJ, s->ABD, s->bbd, s->nabd1, s->nabd2, st, Batch{s->nb, C.npts});
 	else if (s->st.ibc) solve_cg3_per(x, b, C.II, C.JJ, C.KK, s->ABD, s->bbd, s->nabd1, s->st.ibc, st);
-	else solve_cg3(x, b, C.II, C.JJ, C.KK, s->ABD, s->bbd, s->nabd1, s->nabd2, st);
+	else solve_cg3(x, b, C.II, C.JJ, C.KK, s->ABD, s->bbd, s->nabd1, s->nabd2, st, Batch{s->nb, C.npts});
 }
 
 void ncycle(cedar_amd_solver *s, int lvl, real_t *x, const real_t *b, hipStream_t st)
@@ -425,6 +439,8 @@ void ncycle(cedar_amd_solver *s, int lvl, real_t *x, const real_t *b, hipStream_
 	if (s->nd == 2 && s->st.ibc) restrict2_per(L.res, K.b, K.P, L.II, L.JJ, K.II, K.JJ, s->st.ibc, st);
 	else if (s->nd == 2) restrict2(L.res, K.b, K.P, L.II, L.JJ, K.II, K.JJ, st, Batch{s->nb, L.npts}, Batch{s->nb, K.npts});
 	else if (s->st.ibc) restrict3_per(L.res, K.b, K.P, L.II, L.JJ, L.KK, K.II, K.JJ, K.KK, s->st.ibc, st);
+	else if (s->nb > 1)
+		restrict3_many(L.res, K.b, K.P, L.II, L.JJ, L.KK, K.II, K.JJ, K.KK, st, Batch{s->nb, L.npts}, Batch{s->nb, K.npts});
 	else restrict3(L.res, K.b, K.P, L.II, L.JJ, L.KK, K.II, K.JJ, K.KK, st);
 	clear(K.x, K.npts * (size_t)s->nb, st); // coarse_x.set(0.0)
 	}
@@ -438,6 +454,8 @@ void ncycle(cedar_amd_solver *s, int lvl, real_t *x, const real_t *b, hipStream_
 	if (s->nd == 2 && s->st.ibc) interp_add2_per(x, K.x, L.res, L.A, K.P, K.II, K.JJ, L.II, L.JJ, s->st.ibc, st);
 	else if (s->nd == 2) interp_add2(x, K.x, L.res, L.A, K.P, K.II, K.JJ, L.II, L.JJ, st, Batch{s->nb, L.npts}, Batch{s->nb, K.npts});
 	else if (s->st.ibc) interp_add3_per(x, K.x, L.A, L.res, K.P, K.II, K.JJ, K.KK, L.II, L.JJ, L.KK, s->st.ibc, st);
+	else if (s->nb > 1)
+		interp_add3_many(x, K.x, L.A, L.res, K.P, K.II, K.JJ, K.KK, L.II, L.JJ, L.KK, st, Batch{s->nb, L.npts}, Batch{s->nb, K.npts});
 	else interp_add3(x, K.x, L.A, L.res, K.P, K.II, K.JJ, K.KK, L.II, L.JJ, L.KK, st);
 	smooth(s, L, x, b, BMG_UP, s->st.nrelax_post, st);
 }
@@ -641,7 +659,9 @@ static cedar_amd_solver *solver_create(int nd, len_t nx, len_t ny, len_t nz, int
 	// CEDAR_AMD_YLINES_TRANSPOSED=0 keeps the gather / solve / scatter pipeline for cross-checks
 	const char *eyt = getenv("CEDAR_AMD_YLINES_TRANSPOSED");
 	const bool lyt = ly && s->st.ibc == 0 && !(eyt && atoi(eyt) == 0);
-	if (s->nb_alloc > 1 && (nd != 2 || s->st.ibc != 0 || s->st.cycle != 0 || (ly && !lyt))) s->nb_alloc = 1; // batches: see the struct
+	// batches (see the struct): Dirichlet V-cycles; 2D with the y-lines on transposed arrays, 3D point relaxation
+	if (s->nb_alloc > 1 && (s->st.ibc != 0 || s->st.cycle != 0 || (ly && !lyt) || (nd == 3 && s->st.relaxation != CEDAR_AMD_RELAX_POINT)))
+		s->nb_alloc = 1;
 	level_init(s->lv[0], nd, (int)nx, (int)ny, (int)nz, nstencil, false, ly, lyt, s->nb_alloc);
 	Level &F0 = s->lv[0];
 	if (own_device_so && is_device_ptr(so)) {
@@ -679,7 +699,7 @@ static cedar_amd_solver *solver_create(int nd, len_t nx, len_t ny, len_t nz, int
 	}
 	s->ABD = dalloc((size_t)s->nabd1 * s->nabd2);
 	s->bbd = dalloc((size_t)s->nabd2 * s->nb_alloc);
-	s->red = dalloc(4100);
+	s->red = dalloc(4100 + (size_t)s->nb_alloc); // 4096 partials, then one sum of squares per batch item
 	CEDAR_HIP_CHECK(hipMalloc((void **)&s->dinfo, 64));
 	CEDAR_HIP_CHECK(hipMemsetAsync(s->dinfo, 0, 64, st));
 
@@ -889,6 +909,113 @@ int cedar_amd_solver_solve(cedar_amd_solver *s, const real_t *b, real_t *x, real
 	}
 	launch_check("cedar_amd_solver_solve");
 	return it;
+}
+
+// ---- several right-hand sides at once on the one resident hierarchy (include/cedar_amd.h): the operator, 1/diag and the
+// interpolation weights are the same for every right-hand side, so the kernels fetch them once per workgroup task
+cedar_amd_solver *cedar_amd_solver_create_many(int nd, len_t nx, len_t ny, len_t nz, int nstencil, const real_t *so,
+                                               int own_device_so, const cedar_amd_settings *settings, int max_rhs)
+{
+	if (max_rhs < 1 || max_rhs > CEDAR_AMD_MAX_RHS) {
+		char msg[] = "cedar_amd_solver_create_many: max_rhs must be 1 .. 32; no solver created";
+		print_error(msg);
+		return nullptr;
+	}
+	return solver_create(nd, nx, ny, nz, nstencil, so, own_device_so, settings, max_rhs);
+}
+
+int cedar_amd_solver_max_rhs(const cedar_amd_solver *s) { return null_handle(s, "cedar_amd_solver_max_rhs") ? 0 : s->nb_alloc; }
+
+// what the batched entry points cannot do: reported, nothing written
+static bool many_refused(const cedar_amd_solver *s, int nrhs, const char *who)
+{
+	const char *why = nullptr;
+	if (nrhs < 1) why = "nrhs must be at least 1";
+	else if (s->st.ibc != 0) why = "periodic boundary conditions (ibc != 0) are not supported";
+	else if (s->st.cycle != 0) why = "only the V-cycle is supported";
+	else if (s->nd == 3 && s->st.relaxation != CEDAR_AMD_RELAX_POINT) why = "3D plane relaxation is not supported";
+	else if (nrhs > s->nb_alloc) why = "nrhs exceeds the handle's max_rhs (cedar_amd_solver_create_many)";
+	if (!why) return false;
+	char msg[256];
+	snprintf(msg, sizeof(msg), "%s: %s; nothing done", who, why);
+	print_error(msg);
+	return true;
+}
+
+// the batch count holds for the duration of one _many call: every other entry point works on item 0
+struct BatchScope {
+	cedar_amd_solver *s;
+	BatchScope(cedar_amd_solver *s_, int nrhs) : s(s_) { s->nb = nrhs; }
+	~BatchScope() { s->nb = 1; }
+};
+
+// ||v_m||_2 of the first s->nb items of a level-0 vector: one host read of nb doubles
+static void l2_many(cedar_amd_solver *s, const Level &L, const real_t *v, double *out)
+{
+	hipStream_t st = current_stream();
+	sumsq_interior_many(v, L.II, L.JJ, L.KK, s->red, s->red + 4096, st, Batch{s->nb, L.npts});
+	CEDAR_HIP_CHECK(hipMemcpyAsync(out, s->red + 4096, (size_t)s->nb * sizeof(double), hipMemcpyDeviceToHost, st));
+	CEDAR_HIP_CHECK(hipStreamSynchronize(st));
+	for (int m = 0; m < s->nb; m++) out[m] = std::sqrt(out[m]);
+}
+
+int cedar_amd_solver_vcycle_many(cedar_amd_solver *s, int nrhs, real_t *x, const real_t *b)
+{
+	if (null_handle(s, "cedar_amd_solver_vcycle_many") || many_refused(s, nrhs, "cedar_amd_solver_vcycle_many")) return -1;
+	const Level &L = s->lv[0];
+	BatchScope scope(s, nrhs);
+	Staged sx(x, L.npts * nrhs, true, true), sb(b, L.npts * nrhs, true, false);
+	if (sx.staged() || sb.staged()) cycle_launch(s, sx.get(), sb.get(), current_stream()); // staging buffers change from call to call
+	else cycle_dev(s, sx.get(), sb.get());
+	launch_check("cedar_amd_solver_vcycle_many");
+	return 0;
+}
+
+int cedar_amd_solver_solve_many(cedar_amd_solver *s, int nrhs, const real_t *b, real_t *x, real_t *rel, int *iters)
+{
+	if (null_handle(s, "cedar_amd_solver_solve_many") || many_refused(s, nrhs, "cedar_amd_solver_solve_many")) return -1;
+	Level &L = s->lv[0];
+	BatchScope scope(s, nrhs);
+	Staged sx(x, L.npts * nrhs, true, true), sb(b, L.npts * nrhs, true, false);
+	hipStream_t st = current_stream();
+	const int maxit = s->st.max_iter;
+	const size_t ld = (size_t)(maxit > 0 ? maxit : 0) + 1; // row length of rel
+	double res0[CEDAR_AMD_MAX_RHS], nrm[CEDAR_AMD_MAX_RHS];
+	bool met[CEDAR_AMD_MAX_RHS];
+	residual(s, L, sx.get(), sb.get(), L.res, st);
+	l2_many(s, L, L.res, res0);
+	int open = 0;
+	for (int m = 0; m < nrhs; m++) {
+		rel[m * ld] = res0[m];
+		met[m] = res0[m] == 0.0; // a zero residual: converged from the start (a single solve would record 0/0)
+		if (iters) iters[m] = met[m] ? 0 : maxit;
+		open += met[m] ? 0 : 1;
+	}
+	int it = 0;
+	while (open > 0 && it < maxit) {
+		cycle_dev(s, sx.get(), sb.get());
+		residual(s, L, sx.get(), sb.get(), L.res, st);
+		l2_many(s, L, L.res, nrm);
+		it++;
+		for (int m = 0; m < nrhs; m++) {
+			const double r = res0[m] == 0.0 ? 0.0 : nrm[m] / res0[m];
+			rel[m * ld + it] = r;
+			if (!met[m] && r < s->st.tol) {
+				met[m] = true;
+				if (iters) iters[m] = it;
+				open--;
+			}
+		}
+	}
+	launch_check("cedar_amd_solver_solve_many");
+	return it;
+}
+
+float cedar_amd_solver_time_vcycles_many(cedar_amd_solver *s, int nrhs, real_t *x_dev, const real_t *b_dev, int n)
+{
+	if (null_handle(s, "cedar_amd_solver_time_vcycles_many") || many_refused(s, nrhs, "cedar_amd_solver_time_vcycles_many")) return -1.f;
+	BatchScope scope(s, nrhs);
+	return cedar_amd_solver_time_vcycles(s, x_dev, b_dev, n);
 }
 
 // ---- preconditioned conjugate gradient (BoxMG's PCG: src/{2d,3d}/ftn/BMG_PCG_parameters_f90.h) on the resident

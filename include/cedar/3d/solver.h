@@ -136,7 +136,10 @@ protected:
 			st.plane_max_iter = pst.max_iter; st.plane_min_coarse = pst.min_coarse; st.plane_tol = pst.tol;
 		}
 		BMG_get_bc(this->kman->get_params()->per_mask(), &st.ibc);
-		this->h = cedar_amd_solver_create(3, fop.shape(0), fop.shape(1), fop.shape(2), stencil_ndirs<fsten>::value, fop.data(), 0, &st);
+		// solver.max-rhs (default 1): room for that many right-hand sides on every level (multilevel::solve_many)
+		const int max_rhs = this->conf->template get<int>("solver.max-rhs", 1);
+		if (max_rhs == 1) this->h = cedar_amd_solver_create(3, fop.shape(0), fop.shape(1), fop.shape(2), stencil_ndirs<fsten>::value, fop.data(), 0, &st);
+		else this->h = cedar_amd_solver_create_many(3, fop.shape(0), fop.shape(1), fop.shape(2), stencil_ndirs<fsten>::value, fop.data(), 0, &st, max_rhs);
 		if (!this->h)
 			log::error << "cdr3::solver: the device-resident solver could not be created for these settings (reported above)" << std::endl;
 	}

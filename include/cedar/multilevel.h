@@ -13,6 +13,7 @@
 // host arrays are filled from HBM on first access.
 #ifndef CEDAR_MULTILEVEL_H
 #define CEDAR_MULTILEVEL_H
+#include <algorithm>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -139,6 +140,45 @@ public:
 		log::info << "Initial residual l2 norm: " << rel[0] << std::endl;
 		for (int i = 0; i < n; i++) log::status << "PCG iteration " << i << " relative l2 norm: " << rel[i + 1] << std::endl;
 		history.assign(rel.begin(), rel.begin() + n + 1);
+	}
+
+	// several right-hand sides in lockstep on the one hierarchy (cedar_amd_solver_solve_many; room for them is made with
+	// the key solver.max-rhs).  histories[m] / iterations[m]: item m's residual history cut to the cycles run and the
+	// cycles after which it first met the tolerance; `history` holds item 0's.  Resident path only.
+	std::vector<std::vector<real_t>> histories;
+	std::vector<int> iterations;
+	void solve_many(const std::vector<grid_func> & b, std::vector<grid_func> & x)
+	{
+		history.clear();
+		histories.clear();
+		iterations.clear();
+		if (!resident()) {
+			log::error << "solve_many: needs the device-resident solver (every kernel \"hip\")" << std::endl;
+			return;
+		}
+		const std::size_t nrhs = b.size();
+		if (nrhs == 0 || x.size() != nrhs) {
+			log::error << "solve_many: b and x must hold the same number (at least one) of grid functions" << std::endl;
+			return;
+		}
+		// the C ABI takes the items back to back
+		const std::size_t npts = b[0].size(), ld = (std::size_t)settings.maxiter + 1;
+		std::vector<real_t> bb(npts * nrhs), xx(npts * nrhs), rel(ld * nrhs);
+		for (std::size_t m = 0; m < nrhs; m++) {
+			std::copy(b[m].data(), b[m].data() + npts, bb.begin() + m * npts);
+			std::copy(x[m].data(), x[m].data() + npts, xx.begin() + m * npts);
+		}
+		iterations.assign(nrhs, 0);
+		const int n = cedar_amd_solver_solve_many(h, (int)nrhs, bb.data(), xx.data(), rel.data(), iterations.data());
+		if (n < 0) {
+			iterations.clear();
+			return;
+		}
+		for (std::size_t m = 0; m < nrhs; m++) {
+			std::copy(xx.begin() + m * npts, xx.begin() + (m + 1) * npts, x[m].data());
+			histories.emplace_back(rel.begin() + m * ld, rel.begin() + m * ld + n + 1);
+		}
+		history = histories[0];
 	}
 
 	void vcycle(grid_func & x, const grid_func & b)

@@ -388,6 +388,53 @@ int cedar_amd_solver_pcg(cedar_amd_solver *s, const real_t *b, real_t *x, const 
  * z, r host or device.  Refused (z untouched) on the settings cedar_amd_solver_pcg refuses for precon = 3. */
 void cedar_amd_solver_precondition(cedar_amd_solver *s, real_t *z, const real_t *r);
 
+/* Several right-hand sides at once on one resident hierarchy.  The operator, 1/diag and the interpolation weights are
+ * the same for every right-hand side, so the batched 3D kernels (many3d.hip) fetch them once per workgroup task and apply
+ * them to all items from registers; the 2D kernels take the item from the launch grid.
+ * Storage: the vectors of a batch are stored item-major, back to back: item m of a level-0 vector starts at
+ * m * (nx+2)(ny+2)(nz+2) doubles (2D: (nx+2)(ny+2)).  Host or device pointers.
+ * Exactness: the batched kernels keep the reference's term order on every level, so item m of any batched result has the
+ * bits of the single-vector reference-order computation on item m alone (what cedar_amd_solver_vcycle / _solve give
+ * where no level takes the partial-sum sweep, i.e. no 27-point level of 160 rows or more, or under CEDAR_AMD_PSUM=0).
+ *  - A handle made with max_rhs > 1 still serves every single-vector entry point (_solve, _vcycle, _pcg, _precondition,
+ *    _get, _set, _time_*) on item 0, unchanged: those calls run the single-vector kernels.
+ *  - Supported: 3D 7- and 27-point and 2D 5- and 9-point, Dirichlet (ibc == 0), V-cycle; 3D point relaxation; 2D point
+ *    and line relaxation.  The _many calls are refused (print_error, return -1, nothing written) for nrhs < 1,
+ *    nrhs > max_rhs, ibc != 0, an F-cycle and 3D plane relaxation; such a handle reports max_rhs 1.
+ *  - Items nrhs .. max_rhs-1 are not touched (the solver's own level vectors of the unused items may hold anything).
+ *  - Not offered: _pcg on several right-hand sides, the domain-decomposed solvers, the bmg2_/bmg3_ C interface. */
+enum { CEDAR_AMD_MAX_RHS = 32 };
+/* as cedar_amd_solver_create, with room for max_rhs right-hand sides (1 .. 32) on every level; max_rhs outside that range:
+ * print_error, NULL */
+cedar_amd_solver *cedar_amd_solver_create_many(int nd, len_t nx, len_t ny, len_t nz, int nstencil,
+                                               const real_t *so, int own_device_so,
+                                               const cedar_amd_settings *settings, int max_rhs);
+int cedar_amd_solver_max_rhs(const cedar_amd_solver *s); /* 1 for cedar_amd_solver_create */
+/* one cycle on each of the first nrhs items; 0, or -1 when refused (nothing written) */
+int cedar_amd_solver_vcycle_many(cedar_amd_solver *s, int nrhs, real_t *x, const real_t *b);
+/* multilevel::solve for nrhs right-hand sides in lockstep.
+ * rel: nrhs rows of max_iter+1 entries, row m as cedar_amd_solver_solve writes it for item m;
+ * iters[m]: cycles after which item m first met tol (max_iter if it never did); may be NULL.
+ * All items are cycled until every one has met tol or max_iter is reached: an item that met tol early keeps being cycled
+ * and its rel row keeps being written; entries of rel beyond the cycles run are not touched.  An item whose initial
+ * residual norm is exactly 0 counts as converged from the start (iters[m] = 0, its rel row is 0, 0, ... for the cycles
+ * run), so that one zero column does not hold the batch for max_iter cycles: the one deliberate difference from calling
+ * cedar_amd_solver_solve per item, which would record 0/0.  Returns the cycles run, -1 when refused. */
+int cedar_amd_solver_solve_many(cedar_amd_solver *s, int nrhs, const real_t *b, real_t *x, real_t *rel, int *iters);
+/* timing aid next to cedar_amd_solver_time_vcycles: n cycles on nrhs device-resident items, HIP-event ms (-1: refused) */
+float cedar_amd_solver_time_vcycles_many(cedar_amd_solver *s, int nrhs, real_t *x_dev, const real_t *b_dev, int n);
+/* The batched 3D kernels one by one on caller arrays (host or device; vectors hold nrhs items back to back, operator
+ * arrays are shared); argument order of the BMG3_SymStd_* drop-ins, nstncl = 4|14, Dirichlet.  interp_add3 keeps the
+ * reference's side effect (res /= so(kp)) per item.  0, or -1 (print_error, nothing done) for nrhs outside 1 .. 32, an
+ * nstncl they do not serve or a NULL array. */
+int cedar_amd_relax3_gs_many(int nrhs, real_t *so, real_t *qf, real_t *q, real_t *sor, len_t ii, len_t jj, len_t kk, int nstncl,
+                             int updown);
+int cedar_amd_residual3_many(int nrhs, real_t *so, real_t *qf, real_t *q, real_t *res, len_t ii, len_t jj, len_t kk, int nstncl);
+int cedar_amd_restrict3_many(int nrhs, real_t *q, real_t *qc, real_t *ci, len_t ii, len_t jj, len_t kk, len_t iic, len_t jjc,
+                             len_t kkc);
+int cedar_amd_interp_add3_many(int nrhs, real_t *q, real_t *qc, real_t *so, real_t *res, real_t *ci, len_t iic, len_t jjc,
+                               len_t kkc, len_t iif, len_t jjf, len_t kkf, int nstncl);
+
 /* plane relaxation as a kernel of its own -- kernels::plane_relax<stypes, rdir>::setup(so) / run(so, x, b, dir)
  * (include/cedar/kernels/plane_relax.h:10-33; include/cedar/3d/relax_planes.h:164-246, src/3d/relax_planes.cc).
  * dir 0 = xy planes, 1 = xz, 2 = yz; plane_settings = the 2D solvers' configuration (NULL: the reference's default
