@@ -522,11 +522,16 @@ void cedar_amd_relax3_cols_strip(const real_t *strip_lo, const real_t *strip_hi,
 	relax3_cols27_strip(strip_lo, strip_hi, qf, q, (int)ii, (int)jj, (int)kk, jb, kb, ncol, cols, xrow0, xrow1, current_stream());
 }
 
+int cedar_amd_relax3_masked_ok(const real_t *so, len_t ii, len_t jj, len_t kk)
+{
+	return (!so || is_device_ptr(so)) && relax3_masked_ok(so, (int)ii, (int)jj, (int)kk) ? 1 : 0;
+}
+
 int cedar_amd_relax3_planes_masked(real_t *so, real_t *qf, real_t *q, real_t *sor, len_t ii, len_t jj, len_t kk, int kb,
                                    int up, unsigned cols_f, unsigned cols_s, const int *rows)
 {
 	if (!is_device_ptr(so) || !is_device_ptr(q) || !is_device_ptr(qf) || !is_device_ptr(sor)) return 0; // registered operators only
-	if (((ii - 2) & 1) || ((jj - 2) & 1) || ii - 2 < 8) return 0;
+	if (!relax3_masked_ok(so, (int)ii, (int)jj, (int)kk)) return 0;
 	PsumSkip sk = psum_skip_none();
 	sk.colsF = cols_f & 0xffu; sk.colsS = cols_s & 0xffu;
 	for (int t = 0; t < 3; t++) sk.rows[t] = rows ? rows[t] : -1;

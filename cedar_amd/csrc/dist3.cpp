@@ -10,8 +10,9 @@
 // enqueue per 2x2x2 cycle); here it is compiled code: a rank process creates a handle and calls vcycle / solve, Python
 // keeps only the rank bootstrap (unique id over TCP).  Same design rule as dist.py -- serial equivalence by
 // construction: every rank runs the serial kernels on its box (owned points + one ghost layer), ghost layers hold the
-// owner's current values whenever a kernel reads them, local extents stay even on every distributed level so local
-// and global parities coincide; the N-rank residual history equals the single-domain history (the reference's own
+// owner's current values whenever a kernel reads them, local extents stay even along every split direction on the
+// distributed levels (an unsplit direction may be odd: its box starts at the global origin) so local and global parities
+// coincide; the N-rank residual history equals the single-domain history (the reference's own
 // criterion, test/3d/mpi/test_relax.cc:56-59).
 //
 // Transport: the library's RCCL communicator (comm.cpp) -- or a caller-supplied table of three functions, the
@@ -96,8 +97,13 @@ void gather_into(cedar_amd_dist3 *d, real_t *local, int lII, int lJJ, int lKK, i
 // Both colours of a row class run in one kernel with the ghost column of side Q still stale: its c2 column d0 is
 // recomputed after the exchange (nobody has read it in between) -- three exchanges within the rank's z layer per parity
 // (one without an x split), each restricted to what the stage changed, then the launch, then one exchange with everything else.
-void chain_parity(cedar_amd_dist3 *d, DLevel &L, real_t *x, real_t *b, int kb, bool up)
+// Returns false, with nothing relaxed and nothing sent, where the masked launch would refuse (its own predicate,
+// cedar_amd_relax3_masked_ok: setup() decided with it, so that happens only if the registration of the operator has been
+// released or replaced since); smooth() then relaxes the parity by the row-class passes.  The answer depends on the extents
+// and the environment alone, which every rank shares, so the ranks take the same branch and their exchanges still pair up.
+bool chain_parity(cedar_amd_dist3 *d, DLevel &L, real_t *x, real_t *b, int kb, bool up)
 {
+	if (!cedar_amd_relax3_masked_ok(L.A, L.II, L.JJ, L.KK) || !is_device_ptr(x) || !is_device_ptr(b)) return false;
 	const int nx = L.n[0], ny = L.n[1];
 	const int jbF = up ? 0 : 1, jbS = 1 - jbF;
 	int colsF[8], colsS[8], fixc[2], nF = 0, nS = 0, nfix = 0;
@@ -166,13 +172,39 @@ void chain_parity(cedar_amd_dist3 *d, DLevel &L, real_t *x, real_t *b, int kb, b
 	// The launch reads no ghost cell of the rank's own z layer: only the points of a boundary column / row do, and those are
 	// chain points (its ghost-column sources feed partial sums of column d0 in the planes of the other parity -- chain points
 	// again, relaxed from the operator).  The S rows therefore travel with the exchange across z after the launch.
-	if (!cedar_amd_relax3_planes_masked(L.A, b, x, L.sor, L.II, L.JJ, L.KK, kb, up, mF, mS, skip)) {
-		char m[] = "cedar_amd_dist3: the masked launch refused a level set up for it";
-		print_error(m);
-	}
+	// (cannot refuse: everything it checks was checked on entry)
+	(void)cedar_amd_relax3_planes_masked(L.A, b, x, L.sor, L.II, L.JJ, L.KK, kb, up, mF, mS, skip);
 	auto all = [](const int *) { return true; };
 	auto rows_last = [&](const int *o) { return o[2] == 0 ? jparS : -1; };
 	halo_exchange_sub(d, L.halo, L.II, L.JJ, L.KK, x, all, all, rows_last, kpar);
+	return true;
+}
+
+// One k-parity of planes on a rank grid with an x / y split in the reference order: its two row classes, an exchange after each
+void rowclass_parity(cedar_amd_dist3 *d, DLevel &L, real_t *x, real_t *b, int kb, bool up)
+{
+	for (int t = 0; t < 2; t++) {
+		const int jb = up ? t : 1 - t;
+		if (L.overlap) {
+			// interior rows first: they read no y/z ghost, whose exchange (previous pass) may still be in flight on the
+			// side stream; then join and relax the shell rows
+			cedar_amd_relax3_pass_part(L.A, b, x, L.sor, L.II, L.JJ, L.KK, jb, kb, up, 1 | (d->sides << 4));
+			side_wait(d);
+			cedar_amd_relax3_pass_part(L.A, b, x, L.sor, L.II, L.JJ, L.KK, jb, kb, up, 2 | (d->sides << 4));
+		} else
+			cedar_amd_relax3_pass_part(L.A, b, x, L.sor, L.II, L.JJ, L.KK, jb, kb, up, 0);
+		if (d->p[0] > 1) {
+			// the second i-colour of the column next to an x neighbour needs that neighbour's fresh first colour
+			if (halo_exchange_x(d, L.halo, L.II, L.JJ, L.KK, x, up)) cedar_amd_relax3_fixup(L.A, b, x, L.sor, L.II, L.JJ, L.KK, up ? L.n[0] : 1, jb, kb);
+		}
+		if (L.overlap) {
+			halo_exchange(d, L.halo, L.II, L.JJ, L.KK, x, 1, 1); // x ghosts are read by every row of the next pass: in order
+			void *m = side_begin(d);
+			halo_exchange(d, L.halo, L.II, L.JJ, L.KK, x, 1, 2);
+			side_end(d, m);
+		} else
+			halo_exchange(d, L.halo, L.II, L.JJ, L.KK, x, 1, 0);
+	}
 }
 
 void smooth(cedar_amd_dist3 *d, DLevel &L, real_t *x, real_t *b, int updown, int nsweeps)
@@ -180,7 +212,10 @@ void smooth(cedar_amd_dist3 *d, DLevel &L, real_t *x, real_t *b, int updown, int
 	const bool up = updown == BMG_UP;
 	for (int it = 0; it < nsweeps; it++) {
 		if (L.chain) {
-			for (int c = 0; c < 2; c++) chain_parity(d, L, x, b, up ? c : 1 - c, up);
+			for (int c = 0; c < 2; c++) {
+				const int kb = up ? c : 1 - c;
+				if (!chain_parity(d, L, x, b, kb, up)) rowclass_parity(d, L, x, b, kb, up);
+			}
 			continue;
 		}
 		if (L.nst == 4) {
@@ -210,28 +245,7 @@ void smooth(cedar_amd_dist3 *d, DLevel &L, real_t *x, real_t *b, int updown, int
 			}
 			continue;
 		}
-		for (int c = 0; c < 4; c++) {
-			const int cc = up ? c : 3 - c, jb = cc & 1, kb = cc >> 1;
-			if (L.overlap) {
-				// interior rows first: they read no y/z ghost, whose exchange (previous pass) may still be in flight on the
-				// side stream; then join and relax the shell rows
-				cedar_amd_relax3_pass_part(L.A, b, x, L.sor, L.II, L.JJ, L.KK, jb, kb, up, 1 | (d->sides << 4));
-				side_wait(d);
-				cedar_amd_relax3_pass_part(L.A, b, x, L.sor, L.II, L.JJ, L.KK, jb, kb, up, 2 | (d->sides << 4));
-			} else
-				cedar_amd_relax3_pass_part(L.A, b, x, L.sor, L.II, L.JJ, L.KK, jb, kb, up, 0);
-			if (d->p[0] > 1) {
-				// the second i-colour of the column next to an x neighbour needs that neighbour's fresh first colour
-				if (halo_exchange_x(d, L.halo, L.II, L.JJ, L.KK, x, up)) cedar_amd_relax3_fixup(L.A, b, x, L.sor, L.II, L.JJ, L.KK, up ? L.n[0] : 1, jb, kb);
-			}
-			if (L.overlap) {
-				halo_exchange(d, L.halo, L.II, L.JJ, L.KK, x, 1, 1); // x ghosts are read by every row of the next pass: in order
-				void *m = side_begin(d);
-				halo_exchange(d, L.halo, L.II, L.JJ, L.KK, x, 1, 2);
-				side_end(d, m);
-			} else
-				halo_exchange(d, L.halo, L.II, L.JJ, L.KK, x, 1, 0);
-		}
+		for (int c = 0; c < 2; c++) rowclass_parity(d, L, x, b, up ? c : 1 - c, up);
 	}
 	side_wait(d);
 }
@@ -297,12 +311,16 @@ void setup(cedar_amd_dist3 *d)
 		// slab decomposition: its sweeps are the plane-fused passes of the single-GPU solver, which read the
 		// row-interleaved solve copy where one is registered (worth 7 %; neutral on rank grids with an x / y split)
 		if (F.nst == 14 && d->p[0] == 1 && d->p[1] == 1) cedar_amd_relax3_prepare(F.A, F.sor, F.II, F.JJ, F.KK);
-		// x / y split: where the level takes the partial-sum sweep (scratch registered: bit 1), the boundary-first chain
-		// (chain_parity); CEDAR_AMD_DIST_CHAIN=0 keeps the reference-order row-class passes
-		else if (F.nst == 14 && F.n[0] >= 8 && F.n[1] >= 8 && !(getenv("CEDAR_AMD_DIST_CHAIN") && !atoi(getenv("CEDAR_AMD_DIST_CHAIN"))) &&
-		         F.n[1] >= (getenv("CEDAR_AMD_DIST_CHAIN_MIN") ? atoi(getenv("CEDAR_AMD_DIST_CHAIN_MIN")) : 0))
-			F.chain = (cedar_amd_relax3_prepare_rows(F.A, F.sor, F.II, F.JJ, F.KK,
-			                                         getenv("CEDAR_AMD_DIST_PSUM_MIN") ? atoi(getenv("CEDAR_AMD_DIST_PSUM_MIN")) : 128) & 2) != 0;
+		// x / y split: where the level takes the partial-sum sweep, the boundary-first chain (chain_parity) -- decided by the
+		// predicate the masked launch itself applies once the scratch is registered (even nx and ny, 8 .. 512 points per row):
+		// a level with an odd extent along an unsplit x or y keeps the reference-order row-class passes, as does every level
+		// with CEDAR_AMD_DIST_CHAIN=0
+		else if (F.nst == 14 && F.n[1] >= 8 && cedar_amd_relax3_masked_ok(nullptr, F.II, F.JJ, F.KK) &&
+		         !(getenv("CEDAR_AMD_DIST_CHAIN") && !atoi(getenv("CEDAR_AMD_DIST_CHAIN"))) &&
+		         F.n[1] >= (getenv("CEDAR_AMD_DIST_CHAIN_MIN") ? atoi(getenv("CEDAR_AMD_DIST_CHAIN_MIN")) : 0)) {
+			cedar_amd_relax3_prepare_rows(F.A, F.sor, F.II, F.JJ, F.KK, getenv("CEDAR_AMD_DIST_PSUM_MIN") ? atoi(getenv("CEDAR_AMD_DIST_PSUM_MIN")) : 128);
+			F.chain = cedar_amd_relax3_masked_ok(F.A, F.II, F.JJ, F.KK) != 0;
+		}
 		if (F.chain && F.n[0] >= 12 && !(getenv("CEDAR_AMD_DIST_STRIP") && !atoi(getenv("CEDAR_AMD_DIST_STRIP"))))
 			for (int side = 0; side < 2; side++)
 				if (has_nb(d, 0, side ? +1 : -1)) {

@@ -36,6 +36,9 @@ void relax3_planes27_psum(const Op3 &A, const real_t *qf, real_t *q, real_t *T, 
                           int nrk, int nbr, int frun, hipStream_t st, const PsumSkip *skip = nullptr);
 // the same through the operator's registration (relax3_prepare), every plane of the parity, in order (no halo in flight):
 // the launch of a rank grid with an x / y split after its boundary-first chain.  false = the level has no partial-sum sweep.
+// and everything that makes it refuse (odd nx / ny, rows outside 8 .. 512 points, no scratch registered), as one predicate;
+// so = nullptr asks about the shape alone
+bool relax3_masked_ok(const real_t *so, int II, int JJ, int KK);
 bool relax3_planes27_masked(const real_t *so, const real_t *qf, real_t *q, const real_t *sor, int II, int JJ, int KK, int kb,
                             int up, const PsumSkip &skip, hipStream_t st);
 // relax3_prepare with the partial-sum sweep registered from psum_min_rows rows on (runs of 8 rows below the levels that take

@@ -824,13 +824,28 @@ void relax3_planes27(const real_t *so, const real_t *qf, real_t *q, const real_t
 	}
 }
 
+// The one predicate of the masked launch: relax3_planes27_masked applies it, and the distributed driver decides with it which
+// levels take the boundary-first chain (dist3.cpp setup / smooth), so the two cannot disagree.  Even nx and ny: the column
+// masks name the last four points of a row as the lanes P-2, P-1 of full pairs (relax27_dev.h skip27_lane), and the masked
+// walk has only ever been stated and tested with the last row in the second row class; 8 .. 512 points per row; the
+// partial-sum scratch and its run length registered for exactly this operator and shape.  nz is free: an odd number of
+// planes only gives the two k-parities different plane counts.
+bool relax3_masked_ok(const real_t *so, int II, int JJ, int KK)
+{
+	const int nx = II - 2, ny = JJ - 2;
+	if ((nx & 1) || (ny & 1) || nx < 8 || nx > 512 || KK < 3) return false;
+	if (!so) return true; // the shape alone: asked before anything is registered
+	const IlvReg *reg = reg_lookup(so, II, JJ, KK);
+	return reg && reg->T && reg->frun > 0;
+}
+
 bool relax3_planes27_masked(const real_t *so, const real_t *qf, real_t *q, const real_t *sor, int II, int JJ, int KK, int kb,
                             int up, const PsumSkip &skip, hipStream_t st)
 {
+	if (!relax3_masked_ok(so, II, JJ, KK)) return false;
 	const Op3 A = op3_lookup(so, sor, II, JJ, KK);
 	const IlvReg *reg = reg_lookup(so, II, JJ, KK);
-	const int npairs = (II - 2 + 1) / 2, nrk = (KK - 2 - kb + 1) / 2;
-	if (!(reg && reg->T && reg->frun > 0 && npairs >= 4 && npairs <= 256)) return false;
+	const int nrk = (KK - 2 - kb + 1) / 2;
 	if (nrk > 0) relax3_planes27_psum(A, qf, q, reg->T, II, JJ, KK, kb, up, 0, nrk, 0, reg->frun, st, &skip);
 	return true;
 }

@@ -16,7 +16,10 @@ wholesale by grouped point-to-point sends/receives to the (at most 26, on the
 Design rule: *serial equivalence by construction*.  Every rank runs the serial
 kernels on its local box (owned points + one ghost layer); ghost layers always
 hold the owner's current values when a kernel reads them.  Because the local
-extents stay even on every level (512 -> 256 -> ... -> 2 per rank) local and
+extents stay even along every SPLIT direction on every distributed level below
+the gathered one (512 -> 256 -> ... -> 2 per rank; asserted in __init__, as
+cedar_amd_dist3_create checks it -- an unsplit direction may be odd on any level,
+its box starts at the global origin) local and
 global parities coincide, so colourings, coarse-point ownership and all index
 ranges are those of the single-domain run on the global grid, and the residual
 history equals the 1-rank history to rounding -- the reference's own criterion
@@ -514,6 +517,9 @@ class DistSolver3:
                     L.halo.exchange(x)
                 continue
             up = updown == UP
+            # (the statement takes odd unsplit extents too: every update is the reference's, whatever the shape.  The native
+            # driver keeps levels with an odd nx or ny off the chain, cedar_amd_relax3_masked_ok: its masked launch names
+            # the last columns of a row as lanes of full pairs.)
             if self.chain and L.n[0] >= 8 and L.n[1] >= 8:
                 for c in range(2):
                     self._chain_parity(L, x, b, c if up else 1 - c, up)

@@ -204,14 +204,19 @@ void cedar_amd_relax3_fixup(real_t *so, real_t *qf, real_t *q, real_t *sor, len_
  *          (jb,kb) except the rows xrow0 / xrow1 (-1: none);
  *   _planes_masked: cedar_amd_relax3_planes for all planes of the parity, with the points named by the masks skipped --
  *          cols_f / cols_s for the first / second row class of the sweep order: bits 0..3 = columns 1..4, bits 4..7 = the
- *          last four owned columns; rows[3]: whole rows (-1: unused).  Needs even extents, at least 8 columns and the
- *          registration of cedar_amd_relax3_prepare with its scratch; returns 0 (nothing done) otherwise. */
+ *          last four owned columns; rows[3]: whole rows (-1: unused).  Needs even nx and ny, 8 to 512 columns and the
+ *          registration of cedar_amd_relax3_prepare with its scratch (cedar_amd_relax3_masked_ok); returns 0 (nothing done,
+ *          q untouched) otherwise. */
 void cedar_amd_relax3_rows(real_t *so, real_t *qf, real_t *q, real_t *sor, len_t ii, len_t jj, len_t kk, int j0, int jstep,
                            int nrj, int kb, int efirst);
 void cedar_amd_relax3_cols(real_t *so, real_t *qf, real_t *q, real_t *sor, len_t ii, len_t jj, len_t kk, int jb, int kb,
                            int ncol, const int *cols, int xrow0, int xrow1);
 int cedar_amd_relax3_planes_masked(real_t *so, real_t *qf, real_t *q, real_t *sor, len_t ii, len_t jj, len_t kk, int kb,
                                    int up, unsigned cols_f, unsigned cols_s, const int *rows);
+/* The predicate of _planes_masked, which applies it before it launches: 1 where ii-2 and jj-2 are even, a row has 8 to 512
+ * points and `so` is registered with its partial-sum scratch for this shape; so = NULL: the shape alone.  cedar_amd_dist3_*
+ * decides with it which levels take the boundary-first chain, so the driver and the launch cannot disagree. */
+int cedar_amd_relax3_masked_ok(const real_t *so, len_t ii, len_t jj, len_t kk);
 /* _cols on a dense copy of the six operator columns next to an x face (device pointers only; at least 12 columns per row):
  * _strip_build fills out[_strip_doubles(jj,kk)] for the low (side 0: columns 0..5) or the high (side 1: ii-6..ii-1) face from
  * the operator and its SETUP_recip output; _cols_strip takes the copies of the sides its columns lie on (the other may be
@@ -500,7 +505,11 @@ const char *cedar_amd_version(void);
  * ..._SETUP_interp_OI.f90:418-1074, ..._SETUP_ITLI27_ex.f90:1803), norm all-reduce (3d/mpi/grid_func.h:41), coarse levels
  * gathered onto every rank (in place of 3d/mpi/redist_solver.h:221-224).  The whole cycle is orchestrated below this ABI
  * (cedar_amd/csrc/dist3.cpp); a rank process only creates the handle and calls it.  rank = k*px*py + j*px + i
- * (src/3d/util/topo.cc:82-84); every local extent must stay even on the distributed levels.
+ * (src/3d/util/topo.cc:82-84).  Along every SPLIT direction the local extent must be even on every distributed level
+ * below the gathered one (create fails otherwise); along an unsplit direction it may be odd on any level.  On a rank grid
+ * with an x / y split a 27-point level relaxes by the boundary-first chain where cedar_amd_relax3_masked_ok admits it (nx
+ * and ny even, 8 to 512 points per row, at least 8 rows and 128 rows or CEDAR_AMD_FRUN runs for the partial-sum sweep);
+ * every other level, those with an odd unsplit nx or ny among them, keeps the reference-order row-class passes.
  * Transport: `comm` (section 3, RCCL) -- or `transport`, a caller-supplied table, the counterpart of the reference's
  * halo_exchanger plug-in (include/cedar/kernel.h:25-37, kernel_manager::add_halo): exchange has the contract of
  * cedar_amd_comm_exchange (device buffers, ordered with the library's current stream), allgather that of
@@ -532,7 +541,8 @@ void cedar_amd_dist3_destroy(cedar_amd_dist3 *d);
 int cedar_amd_dist3_nlevels(const cedar_amd_dist3 *d);            /* levels of the global hierarchy */
 int cedar_amd_dist3_distributed_levels(const cedar_amd_dist3 *d); /* of which this many are distributed (the last one gathered) */
 /* distributed levels of a rank grid with an x / y split that relax with the partial-sum sweep behind a boundary-first
- * chain (cedar_amd_relax3_planes_masked; CEDAR_AMD_DIST_CHAIN=0: none, the reference-order row-class passes everywhere) */
+ * chain (cedar_amd_relax3_planes_masked; levels it would refuse -- odd nx or ny -- are not counted: they keep the
+ * reference-order row-class passes, as every level does with CEDAR_AMD_DIST_CHAIN=0) */
 int cedar_amd_dist3_chain_levels(const cedar_amd_dist3 *d);
 /* one V-cycle on this rank's device-resident x, b (local boxes incl. ghost layer) */
 void cedar_amd_dist3_vcycle(cedar_amd_dist3 *d, real_t *x_dev, real_t *b_dev);

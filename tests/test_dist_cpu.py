@@ -98,6 +98,19 @@ CASES = [
     ("rand27", (8, 8, 8), (2, 2, 2), 32, True),
     ("fe27", (16, 16, 8), (2, 2, 1), 4, True),
     ("rand27", (8, 8, 4), (3, 2, 1), 2, True),
+    # odd extents along UNSPLIT directions (create asks for even extents along split directions only): the shapes of the GPU
+    # cases of tests/test_gpu_dist.py.  A global grid of 4 planes has a single level, which is gathered whole; the cases
+    # with 8 and 16 planes below are the ones whose level 0 (and level 1) really sweeps on the rank grid.
+    ("rand27", (16, 9, 4), (2, 1, 1), 2, True),    # chain, odd unsplit y
+    ("rand27", (9, 16, 5), (1, 2, 1), 2, True),    # chain, odd unsplit x and z: level 0 distributed, (5, 8, 3) gathered
+    ("rand27", (16, 18, 4), (2, 1, 1), 2, True),   # chain, y turns odd on level 1 (18 -> 9)
+    ("rand27", (13, 11, 8), (1, 1, 2), 2),         # slab, odd x and y: levels (13, 11, 8), (7, 6, 4) distributed
+    ("rand27", (16, 9, 7), (2, 1, 1), 2),          # row-class, odd y and z: level 0 distributed, (8, 5, 4) gathered
+    ("poisson7", (16, 9, 7), (2, 1, 1), 2),        # 7-point level 0, odd y and z
+    ("rand27", (16, 9, 8), (2, 1, 1), 2, True),    # chain on level 0 with odd unsplit y; (8, 5, 4) gathered
+    ("rand27", (9, 16, 8), (1, 3, 1), 2, True),    # chain, odd unsplit x, a rank with neighbours on both y sides
+    # chain on levels 0 (32, 18, 16) and 1 (16, 9, 8): y turns odd on a distributed level; (8, 5, 4) gathered
+    ("rand27", (32, 18, 16), (2, 1, 1), 4, True),
 ]
 
 

@@ -128,8 +128,10 @@ def _spawn(world, args):
     assert not bad, f"rank processes failed: exit codes {bad}"
 
 
-@pytest.mark.parametrize("nd,n,pgrid", [(2, (24, 16), (2, 1)), (2, (16, 12), (2, 2)), (3, (12, 10, 8), (1, 1, 2)), (3, (8, 8, 8), (2, 2, 1))],
-                         ids=["2d-2x1", "2d-2x2", "3d-1x1x2", "3d-2x2x1"])
+# the last two: an odd extent along an unsplit direction (level 0 (24, 15) / (12, 9, 7) on the rank grid, the next level gathered)
+@pytest.mark.parametrize("nd,n,pgrid", [(2, (24, 16), (2, 1)), (2, (16, 12), (2, 2)), (3, (12, 10, 8), (1, 1, 2)), (3, (8, 8, 8), (2, 2, 1)),
+                                        (2, (24, 15), (2, 1)), (3, (12, 9, 7), (2, 1, 1))],
+                         ids=["2d-2x1", "2d-2x2", "3d-1x1x2", "3d-2x2x1", "2d-2x1-odd-ny", "3d-2x1x1-odd-ny-nz"])
 def test_bmg_interface_on_several_ranks(nd, n, pgrid, tmp_path, oracle):
     import problems as pb
     import test_bmg_capi as tb

@@ -25,7 +25,18 @@ def _free_port():
     return p
 
 
-def _worker(rank, world, port, n, pgrid, outdir, overlap_min, driver="python", agg=64, maxit=5):
+def _problem(pb, kind, gn):
+    """(operator, right-hand side) on the global grid gn = (nx, ny, nz): "rand27" a random 27-point operator, "poisson7" the
+    7-point Laplacian (nstencil = 4) -- the generators of tests/test_dist_cpu.py (which cannot be imported here: it brings torch)"""
+    g = (gn[2] + 2, gn[1] + 2, gn[0] + 2)
+    if kind == "rand27":
+        return pb.random_op(g, 14, 77), pb.uniform(g, 78, -1, 1) * pb.interior_mask(g)
+    if kind == "poisson7":
+        return pb.poisson3(*gn), pb.rhs3(*gn)
+    raise ValueError(kind)
+
+
+def _worker(rank, world, port, n, pgrid, outdir, overlap_min, driver="python", agg=64, maxit=5, kind="rand27"):
     for p in (HERE, ROOT, os.path.join(ROOT, "oracle")):
         if p not in sys.path:
             sys.path.insert(0, p)
@@ -45,9 +56,7 @@ def _worker(rank, world, port, n, pgrid, outdir, overlap_min, driver="python", a
         be = GpuBackend(comm, 0)
         topo = Topology(rank, world, pgrid)
         gn = tuple(n[d] * topo.p[d] for d in range(3))
-        g = (gn[2] + 2, gn[1] + 2, gn[0] + 2)
-        gso = pb.random_op(g, 14, 77)
-        gb = pb.uniform(g, 78, -1, 1) * pb.interior_mask(g)
+        gso, gb = _problem(pb, kind, gn)
         ci, cj, ck = topo.coord
         sl = (slice(ck * n[2], ck * n[2] + n[2] + 2), slice(cj * n[1], cj * n[1] + n[1] + 2),
               slice(ci * n[0], ci * n[0] + n[0] + 2))
@@ -97,13 +106,11 @@ IDS = ["2ranks-x", "4ranks-xy", "2ranks-z-overlap", "4ranks-yz-overlap", "4ranks
        "2ranks-z-64cubed-overlap", "4ranks-z-slabs-overlap", "2ranks-z-plane-fused", "2ranks-z-6M-unknowns"]
 
 
-def _check_against_single_domain(n, pgrid, tmp_path, oracle, maxit=5):
+def _check_against_single_domain(n, pgrid, tmp_path, oracle, maxit=5, kind="rand27"):
     import problems as pb
     world = pgrid[0] * pgrid[1] * pgrid[2]
     gn = tuple(n[d] * pgrid[d] for d in range(3))
-    g = (gn[2] + 2, gn[1] + 2, gn[0] + 2)
-    gso = pb.random_op(g, 14, 77)
-    gb = pb.uniform(g, 78, -1, 1) * pb.interior_mask(g)
+    gso, gb = _problem(pb, kind, gn)
     ml = oracle.ml_create(gso)
     x = np.zeros_like(gb)
     want = ml.solve(gb, x, maxiter=maxit)
@@ -170,6 +177,76 @@ def test_native_driver_boundary_first_chain_equals_single_domain(n, pgrid, tmp_p
     _spawn(_worker, world, (_free_port(), n, pgrid, str(tmp_path), 96, "native", 4 if deep else 64, maxit))
     assert int(open(tmp_path / "chain_levels.txt").read()) == (deep or 1)
     _check_against_single_domain(n, pgrid, tmp_path, oracle, maxit)
+
+
+# Odd extents along UNSPLIT directions.  create insists on even extents only along split directions (on every distributed
+# level below the gathered one); an unsplit direction may be odd on level 0 or turn odd further down (18 -> 9).  Coarsening
+# per level: n / 2 along a split direction, (n - 1) / 2 + 1 along an unsplit one.  One case per sweep path of smooth()
+# (dist3.cpp), each with the number of chain levels it must report: the masked launch of the chain takes even nx and ny
+# only (cedar_amd_relax3_masked_ok), so a level with an odd unsplit nx or ny must stay on the reference-order row-class
+# passes -- chain_levels 0 -- while an odd nz does not keep a level off the chain.
+#   (id, n, rank grid, overlap_min, agglomerate_below, environment, operator, chain levels)
+FRUN2 = {"CEDAR_AMD_FRUN": "2"}  # runs of 2 rows: the partial-sum sweep (hence the chain) from 8 rows on, as in CHAIN_CASES
+NOCHAIN = {"CEDAR_AMD_DIST_CHAIN": "0"}
+ODD_CASES = [
+    # -- chain candidates: x / y split, both extents >= 8, partial-sum sweep on offer
+    # level 0 (16, 9, 8), level 1 (8, 5, 4) gathered
+    ("chain-x-odd-ny", (16, 9, 8), (2, 1, 1), 96, 64, FRUN2, "rand27", 0),
+    # level 0 (16, 17, 8), level 1 (8, 9, 4) gathered
+    ("chain-xz-odd-ny", (16, 17, 8), (2, 1, 2), 96, 64, FRUN2, "rand27", 0),
+    # level 0 (9, 16, 8), level 1 (5, 8, 4) gathered
+    ("chain-y-odd-nx", (9, 16, 8), (1, 2, 1), 96, 64, FRUN2, "rand27", 0),
+    # the same box on three ranks: the middle one has a neighbour on both y sides
+    ("chain-y3-odd-nx", (9, 16, 8), (1, 3, 1), 96, 64, FRUN2, "rand27", 0),
+    # level 0 (32, 18, 16) even: stays on the chain; level 1 (16, 9, 8) odd: row-class; level 2 (8, 5, 4) gathered
+    ("chain-x-odd-from-level-1", (32, 18, 16), (2, 1, 1), 96, 4, FRUN2, "rand27", 1),
+    # default run lengths, 129 rows (the driver offers the partial-sum sweep from 128 rows on): level 0 (16, 129, 16),
+    # level 1 (8, 65, 8) gathered
+    ("chain-x-129-rows-default-runs", (16, 129, 16), (2, 1, 1), 96, 64, {}, "rand27", 0),
+    # rows of 257 points (the 256-lane kernels, last lane half empty): level 0 (257, 16, 16), level 1 (129, 8, 8) gathered
+    # (16 planes: the gathered hierarchy gets a second level and its direct solve a band of 520 instead of 2064)
+    ("chain-y-257-point-rows", (257, 16, 16), (1, 2, 1), 96, 64, FRUN2, "rand27", 0),
+    # odd nz with an x / y split: 4 planes of one k-parity, 3 of the other; nx and ny even, so the level takes the chain.
+    # level 0 (16, 16, 7), level 1 (8, 8, 4) gathered
+    ("chain-xy-odd-nz", (16, 16, 7), (2, 2, 1), 96, 64, FRUN2, "rand27", 1),
+    # -- slab path (z split only), odd nx and ny
+    # level 0 (13, 11, 8), level 1 (7, 6, 4) gathered
+    ("slab-odd-nx-ny", (13, 11, 8), (1, 1, 2), 96, 64, {}, "rand27", 0),
+    # 321 rows: plane-fused kernel and partial sums on level 0 (13, 321, 8); level 1 (7, 161, 4) gathered
+    ("slab-321-rows-plane-fused", (13, 321, 8), (1, 1, 2), 96, 64, {}, "rand27", 0),
+    # overlap_min = 4: shell planes / interior planes around the halo on the side stream; level 0 (11, 13, 8), level 1 (6, 7, 4)
+    ("slab-odd-nx-ny-overlap", (11, 13, 8), (1, 1, 2), 4, 64, {}, "rand27", 0),
+    # -- row-class passes asked for outright
+    # x split: relax3_fixup on the column next to the neighbour; level 0 (16, 9, 7), level 1 (8, 5, 4) gathered
+    ("rowclass-x-odd-ny-nz", (16, 9, 7), (2, 1, 1), 96, 64, NOCHAIN, "rand27", 0),
+    # x and z split, overlap_min = 4: interior rows under the y/z halo; level 0 (16, 9, 8), level 1 (8, 5, 4) gathered
+    ("rowclass-xz-odd-ny-overlap", (16, 9, 8), (2, 1, 2), 4, 64, NOCHAIN, "rand27", 0),
+    # -- 7-point operator on level 0 (two-colour sweep): level 0 (16, 9, 7), level 1 (8, 5, 4) gathered
+    ("7pt-x-odd-ny-nz", (16, 9, 7), (2, 1, 1), 96, 64, {}, "poisson7", 0),
+]
+
+
+@pytest.mark.parametrize("name,n,pgrid,overlap_min,agg,env,kind,chain_levels", ODD_CASES, ids=[c[0] for c in ODD_CASES])
+def test_native_driver_odd_unsplit_extents_equal_single_domain(name, n, pgrid, overlap_min, agg, env, kind, chain_levels,
+                                                               tmp_path, oracle, monkeypatch, capfd):
+    """cedar_amd_dist3_* on boxes with an odd extent along an unsplit direction, every sweep path of smooth(): the
+    single-domain history and solution, to the tolerances of the even cases.  Each case also pins the path: the number of
+    chain levels the driver reports, and a rank that printed a library error (a refused launch among them) fails the case
+    even where the numbers agree."""
+    for k in ("CEDAR_AMD_FRUN", "CEDAR_AMD_DIST_CHAIN"):
+        monkeypatch.delenv(k, raising=False)
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    for d in range(3):  # what create enforces on level 0; the comments above carry the levels below
+        assert pgrid[d] == 1 or n[d] % 2 == 0
+    world = pgrid[0] * pgrid[1] * pgrid[2]
+    assert world <= 6
+    capfd.readouterr()
+    _spawn(_worker, world, (_free_port(), n, pgrid, str(tmp_path), overlap_min, "native", agg, 5, kind))
+    err = capfd.readouterr().err
+    assert "refused" not in err and "[cedar_amd]" not in err and "cedar_amd_dist3" not in err, err
+    assert int(open(tmp_path / "chain_levels.txt").read()) == chain_levels
+    _check_against_single_domain(n, pgrid, tmp_path, oracle, 5, kind)
 
 
 # overlap_min = 4: the y/z halo of a row pass travels on a side HIP stream under the interior rows of

@@ -97,6 +97,14 @@ CASES = [
     ("aniso9", (32, 32), (2, 2), "line-xy", 4),
     ("rand9", (128, 128), (2, 2), "line-xy", 64),
     ("aniso9", (64, 32), (4, 1), "line-x", 8),      # x lines cut by four ranks: carries composed over three segments
+    # odd extents along the unsplit direction (create asks for even extents along split directions only, on every level below
+    # the gathered one; coarsening n / 2 along a split direction, (n - 1) / 2 + 1 along an unsplit one)
+    ("rand9", (32, 17), (2, 1), "point", 4),        # levels (32, 17), (16, 9), (8, 5) distributed, (4, 3) gathered
+    ("poisson5", (17, 32), (1, 2), "point", 4),     # levels (17, 32), (9, 16), (5, 8) distributed, (3, 4) gathered
+    ("stretch5", (64, 17), (2, 1), "line-x", 8),    # x lines cut in two, 17 of them: levels (64, 17), (32, 9), then (16, 5) gathered
+    ("stretch5", (17, 64), (1, 2), "line-y", 8),    # y lines cut in two, 17 of them: levels (17, 64), (9, 32), then (5, 16) gathered
+    ("aniso9", (32, 17), (2, 1), "line-xy", 4),     # x lines cut, y lines whole with 17 points: levels as for "point"
+    ("aniso9", (17, 32), (1, 2), "line-xy", 4),     # y lines cut, x lines whole with 17 points
 ]
 
 
@@ -122,10 +130,14 @@ def _check(case, tmp_path, oracle):
 
 
 @pytest.mark.parametrize("case", CASES, ids=lambda c: f"{c[0]}-{'x'.join(map(str, c[1]))}-p{'x'.join(map(str, c[2]))}-{c[3]}")
-def test_2d_ranks_on_one_gpu_equal_single_domain(case, tmp_path, oracle):
+def test_2d_ranks_on_one_gpu_equal_single_domain(case, tmp_path, oracle, capfd):
     kind, n, pgrid, relax, agg = case
     world = pgrid[0] * pgrid[1]
+    capfd.readouterr()
     _spawn(_worker, world, (_free_port(), case, str(tmp_path)))
+    if n[0] % 2 or n[1] % 2:  # no rank printed a library error
+        err = capfd.readouterr().err
+        assert "[cedar_amd]" not in err, err
     _check(case, tmp_path, oracle)
 
 

@@ -141,7 +141,10 @@ def test_partial_sum_relax_matches_reference_order_to_rounding(K, oracle, monkey
 
 @pytest.mark.parametrize("sides", [(1, 0, 0, 0), (0, 1, 0, 0), (0, 0, 1, 0), (0, 0, 0, 1), (1, 1, 1, 1), (1, 0, 0, 1)], ids=str)
 @pytest.mark.parametrize("shape,strip", [((16, 24, 6), True), ((8, 16, 5), False), ((130, 20, 4), True), ((512, 16, 4), True),
-                                         ((512, 24, 3), False)], ids=str)
+                                         ((512, 24, 3), False),
+                                         # odd nz on the box of the distributed case "chain-xy-odd-nz" (4 planes of one
+                                         # k-parity, 3 of the other): the masked launch admits it
+                                         ((16, 16, 7), True)], ids=str)
 def test_boundary_first_pieces_reorder_the_sweep_without_changing_it(oracle, monkeypatch, shape, strip, sides):
     """cedar_amd_relax3_rows / _cols / _cols_strip / _planes_masked (the pieces of the distributed sweep on rank grids with
     an x / y split, dist3.cpp chain_parity) on ONE box without neighbours: the columns and rows that a neighbour on the
@@ -173,6 +176,8 @@ def test_boundary_first_pieces_reorder_the_sweep_without_changing_it(oracle, mon
     lib.cedar_amd_relax3_strip_doubles.argtypes = [U, U]
     lib.cedar_amd_relax3_strip_build.argtypes = [VP, VP, U, U, U, C.c_int, VP]
     assert lib.cedar_amd_relax3_prepare(so.ptr, sor.ptr, II, JJ, KK) & 2
+    lib.cedar_amd_relax3_masked_ok.argtypes = [VP, U, U, U]
+    assert lib.cedar_amd_relax3_masked_ok(so.ptr, II, JJ, KK) == 1  # the predicate the distributed driver decides with
     strips = [None, None]
     if strip:
         for side in (0, 1):
@@ -237,6 +242,58 @@ def test_boundary_first_pieces_reorder_the_sweep_without_changing_it(oracle, mon
                 got = q.numpy()
                 scale = np.max(np.abs(want))
                 assert np.max(np.abs(got - want)) <= 2e-14 * (sweep + 1) * scale, (shape, sides, ud, sweep, np.max(np.abs(got - want)) / scale)
+    finally:
+        lib.cedar_amd_relax3_release(so.ptr)
+
+
+# odd nx with neighbours in y only, odd ny with neighbours in x only (the far side of an odd extent never carries a mask in
+# the distributed driver: the direction is unsplit), both odd, rows of 257 points, 129 rows; the last case is an even box
+# whose operator was never registered
+@pytest.mark.parametrize("shape,sides,register", [
+    ((9, 16, 6), (0, 0, 1, 0), True), ((9, 16, 6), (0, 0, 1, 1), True), ((9, 16, 5), (0, 0, 0, 1), True),
+    ((16, 9, 6), (1, 0, 0, 0), True), ((16, 9, 6), (1, 1, 0, 0), True), ((16, 9, 7), (0, 1, 0, 0), True),
+    ((257, 16, 4), (0, 0, 1, 1), True), ((16, 129, 4), (1, 1, 0, 0), True), ((13, 11, 8), (0, 0, 0, 0), True),
+    ((16, 16, 6), (1, 1, 1, 1), False)], ids=str)
+def test_masked_launch_refuses_odd_rows_and_columns_and_says_so_beforehand(oracle, monkeypatch, shape, sides, register):
+    """cedar_amd_relax3_planes_masked takes even nx and ny only (its column masks name lanes of full pairs).  The
+    distributed driver keeps levels with an odd unsplit nx or ny off the boundary-first chain by asking
+    cedar_amd_relax3_masked_ok, the predicate the launch itself applies.  On every shape the launch does not take: the
+    predicate says 0 for the registered operator and for the shape alone, the launch returns 0, and q keeps every bit --
+    a refusal never leaves a level partly relaxed.  The partial-sum scratch IS registered on the odd shapes (runs of 2
+    rows), so the refusal is the parity's, not a missing registration's; the unregistered even box is refused for that
+    reason alone (its shape passes)."""
+    import ctypes as C
+    from cedar_amd import capi
+    lib = capi.lib
+    monkeypatch.setenv("CEDAR_AMD_FRUN", "2")
+    nx, ny, nz = shape
+    g = (nz + 2, ny + 2, nx + 2)
+    II, JJ, KK = nx + 2, ny + 2, nz + 2
+    so_h = pb.random_op(g, 14, 91, zero_ghost=False)
+    qf_h, q0 = pb.uniform(g, 92, -1, 1), pb.uniform(g, 93, -1, 1)
+    sor_h = np.zeros((2,) + g)
+    oracle.setup_recip3(so_h, sor_h)
+    so, sor, qf, q = (capi.DeviceArray.from_numpy(a) for a in (so_h, sor_h, qf_h, q0))
+    VP, U = C.c_void_p, C.c_uint
+    lib.cedar_amd_relax3_prepare.argtypes = [VP, VP, U, U, U]
+    lib.cedar_amd_relax3_release.argtypes = [VP]
+    lib.cedar_amd_relax3_masked_ok.argtypes = [VP, U, U, U]
+    lib.cedar_amd_relax3_planes_masked.argtypes = [VP, VP, VP, VP, U, U, U, C.c_int, C.c_int, U, U, C.POINTER(C.c_int)]
+    odd = bool(nx & 1 or ny & 1)
+    assert odd == register
+    try:
+        if register:
+            assert lib.cedar_amd_relax3_prepare(so.ptr, sor.ptr, II, JJ, KK) & 2
+        assert lib.cedar_amd_relax3_masked_ok(None, II, JJ, KK) == (0 if odd else 1)
+        assert lib.cedar_amd_relax3_masked_ok(so.ptr, II, JJ, KK) == 0
+        mF = (0x0f if sides[0] else 0) | (0xf0 if sides[1] else 0)
+        mS = (0x03 if sides[0] else 0) | (0xc0 if sides[1] else 0)
+        skip = (C.c_int * 3)(1 if sides[2] else -1, ny - 1 if sides[3] else -1, ny if sides[3] else -1)
+        for up in (0, 1):
+            for kb in (0, 1):
+                assert lib.cedar_amd_relax3_planes_masked(so.ptr, qf.ptr, q.ptr, sor.ptr, II, JJ, KK, kb, up, mF, mS, skip) == 0
+        capi.sync()
+        assert np.array_equal(q.numpy(), q0)
     finally:
         lib.cedar_amd_relax3_release(so.ptr)
 
