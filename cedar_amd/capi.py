@@ -351,6 +351,32 @@ class Kernels:
                                     int(first), _p(sc), _p(partial)) != 0:
             raise RuntimeError("cedar_amd_pcg_update refused")
 
+    # the same two passes on a batch: vectors of shape (items,) + grid, item-major, sc of shape (items, 8); nrhs: work on
+    # the first nrhs items only (default: all); active: bit mask of the items that take part (default: all nrhs)
+    @staticmethod
+    def _batch(v, sc, nrhs, active):
+        n = int(v.shape[0] if nrhs is None else nrhs)
+        assert sc.size >= 8 * n and v.shape[0] >= n
+        return n, u((1 << n) - 1 if active is None else int(active))
+
+    def pcg_direction_many(self, so, z, p, pn, w, first, sc, nrhs=None, active=None):
+        """per item m: pn = z + beta_m p (first: z), w = A pn, sigma = pn.w -> sc[m]"""
+        assert tuple(so.shape[1:]) == tuple(z.shape[1:]) and all(a is None or a.shape == z.shape for a in (p, pn, w))
+        n, act = self._batch(z, sc, nrhs, active)
+        grid = z.shape[1:]
+        if lib.cedar_amd_pcg_direction_many(n, act, _p(so), _p(z), _p(p), _p(pn), _p(w), u(grid[-1]), u(grid[-2]),
+                                            u(grid[0] if len(grid) == 3 else 1), so.shape[0], int(first), _p(sc)) != 0:
+            raise RuntimeError("cedar_amd_pcg_direction_many refused")
+
+    def pcg_update_many(self, zmode, move, x, r, p, w, z, diag, first, sc, nrhs=None, active=None):
+        """per item m: x += alpha_m p, r -= alpha_m w (move), r.r and r.z by zmode -> sc[m]; diag is shared"""
+        assert all(a is None or a.shape == r.shape for a in (x, p, w, z)) and (diag is None or diag.shape == r.shape[1:])
+        n, act = self._batch(r, sc, nrhs, active)
+        grid = r.shape[1:]
+        if lib.cedar_amd_pcg_update_many(n, act, int(zmode), int(move), _p(x), _p(r), _p(p), _p(w), _p(z), _p(diag),
+                                         u(grid[-1]), u(grid[-2]), u(grid[0] if len(grid) == 3 else 1), int(first), _p(sc)) != 0:
+            raise RuntimeError("cedar_amd_pcg_update_many refused")
+
     def pcg_rank_scalars(self, which, zmode, gathered, world, stride, first, sc):
         """which 0: alpha from the ranks' sigma; 1: rho / beta from their r.r (and r.z); summed in rank order"""
         assert sc.size == 8 and gathered.size >= world * stride
@@ -441,6 +467,9 @@ PCG_PRECON = {"none": 1, "diag": 2, "mg": 3}
 lib.cedar_amd_solver_pcg.restype = C.c_int
 lib.cedar_amd_solver_pcg.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(PcgSettings), C.c_void_p]
 lib.cedar_amd_solver_precondition.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+lib.cedar_amd_solver_pcg_many.restype = C.c_int
+lib.cedar_amd_solver_pcg_many.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(PcgSettings), C.c_void_p,
+                                          C.POINTER(C.c_int)]
 
 
 class Solver:
@@ -546,6 +575,24 @@ class Solver:
         if n < 0:
             raise RuntimeError("cedar_amd_solver_pcg refused the settings (see the printed reason)")
         return hist[: n + 1]
+
+    def pcg_many(self, b, x, max_iter=50, tol=1e-8, stop="rel_l2", precon="mg", nmg_cycles=1, hist=None):
+        """pcg for the items of b, x of shape (nrhs,) + grid in lockstep (cedar_amd_solver_pcg_many): an item that has
+        stopped is left alone, so x[m] and its history are those of pcg on item m.  Returns (hist_rows, iters): row m cut
+        to iters[m] + 1 entries.  hist: optional (nrhs, max_iter + 1) array the library writes into.  RuntimeError when
+        the library refuses (x and hist untouched)."""
+        nrhs = self._nrhs(x, b)
+        ps = PcgSettings(int(max_iter), float(tol), PCG_STOP[stop], PCG_PRECON[precon], int(nmg_cycles))
+        ld = max(int(max_iter), 0) + 1
+        if hist is None:
+            hist = np.zeros((nrhs, ld))
+        assert hist.shape == (nrhs, ld) and hist.dtype == np.float64 and hist.flags["C_CONTIGUOUS"]
+        iters = np.zeros(nrhs, dtype=np.int32)
+        n = lib.cedar_amd_solver_pcg_many(self.h, nrhs, _vp(b), _vp(x), C.byref(ps), hist.ctypes.data,
+                                          iters.ctypes.data_as(C.POINTER(C.c_int)))
+        if n < 0:
+            raise RuntimeError("cedar_amd_solver_pcg_many refused (see the printed reason)")
+        return [hist[m, : int(iters[m]) + 1] for m in range(nrhs)], [int(v) for v in iters]
 
     def precondition(self, z, r):
         """z = M^-1 r: one cycle from z = 0 (cedar_amd_solver_precondition)"""

@@ -697,6 +697,47 @@ int cedar_amd_pcg_update(int zmode, int move, real_t *x, real_t *r, const real_t
 	return 0;
 }
 
+// the same two passes on nrhs items (krylov.hip *_many); every item's slab NaN-filled
+int cedar_amd_pcg_direction_many(int nrhs, unsigned active, const real_t *so, const real_t *z, const real_t *p, real_t *pn,
+                                 real_t *w, len_t ii, len_t jj, len_t kk, int nstncl, int first, real_t *sc)
+{
+	const char *who = "cedar_amd_pcg_direction_many";
+	if (nrhs < 1 || nrhs > CEDAR_AMD_MAX_RHS) return pcg_refuse(who, "nrhs must be 1 .. 32"), -1;
+	if (pcg_shape_refused(ii, jj, kk, who)) return -1;
+	const int nd = kk == 1 ? 2 : 3;
+	if (nd == 2 ? (nstncl != 3 && nstncl != 5) : (nstncl != 4 && nstncl != 14)) return pcg_refuse(who, "nstncl must be 3|5 (2D), 4|14 (3D)"), -1;
+	if (!so || !z || !pn || !w || !sc || (!first && !p)) return pcg_refuse(who, "a required array is NULL"), -1;
+	const size_t P = (size_t)ii * jj * kk, N = P * nrhs;
+	NanSlab slab(pcg_slab_doubles(nd, nstncl, (int)ii, (int)jj, (int)kk) * nrhs);
+	Staged sso(so, P * nstncl, true, false), sz(z, N, true, false), sp(first ? nullptr : p, N, true, false),
+	    spn(pn, N, true, true), sw(w, N, true, true), ssc(sc, (size_t)PCG_NSC * nrhs, true, true);
+	const Op3 view = nstncl == 14 ? relax3_op_view(sso.get(), (int)ii, (int)jj, (int)kk) : Op3{};
+	pcg_direction_many(sso.get(), nstncl == 14 ? &view : nullptr, sz.get(), sp.get(), spn.get(), sw.get(), nd, nstncl, (int)ii,
+	                   (int)jj, (int)kk, first != 0, slab.dev, ssc.get(), current_stream(), Batch{nrhs, P}, active);
+	return 0;
+}
+
+int cedar_amd_pcg_update_many(int nrhs, unsigned active, int zmode, int move, real_t *x, real_t *r, const real_t *p,
+                              const real_t *w, real_t *z, const real_t *diag, len_t ii, len_t jj, len_t kk, int first,
+                              real_t *sc)
+{
+	const char *who = "cedar_amd_pcg_update_many";
+	if (nrhs < 1 || nrhs > CEDAR_AMD_MAX_RHS) return pcg_refuse(who, "nrhs must be 1 .. 32"), -1;
+	if (pcg_shape_refused(ii, jj, kk, who)) return -1;
+	if (zmode < 0 || zmode > 3) return pcg_refuse(who, "zmode must be 0..3"), -1;
+	if (!r || !sc || (move && (!x || !p || !w)) || ((zmode == 1 || zmode == 2) && !z) || (zmode == 1 && !diag))
+		return pcg_refuse(who, "a required array is NULL"), -1;
+	const size_t P = (size_t)ii * jj * kk, N = P * nrhs;
+	NanSlab slab(pcg_slab_doubles(kk == 1 ? 2 : 3, kk == 1 ? 3 : 4, (int)ii, (int)jj, (int)kk) * nrhs);
+	const bool mv = move != 0;
+	Staged sx(mv ? x : nullptr, N, true, true), sr(r, N, true, mv), sp(mv ? p : nullptr, N, true, false),
+	    sw(mv ? w : nullptr, N, true, false), sz(zmode == 1 || zmode == 2 ? z : nullptr, N, true, zmode == 1),
+	    sd(zmode == 1 ? diag : nullptr, P, true, false), ssc(sc, (size_t)PCG_NSC * nrhs, true, true);
+	pcg_update_many(zmode, mv, sx.get(), sr.get(), sp.get(), sw.get(), sz.get(), sd.get(), (int)ii, (int)jj, (int)kk,
+	                first != 0, slab.dev, ssc.get(), current_stream(), Batch{nrhs, P}, active);
+	return 0;
+}
+
 int cedar_amd_pcg_rank_scalars(int which, int zmode, const real_t *gathered, int world, int stride, int first, real_t *sc)
 {
 	const char *who = "cedar_amd_pcg_rank_scalars";

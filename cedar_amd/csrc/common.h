@@ -258,7 +258,16 @@ void pcg_direction(const real_t *so, const Op3 *op27, const real_t *z, const rea
 void pcg_update(int zmode, bool move, real_t *x, real_t *r, const real_t *p, const real_t *w, real_t *z,
                 const real_t *diag, int II, int JJ, int KK, bool first, real_t *slab, real_t *sc, hipStream_t st,
                 real_t *partial = nullptr);
-// On a rank grid (dist_common.h dist_pcg) the two launchers above get `partial`: instead of the one-rank second stage they
+// The two passes on a batch of right-hand sides (cedar_amd_solver_pcg_many): vectors item-major with bt.stride, item m's
+// scalars at sc + m * PCG_NSC, slab of bt.n * pcg_slab_doubles(..) doubles.  Bit m of `active` clear: item m is skipped
+// (vectors, slab, scalars untouched).  Item m's vectors and scalars have the bits of the single pass on item m alone.
+void pcg_direction_many(const real_t *so, const Op3 *op27, const real_t *z, const real_t *p, real_t *pn, real_t *w, int nd,
+                        int nst, int II, int JJ, int KK, bool first, real_t *slab, real_t *sc, hipStream_t st, Batch bt,
+                        unsigned active);
+void pcg_update_many(int zmode, bool move, real_t *x, real_t *r, const real_t *p, const real_t *w, real_t *z,
+                     const real_t *diag, int II, int JJ, int KK, bool first, real_t *slab, real_t *sc, hipStream_t st,
+                     Batch bt, unsigned active);
+// On a rank grid (dist_common.h dist_pcg) the two single-vector launchers above get `partial`: instead of the one-rank second stage they
 // leave this rank's slab sums there (direction: sigma; update: r.r, and r.z unless zmode 0; zmode 3: nothing -- r.r is
 // gathered with r.z after the preconditioner).  After the all-gather of `stride` doubles per rank, the _ranks kernels
 // sum the partials in rank order and set the scalars as the one-rank stages do (world = 1: the same values bit for bit).

@@ -81,10 +81,9 @@ __device__ __forceinline__ real_t mv27(real_t d, const C27 &c, const real_t (&qq
 // ---------------------------------------------------------------- p' = z + beta p, w = A p', partial p'.w
 // 2D: one lane per point, one workgroup per 256-point segment of a row (residual2_kernel's layout)
 template <bool NINE, bool FIRST>
-__global__ __launch_bounds__(256) void pcg_dir2(const real_t *__restrict__ so, const real_t *__restrict__ z,
-                                                const real_t *__restrict__ p, real_t *__restrict__ pn,
-                                                real_t *__restrict__ w, const real_t *__restrict__ sc, int II, int JJ,
-                                                real_t *__restrict__ part)
+__device__ __forceinline__ void dir2_segment(const real_t *__restrict__ so, const real_t *__restrict__ z,
+                                             const real_t *__restrict__ p, real_t *__restrict__ pn, real_t *__restrict__ w,
+                                             const real_t *__restrict__ sc, int II, int JJ, real_t *__restrict__ part)
 {
 	__shared__ real_t lds[4];
 	const int i = blockIdx.x * blockDim.x + threadIdx.x + 1;
@@ -113,6 +112,15 @@ __global__ __launch_bounds__(256) void pcg_dir2(const real_t *__restrict__ so, c
 	}
 	const real_t t = block_sum_k<256>(acc, lds);
 	if (threadIdx.x == 0) part[blockIdx.x + (size_t)gridDim.x * blockIdx.y] = t;
+}
+
+template <bool NINE, bool FIRST>
+__global__ __launch_bounds__(256) void pcg_dir2(const real_t *__restrict__ so, const real_t *__restrict__ z,
+                                                const real_t *__restrict__ p, real_t *__restrict__ pn,
+                                                real_t *__restrict__ w, const real_t *__restrict__ sc, int II, int JJ,
+                                                real_t *__restrict__ part)
+{
+	dir2_segment<NINE, FIRST>(so, z, p, pn, w, sc, II, JJ, part);
 }
 
 // 3D 7-point: one workgroup per grid row (residual3_kernel's layout); partial of logical row L at part[L]
@@ -381,6 +389,276 @@ __global__ __launch_bounds__(256) void pcg_shell(const real_t *__restrict__ z, c
 
 constexpr unsigned UPD_NB = 2048;
 
+// ================================================================ the same passes on a batch of right-hand sides
+// (solver.cpp cedar_amd_solver_pcg_many): nrhs independent CG recurrences on ONE operator.  Vectors are item-major with
+// the stride of common.h Batch; item m has its own scalar block sc + m * PCG_NSC and its own slab part + m * n (n = the
+// single pass' partial count).  Each pass keeps the single pass' geometry per item -- same workgroup width, same tile
+// walk, same row dealing, block_sum_k per item, slab_sum per item -- and the build has no FMA contraction, so every
+// vector AND every scalar of item m has the bits the single-vector pass gives on item m alone.  What a batch saves is
+// the operator: a workgroup task fetches its coefficients once and applies them to every item from registers.
+// `active`: bit m clear = item m is skipped by the vector pass and by its second stage (nothing of it is read or
+// written); a kernel argument, so that freezing an item costs no copy.
+//
+// Algorithmic bytes per interior point for n items:
+//   pcg_dir27_many  operator once 112 (interleaved copy 120) + n x (z, p read 16 + p', w written 16)  = 120 + 32 n
+//   pcg_dir7_many   4 x 8 + 32 n;   pcg_dir2_many  as pcg_dir2 per item (the item comes from the launch grid)
+//   pcg_upd_many    48 n; precon = diag: 8 + 56 n
+constexpr int ITEM_CHUNK = 8; // items of one workgroup of pcg_dir7_many / pcg_upd_many (their per-lane sums live in LDS)
+
+__device__ __forceinline__ bool item_on(unsigned active, int m) { return (active >> m) & 1u; }
+
+// 2D: pcg_dir2 with the item in blockIdx.z (no operator reuse, as the 2D kernels of a batched cycle)
+template <bool NINE, bool FIRST>
+__global__ __launch_bounds__(256) void pcg_dir2_many(const real_t *__restrict__ so, const real_t *__restrict__ z,
+                                                     const real_t *__restrict__ p, real_t *__restrict__ pn,
+                                                     real_t *__restrict__ w, const real_t *__restrict__ sc, int II, int JJ,
+                                                     real_t *__restrict__ part, size_t stride, unsigned active)
+{
+	const int m = blockIdx.z;
+	if (!item_on(active, m)) return;
+	const size_t off = (size_t)m * stride;
+	dir2_segment<NINE, FIRST>(so, z + off, FIRST ? z : p + off, pn + off, w + off, sc + (size_t)m * PCG_NSC, II, JJ,
+	                          part + (size_t)m * gridDim.x * gridDim.y);
+}
+
+// 3D 7-point: pcg_dir7 with the seven operator entries a point reads in registers across the items m0 .. m0 + nitems-1
+// (m0 = ITEM_CHUNK * blockIdx.y).  A lane's sum runs over the trips of a row longer than the workgroup, per item: one
+// LDS column per lane (accl[item][lane], lane-private, so no barrier), summed per item exactly as pcg_dir7 sums acc.
+template <bool FIRST>
+__global__ __launch_bounds__(256) void pcg_dir7_many(const real_t *__restrict__ so, const real_t *__restrict__ z,
+                                                     const real_t *__restrict__ p, real_t *__restrict__ pn,
+                                                     real_t *__restrict__ w, const real_t *__restrict__ sc, int II, int JJ,
+                                                     int KK, unsigned nrows, real_t *__restrict__ part, int nrhs,
+                                                     size_t stride, unsigned active)
+{
+	__shared__ real_t lds[4];
+	__shared__ real_t accl[ITEM_CHUNK][256];
+	const unsigned L = xcd_remap(blockIdx.x, nrows);
+	if (L >= nrows) return; // grid padding of xcd_grid: no slab entry
+	const int m0 = ITEM_CHUNK * (int)blockIdx.y, nitems = min(ITEM_CHUNK, nrhs - m0);
+	const int j = (int)(L % (unsigned)(JJ - 2)) + 1, k = (int)(L / (unsigned)(JJ - 2)) + 1;
+	const size_t sj = II, sk = (size_t)II * JJ, PS = sk * KK;
+	for (int t = 0; t < nitems; t++) accl[t][threadIdx.x] = 0.0;
+	for (int i = threadIdx.x + 1; i <= II - 2; i += blockDim.x) {
+		const size_t x = (size_t)i + sj * (size_t)j + sk * (size_t)k;
+		const real_t cp = so[KP * PS + x], cw = so[KPW * PS + x], cn = so[KPS * PS + x + sj], ce = so[KPW * PS + x + 1];
+		const real_t cs = so[KPS * PS + x], cb = so[KB * PS + x], ct = so[KB * PS + x + sk];
+#pragma unroll 1
+		for (int t = 0; t < nitems; t++) {
+			const int m = m0 + t;
+			if (!item_on(active, m)) continue;
+			const size_t off = (size_t)m * stride;
+			const real_t *__restrict__ zm = z + off, *__restrict__ pm = FIRST ? zm : p + off;
+			const real_t beta = FIRST ? 0.0 : sc[(size_t)m * PCG_NSC + PCG_BETA];
+			auto P = [&](size_t y) -> real_t { return FIRST ? zm[y] : zm[y] + beta * pm[y]; };
+			const real_t pc = P(x);
+			real_t s = cp * pc;
+			s = s - cw * P(x - 1);
+			s = s - cn * P(x + sj);
+			s = s - ce * P(x + 1);
+			s = s - cs * P(x - sj);
+			s = s - cb * P(x - sk);
+			s = s - ct * P(x + sk);
+			pn[off + x] = pc;
+			w[off + x] = s;
+			accl[t][threadIdx.x] += pc * s;
+		}
+	}
+	for (int t = 0; t < nitems; t++) {
+		const int m = m0 + t;
+		if (!item_on(active, m)) continue; // uniform over the workgroup
+		const real_t v = block_sum_k<256>(accl[t][threadIdx.x], lds);
+		if (threadIdx.x == 0) part[(size_t)m * nrows + L] = v;
+	}
+}
+
+// 3D 27-point: pcg_dir27 for rows of one trip (at most 2 BS points; longer rows go through pcg_dir27 item by item, see
+// pcg_direction_many), so that a lane's sum of an item is one register and not a run-time indexed array.  The 52
+// coefficients and the diagonal pair stay in registers across the item loop; one window set is live at a time.
+template <int BS, bool FIRST>
+__global__ __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(2))) void pcg_dir27_many(
+    const Op3 A, const real_t *__restrict__ z, const real_t *__restrict__ p, real_t *__restrict__ pn, real_t *__restrict__ w,
+    const real_t *__restrict__ sc, int II, int JJ, int KK, unsigned nblk, TileShape ts, real_t *__restrict__ part, int nrhs,
+    size_t stride, unsigned active)
+{
+	__shared__ real_t lds[(BS + 63) / 64];
+	const unsigned L = xcd_remap(blockIdx.x, nblk);
+	if (L >= nblk) return; // grid padding: no slab entry
+	unsigned jr, kr;
+	const bool have = tile_rows(L, (unsigned)(JJ - 2), (unsigned)(KK - 2), ts, jr, kr);
+	const int q = threadIdx.x;
+	const bool mine = have && 2 * q + 1 <= II - 2;
+	const int ie = 2 * q + 1, io = 2 * q + 2;
+	const bool o_ok = io <= II - 2, two = io + 1 <= II - 1;
+	const size_t j = (size_t)jr + 1, k = (size_t)kr + 1;
+	const size_t sj = (size_t)II, sk = (size_t)II * JJ;
+	const size_t row = j * sj + k * sk, rowA = j * A.SJ + k * A.SK;
+	C27 ce, co;
+	real_t de = 0.0, dn = 0.0;
+	if (mine) {
+		load_coef27<false, false, false>(A, rowA, ie, io, two, ce, co);
+		co.pw = ce.pw_e; // both are the operator entry (KPW, io): one register pair less across the item loop
+		ldpair(A.so + rowA + ie, true, de, dn); // KP plane
+	}
+#pragma unroll 1
+	for (int m = 0; m < nrhs; m++) {
+		if (!item_on(active, m)) continue; // uniform over the workgroup
+		real_t acc = 0.0;
+		if (mine) {
+			const size_t off = (size_t)m * stride;
+			const real_t *__restrict__ zm = z + off;
+			real_t qe[3][3][3], qo[3][3][3];
+			if (FIRST) { // the 3x3 windows of z
+				real_t zfe, zfo;
+				load_vec27<0>(zm, zm, row, sj, sk, ie, io, two, qe, qo, zfe, zfo);
+			} else { // of z + beta p, row by row: pcg_dir27's expression per element
+				const real_t beta = sc[(size_t)m * PCG_NSC + PCG_BETA];
+				const real_t *__restrict__ pm = p + off;
+#pragma unroll
+				for (int dk = 0; dk < 3; dk++)
+#pragma unroll
+					for (int dj = 0; dj < 3; dj++) {
+						const size_t y = row + (ptrdiff_t)(dj - 1) * (ptrdiff_t)sj + (ptrdiff_t)(dk - 1) * (ptrdiff_t)sk;
+						real_t w0, w1, w2, w3, p0, p1, p2, p3;
+						ldpair(pm + y + ie - 1, true, p0, p1);
+						ldpair(pm + y + io, two, p2, p3);
+						ldpair(zm + y + ie - 1, true, w0, w1);
+						ldpair(zm + y + io, two, w2, w3);
+						qe[dk][dj][0] = w0 + beta * p0;
+						qe[dk][dj][1] = w1 + beta * p1;
+						qe[dk][dj][2] = w2 + beta * p2;
+						qo[dk][dj][0] = qe[dk][dj][1];
+						qo[dk][dj][1] = qe[dk][dj][2];
+						qo[dk][dj][2] = w3 + beta * p3;
+					}
+			}
+			const real_t we = mv27(de, ce, qe);
+			const real_t pe = qe[1][1][1];
+			acc += pe * we;
+			if (o_ok) {
+				const real_t wo = mv27(dn, co, qo);
+				const real_t po = qo[1][1][1];
+				acc += po * wo;
+				d2u v; v.x = we; v.y = wo;
+				*reinterpret_cast<d2u *>(w + off + row + ie) = v;
+				v.x = pe; v.y = po;
+				*reinterpret_cast<d2u *>(pn + off + row + ie) = v;
+			} else {
+				w[off + row + ie] = we;
+				pn[off + row + ie] = pe;
+			}
+		}
+		const real_t t = block_sum_k<BS>(acc, lds);
+		if (threadIdx.x == 0) part[(size_t)m * nblk + L] = t;
+	}
+}
+
+// pcg_upd on the items m0 .. m0 + nitems-1 (m0 = ITEM_CHUNK * blockIdx.y): the same UPD_NB workgroups and row dealing, the
+// item loop inside the pair loop so that diag (ZM 1) is read once per pair.  A lane's r.r / r.z of an item run over all
+// the rows dealt to the workgroup: LDS columns (lane-private), summed per item as pcg_upd sums rr and rz.  Item m's slab:
+// part[2 m gridDim.x + ..] (r.r), part[(2 m + 1) gridDim.x + ..] (r.z).
+template <int ZM, bool MOVE>
+__global__ __launch_bounds__(256) void pcg_upd_many(real_t *__restrict__ x, real_t *__restrict__ r,
+                                                    const real_t *__restrict__ p, const real_t *__restrict__ w,
+                                                    real_t *__restrict__ z, const real_t *__restrict__ diag,
+                                                    const real_t *__restrict__ sc, int II, int JJ, int KK,
+                                                    real_t *__restrict__ part, int nrhs, size_t stride, unsigned active)
+{
+	__shared__ real_t lds[4];
+	__shared__ real_t rrl[ITEM_CHUNK][256], rzl[(ZM == 1 || ZM == 2) ? ITEM_CHUNK : 1][256];
+	const int m0 = ITEM_CHUNK * (int)blockIdx.y, nitems = min(ITEM_CHUNK, nrhs - m0);
+	const int nj = JJ - 2, nk = KK == 1 ? 1 : KK - 2;
+	const size_t nrows = (size_t)nj * nk;
+	for (int t = 0; t < nitems; t++) {
+		rrl[t][threadIdx.x] = 0.0;
+		if (ZM == 1 || ZM == 2) rzl[t][threadIdx.x] = 0.0;
+	}
+	for (size_t tr = blockIdx.x; tr < nrows; tr += gridDim.x) {
+		const size_t j = tr % nj + 1, k = KK == 1 ? 0 : tr / nj + 1;
+		const size_t row = (size_t)II * (j + (size_t)JJ * k);
+		for (int q = threadIdx.x; 2 * q + 1 <= II - 2; q += blockDim.x) {
+			const size_t ip = row + 2 * q + 1;
+			const bool two = 2 * q + 2 <= II - 2;
+			real_t d0 = 0.0, d1 = 0.0;
+			if (ZM == 1) ldpair(diag + ip, two, d0, d1);
+#pragma unroll 1
+			for (int t = 0; t < nitems; t++) {
+				const int m = m0 + t;
+				if (!item_on(active, m)) continue;
+				const size_t ie = (size_t)m * stride + ip;
+				const real_t a = MOVE ? sc[(size_t)m * PCG_NSC + PCG_ALPHA] : 0.0;
+				const bool mv = MOVE && a != 0.0; // alpha = 0 (breakdown): x and r stay as they are
+				real_t rr = rrl[t][threadIdx.x], rz = (ZM == 1 || ZM == 2) ? rzl[t][threadIdx.x] : 0.0;
+				real_t r0, r1;
+				ldpair(r + ie, two, r0, r1);
+				if (mv) {
+					real_t x0, x1, p0, p1, w0, w1;
+					ldpair(x + ie, two, x0, x1);
+					ldpair(p + ie, two, p0, p1);
+					ldpair(w + ie, two, w0, w1);
+					x0 = x0 + a * p0; x1 = x1 + a * p1;
+					r0 = r0 - a * w0; r1 = r1 - a * w1;
+					if (two) {
+						d2u v; v.x = x0; v.y = x1; *reinterpret_cast<d2u *>(x + ie) = v;
+						v.x = r0; v.y = r1; *reinterpret_cast<d2u *>(r + ie) = v;
+					} else {
+						x[ie] = x0; r[ie] = r0;
+					}
+				}
+				rr += r0 * r0;
+				if (two) rr += r1 * r1;
+				if (ZM == 1) {
+					const real_t z0 = r0 / d0, z1 = two ? r1 / d1 : 0.0;
+					if (two) { d2u v; v.x = z0; v.y = z1; *reinterpret_cast<d2u *>(z + ie) = v; }
+					else z[ie] = z0;
+					rz += r0 * z0;
+					if (two) rz += r1 * z1;
+				} else if (ZM == 2) {
+					real_t z0, z1;
+					ldpair(z + ie, two, z0, z1);
+					rz += r0 * z0;
+					if (two) rz += r1 * z1;
+				}
+				rrl[t][threadIdx.x] = rr;
+				if (ZM == 1 || ZM == 2) rzl[t][threadIdx.x] = rz;
+			}
+		}
+	}
+	for (int t = 0; t < nitems; t++) {
+		const int m = m0 + t;
+		if (!item_on(active, m)) continue; // uniform over the workgroup
+		const real_t s0 = block_sum_k<256>(rrl[t][threadIdx.x], lds);
+		const real_t s1 = (ZM == 1 || ZM == 2) ? block_sum_k<256>(rzl[t][threadIdx.x], lds) : 0.0;
+		if (threadIdx.x == 0) {
+			part[(size_t)(2 * m) * gridDim.x + blockIdx.x] = s0;
+			part[(size_t)(2 * m + 1) * gridDim.x + blockIdx.x] = s1;
+		}
+	}
+}
+
+// second stages: workgroup m is pcg_alpha / pcg_rho on item m's slab (item stride `ld` doubles) and scalar block
+__global__ __launch_bounds__(RED_BS) void pcg_alpha_many(const real_t *__restrict__ part, unsigned n, size_t ld,
+                                                         real_t *__restrict__ sc, unsigned active)
+{
+	__shared__ real_t lds[RED_BS / 64];
+	const int m = blockIdx.x;
+	if (!item_on(active, m)) return;
+	const real_t sigma = slab_sum(part + (size_t)m * ld, n, lds);
+	if (threadIdx.x == 0) set_alpha(sigma, sc + (size_t)m * PCG_NSC);
+}
+
+__global__ __launch_bounds__(RED_BS) void pcg_rho_many(const real_t *__restrict__ part, unsigned n, size_t ld, int has_rz,
+                                                       int first, real_t *__restrict__ sc, unsigned active)
+{
+	__shared__ real_t lds[RED_BS / 64];
+	const int m = blockIdx.x;
+	if (!item_on(active, m)) return;
+	const real_t *__restrict__ pm = part + (size_t)m * ld;
+	const real_t rr = slab_sum(pm, n, lds);
+	const real_t rz = has_rz == 1 ? slab_sum(pm + n, n, lds) : rr;
+	if (threadIdx.x == 0) set_rho(rr, rz, has_rz, first, sc + (size_t)m * PCG_NSC);
+}
+
 } // namespace
 
 size_t pcg_slab_doubles(int nd, int nst, int II, int JJ, int KK)
@@ -445,6 +723,70 @@ void pcg_update(int zmode, bool move, real_t *x, real_t *r, const real_t *p, con
 	const int has_rz = zmode == 3 ? 0 : zmode == 0 ? 2 : 1; // 2: r.z = r.r
 	if (!partial) hipLaunchKernelGGL(pcg_rho, dim3(1), dim3(RED_BS), 0, st, slab, nb, has_rz, first ? 1 : 0, sc);
 	else if (zmode != 3) hipLaunchKernelGGL(pcg_partial, dim3(1), dim3(RED_BS), 0, st, slab, nb, has_rz == 1 ? 2 : 1, partial);
+}
+
+void pcg_direction_many(const real_t *so, const Op3 *op27, const real_t *z, const real_t *p, real_t *pn, real_t *w, int nd,
+                        int nst, int II, int JJ, int KK, bool first, real_t *slab, real_t *sc, hipStream_t st, Batch bt,
+                        unsigned active)
+{
+	const size_t ld = pcg_slab_doubles(nd, nst, II, JJ, KK); // item stride of the slab
+	const unsigned chunks = (unsigned)((bt.n + ITEM_CHUNK - 1) / ITEM_CHUNK);
+	unsigned n = 0;
+	if (nd == 2) {
+		dim3 grid((II - 2 + 255) / 256, JJ - 2, bt.n);
+		n = grid.x * grid.y;
+#define L2_(NINE, F) hipLaunchKernelGGL((pcg_dir2_many<NINE, F>), grid, dim3(256), 0, st, so, z, p, pn, w, sc, II, JJ, slab, bt.stride, active)
+		if (nst == 5) { if (first) L2_(true, true); else L2_(true, false); }
+		else { if (first) L2_(false, true); else L2_(false, false); }
+#undef L2_
+	} else if (nst == 4) {
+		n = (unsigned)(JJ - 2) * (unsigned)(KK - 2);
+		const int bs = II - 2 >= 256 ? 256 : (II - 2 > 64 ? 128 : 64);
+		const dim3 grid(xcd_grid(n), chunks);
+		if (first) hipLaunchKernelGGL(pcg_dir7_many<true>, grid, dim3(bs), 0, st, so, z, p, pn, w, sc, II, JJ, KK, n, slab, bt.n, bt.stride, active);
+		else hipLaunchKernelGGL(pcg_dir7_many<false>, grid, dim3(bs), 0, st, so, z, p, pn, w, sc, II, JJ, KK, n, slab, bt.n, bt.stride, active);
+	} else {
+		const int npairs = (II - 2 + 1) / 2;
+		if (npairs > 256) { // rows of more than one trip: the single-vector pass item by item (its second stage included)
+			for (int m = 0; m < bt.n; m++)
+				if ((active >> m) & 1u)
+					pcg_direction(so, op27, z + m * bt.stride, first ? nullptr : p + m * bt.stride, pn + m * bt.stride,
+					              w + m * bt.stride, nd, nst, II, JJ, KK, first, slab + m * ld, sc + (size_t)m * PCG_NSC, st);
+			return;
+		}
+		const Op3 A = op27 ? *op27 : op3_cedar(so, nullptr, II, JJ, KK);
+		const TileShape ts = tile_shape_resid();
+		n = tile_blocks((unsigned)(JJ - 2), (unsigned)(KK - 2), ts);
+#define L27_(BS, F) hipLaunchKernelGGL((pcg_dir27_many<BS, F>), dim3(xcd_grid(n)), dim3(BS), 0, st, A, z, p, pn, w, sc, II, JJ, KK, n, ts, slab, bt.n, bt.stride, active)
+		if (npairs <= 64) { if (first) L27_(64, true); else L27_(64, false); }
+		else if (npairs <= 128) { if (first) L27_(128, true); else L27_(128, false); }
+		else { if (first) L27_(256, true); else L27_(256, false); }
+#undef L27_
+	}
+	hipLaunchKernelGGL(pcg_alpha_many, dim3(bt.n), dim3(RED_BS), 0, st, slab, n, (size_t)n, sc, active);
+}
+
+void pcg_update_many(int zmode, bool move, real_t *x, real_t *r, const real_t *p, const real_t *w, real_t *z,
+                     const real_t *diag, int II, int JJ, int KK, bool first, real_t *slab, real_t *sc, hipStream_t st,
+                     Batch bt, unsigned active)
+{
+	const size_t nrows = (size_t)(JJ - 2) * (KK == 1 ? 1 : KK - 2);
+	const unsigned nb = (unsigned)std::min<size_t>(UPD_NB, nrows);
+	const dim3 grid(nb, (unsigned)((bt.n + ITEM_CHUNK - 1) / ITEM_CHUNK));
+#define LU_(ZM, MV) hipLaunchKernelGGL((pcg_upd_many<ZM, MV>), grid, dim3(256), 0, st, x, r, p, w, z, diag, sc, II, JJ, KK, slab, bt.n, bt.stride, active)
+	switch (zmode * 2 + (move ? 1 : 0)) {
+	case 0: LU_(0, false); break;
+	case 1: LU_(0, true); break;
+	case 2: LU_(1, false); break;
+	case 3: LU_(1, true); break;
+	case 4: LU_(2, false); break;
+	case 5: LU_(2, true); break;
+	case 6: LU_(3, false); break;
+	default: LU_(3, true); break;
+	}
+#undef LU_
+	const int has_rz = zmode == 3 ? 0 : zmode == 0 ? 2 : 1; // 2: r.z = r.r
+	hipLaunchKernelGGL(pcg_rho_many, dim3(bt.n), dim3(RED_BS), 0, st, slab, nb, (size_t)2 * nb, has_rz, first ? 1 : 0, sc, active);
 }
 
 void pcg_ranks_alpha(const real_t *gathered, int world, int stride, real_t *sc, hipStream_t st)

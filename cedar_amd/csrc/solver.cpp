@@ -14,6 +14,7 @@
 #include "common.h"
 #include "stage.h"
 #include "relax3_psum.h"
+#include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <utility>
@@ -117,6 +118,7 @@ struct cedar_amd_solver {
 	// the pair of directions (p is read at the stencil neighbours while p' is written), partial-sum slab, device scalars
 	real_t *kr = nullptr, *kz = nullptr, *kw = nullptr, *kp[2] = {nullptr, nullptr};
 	real_t *kslab = nullptr, *ksc = nullptr;
+	int kitems = 0; // items each of them holds: 1, or nb_alloc after the first cedar_amd_solver_pcg_many (item-major)
 };
 
 namespace {
@@ -1053,21 +1055,30 @@ static bool pcg_refused(const cedar_amd_solver *s, const cedar_amd_pcg_settings 
 	return true;
 }
 
-static void pcg_alloc(cedar_amd_solver *s)
+// the Krylov storage for `items` right-hand sides (item-major; the single-vector calls work on item 0's set).  Growing it
+// frees the smaller set first: a captured cycle on the old (z, r) pair is re-recorded by graph_prepare when they moved.
+static void pcg_alloc(cedar_amd_solver *s, int items = 1)
 {
-	if (s->kr) return;
+	if (s->kr && s->kitems >= items) return;
+	if (s->kr) {
+		CEDAR_HIP_CHECK(hipStreamSynchronize(current_stream()));
+		(void)hipFree(s->kr); (void)hipFree(s->kz); (void)hipFree(s->kw); (void)hipFree(s->kp[0]); (void)hipFree(s->kp[1]);
+		(void)hipFree(s->kslab); (void)hipFree(s->ksc);
+	}
 	const Level &L = s->lv[0];
+	const size_t n = L.npts * (size_t)items;
 	// zero-filled: ghost entries stay zero (the kernels write interiors only)
-	s->kr = dalloc(L.npts); s->kz = dalloc(L.npts); s->kw = dalloc(L.npts);
-	s->kp[0] = dalloc(L.npts); s->kp[1] = dalloc(L.npts);
-	s->kslab = dalloc_raw(pcg_slab_doubles(s->nd, L.nst, L.II, L.JJ, L.KK));
-	s->ksc = dalloc(PCG_NSC);
+	s->kr = dalloc(n); s->kz = dalloc(n); s->kw = dalloc(n);
+	s->kp[0] = dalloc(n); s->kp[1] = dalloc(n);
+	s->kslab = dalloc_raw(pcg_slab_doubles(s->nd, L.nst, L.II, L.JJ, L.KK) * (size_t)items);
+	s->ksc = dalloc((size_t)PCG_NSC * items);
+	s->kitems = items;
 }
 
 // z = M^-1 r on the solver's own vectors: z = 0, then nmg V-cycles
 static void pcg_precondition(cedar_amd_solver *s, int nmg, hipStream_t st)
 {
-	clear(s->kz, s->lv[0].npts, st);
+	clear(s->kz, s->lv[0].npts * (size_t)s->nb, st);
 	for (int c = 0; c < nmg; c++) cycle_on(s, s->kz, s->kr, st);
 }
 
@@ -1136,6 +1147,99 @@ int cedar_amd_solver_pcg(cedar_amd_solver *s, const real_t *b, real_t *x, const 
 	}
 	launch_check("cedar_amd_solver_pcg");
 	return it;
+}
+
+// cedar_amd_solver_pcg on nrhs right-hand sides in lockstep: the loop above with every pass batched (krylov.hip *_many;
+// the preconditioner is the batched cycle on the handle's own nrhs pairs (z, r)).  One host read of nrhs scalar blocks
+// per iteration.  An item that met its stop test, broke down or had nothing to do leaves the `active` mask: its x, r,
+// scalars stay as they are from then on (it still rides through the batched cycle, which has no mask; its z is unused).
+int cedar_amd_solver_pcg_many(cedar_amd_solver *s, int nrhs, const real_t *b, real_t *x, const cedar_amd_pcg_settings *settings,
+                              real_t *hist, int *iters)
+{
+	const char *who = "cedar_amd_solver_pcg_many";
+	if (null_handle(s, who) || many_refused(s, nrhs, who)) return -1;
+	cedar_amd_pcg_settings p;
+	if (settings) p = *settings;
+	else cedar_amd_default_pcg_settings(&p);
+	if (pcg_refused(s, p, who)) return -1;
+	if (nrhs == 1) { // the single-vector path, partial-sum sweeps included
+		const int it = cedar_amd_solver_pcg(s, b, x, &p, hist);
+		if (iters && it >= 0) iters[0] = it;
+		return it;
+	}
+	pcg_alloc(s, s->nb_alloc);
+	Level &L = s->lv[0];
+	hipStream_t st = current_stream();
+	BatchScope scope(s, nrhs);
+	Staged sx(x, L.npts * nrhs, true, true), sb(b, L.npts * nrhs, true, false);
+	real_t *X = sx.get();
+	const Batch bt{nrhs, L.npts};
+	const int zm = p.precon == CEDAR_AMD_PCG_PRECON_NONE ? 0 : p.precon == CEDAR_AMD_PCG_PRECON_DIAG ? 1 : 2;
+	real_t *Z = zm == 0 ? s->kr : s->kz;
+	const Op3 ilv = L.Ailv ? op3_ilv(L.Ailv, L.II, L.JJ, L.KK) : Op3{};
+	const bool mnorm = p.stop_test >= CEDAR_AMD_PCG_STOP_ABS_RES_M2;
+	const bool rel = p.stop_test == CEDAR_AMD_PCG_STOP_REL_RES_L2 || p.stop_test == CEDAR_AMD_PCG_STOP_REL_RES_M2;
+	const size_t ld = (size_t)p.max_iter + 1; // row length of hist
+	double sc[CEDAR_AMD_MAX_RHS * PCG_NSC], r0[CEDAR_AMD_MAX_RHS], m0[CEDAR_AMD_MAX_RHS];
+	int itm[CEDAR_AMD_MAX_RHS];
+	auto scalars = [&]() {
+		CEDAR_HIP_CHECK(hipMemcpyAsync(sc, s->ksc, (size_t)nrhs * PCG_NSC * sizeof(double), hipMemcpyDeviceToHost, st));
+		CEDAR_HIP_CHECK(hipStreamSynchronize(st));
+	};
+	auto stop = [&](int m, double rr, double rz) {
+		const double v = mnorm ? std::sqrt(rz > 0 ? rz : 0.0) : std::sqrt(rr);
+		return (rel ? v / (mnorm ? m0[m] : r0[m]) : v) < p.tol;
+	};
+	const unsigned all = nrhs >= 32 ? ~0u : (1u << nrhs) - 1u;
+
+	// r0 = b - A x0, z0 = M^-1 r0, rho0 = r0.z0 of every item
+	zero_fill(s->ksc, (size_t)PCG_NSC * nrhs, st);
+	residual(s, L, X, sb.get(), s->kr, st);
+	if (zm == 2) pcg_precondition(s, p.nmg_cycles, st);
+	pcg_update_many(zm, false, X, s->kr, nullptr, nullptr, Z, L.A, L.II, L.JJ, L.KK, true, s->kslab, s->ksc, st, bt, all);
+	scalars();
+	unsigned active = 0;
+	for (int m = 0; m < nrhs; m++) {
+		const double *q = sc + (size_t)m * PCG_NSC;
+		r0[m] = std::sqrt(q[PCG_RR]);
+		m0[m] = std::sqrt(q[PCG_RZ] > 0 ? q[PCG_RZ] : 0.0);
+		itm[m] = 0;
+		if (hist) hist[m * ld] = r0[m];
+		// b = A x0 exactly, r0.z0 <= 0 (M not positive definite on r0), or already converged: nothing to do for this item
+		if (!(r0[m] == 0.0 || !(q[PCG_RZ] > 0) || stop(m, q[PCG_RR], q[PCG_RZ]))) active |= 1u << m;
+	}
+	for (int k = 0; k < p.max_iter && active; k++) {
+		real_t *pold = s->kp[(k + 1) & 1], *pn = s->kp[k & 1];
+		pcg_direction_many(L.A, L.Ailv ? &ilv : nullptr, Z, pold, pn, s->kw, s->nd, L.nst, L.II, L.JJ, L.KK, k == 0, s->kslab,
+		                   s->ksc, st, bt, active);
+		pcg_update_many(zm == 2 ? 3 : zm, true, X, s->kr, pn, s->kw, Z, L.A, L.II, L.JJ, L.KK, false, s->kslab, s->ksc, st, bt,
+		                active);
+		const bool last = k + 1 == p.max_iter;
+		if (zm == 2 && mnorm) { // the M-norm of the new residuals needs their preconditioned form first
+			pcg_precondition(s, p.nmg_cycles, st);
+			pcg_update_many(2, false, X, s->kr, nullptr, nullptr, Z, L.A, L.II, L.JJ, L.KK, false, s->kslab, s->ksc, st, bt, active);
+		}
+		scalars();
+		for (int m = 0; m < nrhs; m++) {
+			if (!((active >> m) & 1u)) continue;
+			const double *q = sc + (size_t)m * PCG_NSC;
+			if (q[PCG_FLAG] != 0) { active &= ~(1u << m); continue; } // breakdown: alpha was 0, x is as it was
+			itm[m] = k + 1;
+			if (hist) hist[m * ld + itm[m]] = std::sqrt(q[PCG_RR]) / r0[m];
+			if (stop(m, q[PCG_RR], q[PCG_RZ])) active &= ~(1u << m);
+		}
+		if (zm == 2 && !mnorm && !last && active) {
+			pcg_precondition(s, p.nmg_cycles, st);
+			pcg_update_many(2, false, X, s->kr, nullptr, nullptr, Z, L.A, L.II, L.JJ, L.KK, false, s->kslab, s->ksc, st, bt, active);
+		}
+	}
+	launch_check(who);
+	int most = 0;
+	for (int m = 0; m < nrhs; m++) {
+		if (iters) iters[m] = itm[m];
+		most = std::max(most, itm[m]);
+	}
+	return most;
 }
 
 void cedar_amd_solver_precondition(cedar_amd_solver *s, real_t *z, const real_t *r)

@@ -108,16 +108,9 @@ public:
 		}
 	}
 
-	// conjugate gradients preconditioned by the cycle (cedar_amd_solver_pcg), configured by the keys pcg.max-iter,
-	// pcg.tol, pcg.stop-test (BoxMG's 0..3 or abs-l2 / rel-l2 / abs-m / rel-m), pcg.precon (1..3 or none / diag / mg) and
-	// pcg.nmg-cycles; `history` as after solve().  Resident path only.
-	void pcg(const grid_func & b, grid_func & x)
+	// the pcg.* keys of the configuration over the library's defaults (pcg and pcg_many)
+	cedar_amd_pcg_settings pcg_settings()
 	{
-		history.clear();
-		if (!resident()) {
-			log::error << "pcg: needs the device-resident solver (every kernel \"hip\")" << std::endl;
-			return;
-		}
 		cedar_amd_pcg_settings ps;
 		cedar_amd_default_pcg_settings(&ps);
 		auto pick = [this](const char * key, int dflt, const char * const * names, int first) {
@@ -134,6 +127,20 @@ public:
 		ps.stop_test = pick("pcg.stop-test", ps.stop_test, stops, CEDAR_AMD_PCG_STOP_ABS_RES_L2);
 		ps.precon = pick("pcg.precon", ps.precon, precons, CEDAR_AMD_PCG_PRECON_NONE);
 		ps.nmg_cycles = conf->get<int>("pcg.nmg-cycles", ps.nmg_cycles);
+		return ps;
+	}
+
+	// conjugate gradients preconditioned by the cycle (cedar_amd_solver_pcg), configured by the keys pcg.max-iter,
+	// pcg.tol, pcg.stop-test (BoxMG's 0..3 or abs-l2 / rel-l2 / abs-m / rel-m), pcg.precon (1..3 or none / diag / mg) and
+	// pcg.nmg-cycles; `history` as after solve().  Resident path only.
+	void pcg(const grid_func & b, grid_func & x)
+	{
+		history.clear();
+		if (!resident()) {
+			log::error << "pcg: needs the device-resident solver (every kernel \"hip\")" << std::endl;
+			return;
+		}
+		const cedar_amd_pcg_settings ps = pcg_settings();
 		std::vector<real_t> rel(ps.max_iter > 0 ? ps.max_iter + 1 : 1);
 		int n = cedar_amd_solver_pcg(h, b.data(), x.data(), &ps, rel.data());
 		if (n < 0) return;
@@ -177,6 +184,43 @@ public:
 		for (std::size_t m = 0; m < nrhs; m++) {
 			std::copy(xx.begin() + m * npts, xx.begin() + (m + 1) * npts, x[m].data());
 			histories.emplace_back(rel.begin() + m * ld, rel.begin() + m * ld + n + 1);
+		}
+		history = histories[0];
+	}
+
+	// pcg on several right-hand sides in lockstep (cedar_amd_solver_pcg_many): the pcg.* keys of pcg, room made with
+	// solver.max-rhs.  histories[m]: item m's history cut to its own iterations[m]; `history` holds item 0's.  An item
+	// that has converged is left alone from then on, so x[m] is what pcg(b[m], x[m]) gives.  Resident path only.
+	void pcg_many(const std::vector<grid_func> & b, std::vector<grid_func> & x)
+	{
+		history.clear();
+		histories.clear();
+		iterations.clear();
+		if (!resident()) {
+			log::error << "pcg_many: needs the device-resident solver (every kernel \"hip\")" << std::endl;
+			return;
+		}
+		const std::size_t nrhs = b.size();
+		if (nrhs == 0 || x.size() != nrhs) {
+			log::error << "pcg_many: b and x must hold the same number (at least one) of grid functions" << std::endl;
+			return;
+		}
+		const cedar_amd_pcg_settings ps = pcg_settings();
+		const std::size_t npts = b[0].size(), ld = (std::size_t)(ps.max_iter > 0 ? ps.max_iter : 0) + 1;
+		std::vector<real_t> bb(npts * nrhs), xx(npts * nrhs), rel(ld * nrhs);
+		for (std::size_t m = 0; m < nrhs; m++) {
+			std::copy(b[m].data(), b[m].data() + npts, bb.begin() + m * npts);
+			std::copy(x[m].data(), x[m].data() + npts, xx.begin() + m * npts);
+		}
+		iterations.assign(nrhs, 0);
+		const int n = cedar_amd_solver_pcg_many(h, (int)nrhs, bb.data(), xx.data(), &ps, rel.data(), iterations.data());
+		if (n < 0) {
+			iterations.clear();
+			return;
+		}
+		for (std::size_t m = 0; m < nrhs; m++) {
+			std::copy(xx.begin() + m * npts, xx.begin() + (m + 1) * npts, x[m].data());
+			histories.emplace_back(rel.begin() + m * ld, rel.begin() + m * ld + iterations[m] + 1);
 		}
 		history = histories[0];
 	}

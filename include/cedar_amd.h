@@ -407,7 +407,8 @@ void cedar_amd_solver_precondition(cedar_amd_solver *s, real_t *z, const real_t 
  *    and line relaxation.  The _many calls are refused (print_error, return -1, nothing written) for nrhs < 1,
  *    nrhs > max_rhs, ibc != 0, an F-cycle and 3D plane relaxation; such a handle reports max_rhs 1.
  *  - Items nrhs .. max_rhs-1 are not touched (the solver's own level vectors of the unused items may hold anything).
- *  - Not offered: _pcg on several right-hand sides, the domain-decomposed solvers, the bmg2_/bmg3_ C interface. */
+ *  - Conjugate gradients on a batch: cedar_amd_solver_pcg_many below.
+ *  - Not offered: the domain-decomposed solvers, the bmg2_/bmg3_ C interface. */
 enum { CEDAR_AMD_MAX_RHS = 32 };
 /* as cedar_amd_solver_create, with room for max_rhs right-hand sides (1 .. 32) on every level; max_rhs outside that range:
  * print_error, NULL */
@@ -428,6 +429,40 @@ int cedar_amd_solver_vcycle_many(cedar_amd_solver *s, int nrhs, real_t *x, const
 int cedar_amd_solver_solve_many(cedar_amd_solver *s, int nrhs, const real_t *b, real_t *x, real_t *rel, int *iters);
 /* timing aid next to cedar_amd_solver_time_vcycles: n cycles on nrhs device-resident items, HIP-event ms (-1: refused) */
 float cedar_amd_solver_time_vcycles_many(cedar_amd_solver *s, int nrhs, real_t *x_dev, const real_t *b_dev, int n);
+/* cedar_amd_solver_pcg on the first nrhs items of b, x (item-major) in lockstep on a handle made with
+ * cedar_amd_solver_create_many: nrhs independent CG recurrences that share the operator fetches of every pass (krylov.hip
+ * *_many) and the batched cycle as preconditioner -- not a block CG, the items share no search space.
+ * hist: nrhs rows of p->max_iter + 1 entries (may be NULL), row m as cedar_amd_solver_pcg writes it for item m; iters[m]
+ * (may be NULL): the value that call would return for item m.  Returns the largest iters[m], -1 when refused.
+ *  - An item is frozen when it meets the stop test, breaks down, or starts with r0 == 0, r0.z0 <= 0 or converged: from
+ *    then on its x, its hist row beyond iters[m] and iters[m] are exactly what the single call leaves, and the loop ends
+ *    when no item is active or max_iter is reached.  This differs from cedar_amd_solver_solve_many, which keeps cycling
+ *    converged items: a CG item that goes on after convergence runs into rho -> 0 and the breakdown branch, and x equal
+ *    to the single call's bit for bit is worth more.  Frozen items still ride through the batched preconditioner cycle
+ *    (the cycle has no item mask; their z is not used): the known cost of lockstep.
+ *  - Bits: item m's x, hist row and iters[m] equal those of cedar_amd_solver_pcg on item m alone on a single-vector handle
+ *    in reference order (the default path where no 27-point level has 160 rows or more, CEDAR_AMD_PSUM=0 otherwise).
+ *    nrhs == 1 runs the single-vector path itself (partial-sum sweeps included) and equals cedar_amd_solver_pcg on any handle.
+ *  - Storage: five level-0 vectors per item plus slabs and scalar blocks for max_rhs items, allocated on the first call
+ *    and kept until cedar_amd_solver_destroy; cedar_amd_solver_pcg on the same handle works on item 0's set.
+ *  - Refused (print_error, -1, x / hist / iters untouched, the handle stays usable), decided before any allocation or
+ *    launch: whatever the other _many calls refuse and whatever cedar_amd_solver_pcg refuses.  Served: every precon and
+ *    stop_test; 3D 7- and 27-point with point relaxation, 2D 5- and 9-point with point and line relaxation.
+ *  - Out of scope: the domain-decomposed drivers, periodic boundaries, F-cycles, 3D plane relaxation, the bmg2_/bmg3_ C
+ *    interface, a true block CG. */
+int cedar_amd_solver_pcg_many(cedar_amd_solver *s, int nrhs, const real_t *b, real_t *x,
+                              const cedar_amd_pcg_settings *p, real_t *hist, int *iters);
+/* the batched passes one by one on caller arrays, as cedar_amd_pcg_direction / _update do for one vector (no rank-grid
+ * `partial`): vectors hold at least nrhs items back to back, the operator (and diag) is shared; sc = nrhs blocks of
+ * CEDAR_AMD_PCG_NSC doubles, item m reads beta / alpha from and writes its scalars to block m; slabs NaN-filled before the
+ * launch.  `active`: bit m clear = item m is skipped, its outputs and its block stay as given.  Item m's vectors and
+ * scalars have the bits the single-vector call gives on item m alone.  0, or -1 (print_error, nothing done) for nrhs
+ * outside 1 .. 32 or arguments the single-vector calls refuse. */
+int cedar_amd_pcg_direction_many(int nrhs, unsigned active, const real_t *so, const real_t *z, const real_t *p,
+                                 real_t *pn, real_t *w, len_t ii, len_t jj, len_t kk, int nstncl, int first, real_t *sc);
+int cedar_amd_pcg_update_many(int nrhs, unsigned active, int zmode, int move, real_t *x, real_t *r, const real_t *p,
+                              const real_t *w, real_t *z, const real_t *diag, len_t ii, len_t jj, len_t kk, int first,
+                              real_t *sc);
 /* The batched 3D kernels one by one on caller arrays (host or device; vectors hold nrhs items back to back, operator
  * arrays are shared); argument order of the BMG3_SymStd_* drop-ins, nstncl = 4|14, Dirichlet.  interp_add3 keeps the
  * reference's side effect (res /= so(kp)) per item.  0, or -1 (print_error, nothing done) for nrhs outside 1 .. 32, an
