@@ -9,7 +9,9 @@
 // the reference's term order, so the solve-phase kernels round exactly like
 // the reference's FMA-free CPU build.
 #pragma once
+#include "../../include/cedar_amd.h"
 #include <hip/hip_runtime.h>
+#include <cmath>
 #include <cstddef>
 #include <cstdint>
 #include <cstdio>
@@ -247,6 +249,33 @@ void solve_cg3(real_t *q, const real_t *qf, int II, int JJ, int KK, const real_t
 // krylov.hip: the vector work of the preconditioned conjugate gradient (solver.cpp cedar_amd_solver_pcg).  The scalars
 // of a run live on the device in sc[PCG_NSC]; the kernels read alpha / beta from there and write them back.
 enum { PCG_RHO = 0, PCG_SIGMA = 1, PCG_ALPHA = 2, PCG_BETA = 3, PCG_RR = 4, PCG_RZ = 5, PCG_FLAG = 6, PCG_NSC = 8 };
+// What a run's settings decide on the host, for the resident solver and the rank grid alike (solver.cpp pcg_run,
+// dist_common.h dist_pcg).  zm: where z = M^-1 r comes from, 0 z = r, 1 z = r / diag, 2 the multigrid cycle; the stop test
+// is on ||r||_2, or with mnorm on sqrt(r.z), relative (rel) to its initial value or absolute.
+struct PcgRule {
+	int zm;
+	bool mnorm, rel;
+	double tol;
+	// rr = r.r and rz = r.z of the current residual, r0 = ||r0||_2, m0 = sqrt(r0.z0)
+	bool stop(double rr, double rz, double r0, double m0) const
+	{
+		const double v = mnorm ? std::sqrt(rz > 0 ? rz : 0.0) : std::sqrt(rr);
+		return (rel ? v / (mnorm ? m0 : r0) : v) < tol;
+	}
+};
+static inline PcgRule pcg_rule(const cedar_amd_pcg_settings &p)
+{
+	return PcgRule{p.precon == CEDAR_AMD_PCG_PRECON_NONE ? 0 : p.precon == CEDAR_AMD_PCG_PRECON_DIAG ? 1 : 2,
+	               p.stop_test >= CEDAR_AMD_PCG_STOP_ABS_RES_M2,
+	               p.stop_test == CEDAR_AMD_PCG_STOP_REL_RES_L2 || p.stop_test == CEDAR_AMD_PCG_STOP_REL_RES_M2, p.tol};
+}
+static inline cedar_amd_pcg_settings pcg_settings_or_default(const cedar_amd_pcg_settings *settings)
+{
+	cedar_amd_pcg_settings p;
+	if (settings) p = *settings;
+	else cedar_amd_default_pcg_settings(&p);
+	return p;
+}
 size_t pcg_slab_doubles(int nd, int nst, int II, int JJ, int KK); // partial-sum slab of the two launchers below
 // pn = z + beta p (first: pn = z), w = A pn, sigma = pn.w, alpha = rho / sigma (0 and PCG_FLAG = 1 when sigma <= 0 or
 // rho = 0); op27: the operator view of a 27-point level (nullptr: the Cedar planes of so)

@@ -336,17 +336,14 @@ template <class Resid, class Cycle>
 int dist_pcg(RankCtx *d, const PcgBox &B, int pre, int post, const real_t *b, real_t *x, const cedar_amd_pcg_settings *settings,
              real_t *hist, const char *who, Resid resid, Cycle vcycle)
 {
-	cedar_amd_pcg_settings p;
-	if (settings) p = *settings;
-	else cedar_amd_default_pcg_settings(&p);
+	const cedar_amd_pcg_settings p = pcg_settings_or_default(settings);
 	if (dist_pcg_refused(pre, post, p, who)) return -1;
 	krylov_alloc(d, B);
 	Krylov &K = d->kry;
 	hipStream_t st = current_stream();
-	const int zm = p.precon == CEDAR_AMD_PCG_PRECON_NONE ? 0 : p.precon == CEDAR_AMD_PCG_PRECON_DIAG ? 1 : 2;
+	const PcgRule rule = pcg_rule(p);
+	const int zm = rule.zm;
 	real_t *Z = zm == 0 ? K.r : K.z;
-	const bool mnorm = p.stop_test >= CEDAR_AMD_PCG_STOP_ABS_RES_M2;
-	const bool rel = p.stop_test == CEDAR_AMD_PCG_STOP_REL_RES_L2 || p.stop_test == CEDAR_AMD_PCG_STOP_REL_RES_M2;
 	auto exch = [&](real_t *a) { halo_exchange(d, *B.halo, B.II, B.JJ, B.KK, a, 1, 0); };
 	auto precondition = [&]() {
 		CEDAR_HIP_CHECK(hipMemsetAsync(K.z, 0, B.npts * sizeof(real_t), st));
@@ -370,12 +367,8 @@ int dist_pcg(RankCtx *d, const PcgBox &B, int pre, int post, const real_t *b, re
 	dots(zm, false, nullptr, true);
 	const double r0 = std::sqrt(sc[PCG_RR]), m0 = std::sqrt(sc[PCG_RZ] > 0 ? sc[PCG_RZ] : 0.0);
 	if (hist) hist[0] = r0;
-	auto stop = [&](double rr, double rz) {
-		const double v = mnorm ? std::sqrt(rz > 0 ? rz : 0.0) : std::sqrt(rr);
-		return (rel ? v / (mnorm ? m0 : r0) : v) < p.tol;
-	};
 	int it = 0;
-	if (!(r0 == 0.0 || !(sc[PCG_RZ] > 0) || stop(sc[PCG_RR], sc[PCG_RZ])))
+	if (!(r0 == 0.0 || !(sc[PCG_RZ] > 0) || rule.stop(sc[PCG_RR], sc[PCG_RZ], r0, m0)))
 		for (int k = 0; k < p.max_iter; k++) {
 			real_t *pold = K.p[(k + 1) & 1], *pn = K.p[k & 1];
 			pcg_direction(B.A, B.op27, Z, pold, pn, K.w, B.nd, B.nst, B.II, B.JJ, B.KK, k == 0, K.slab, K.sc, st, K.part);
@@ -391,7 +384,7 @@ int dist_pcg(RankCtx *d, const PcgBox &B, int pre, int post, const real_t *b, re
 			if (sc[PCG_FLAG] != 0) break; // breakdown (p.Ap <= 0 or rho = 0): alpha was 0, x is as it was
 			it = k + 1;
 			if (hist) hist[it] = std::sqrt(sc[PCG_RR]) / r0;
-			if (stop(sc[PCG_RR], sc[PCG_RZ])) break;
+			if (rule.stop(sc[PCG_RR], sc[PCG_RZ], r0, m0)) break;
 		}
 	exch(x); // the caller's box as cedar_amd_dist*_solve leaves it: ghosts current
 	return it;
@@ -401,9 +394,7 @@ int dist_pcg(RankCtx *d, const PcgBox &B, int pre, int post, const real_t *b, re
 template <class Cycle>
 void dist_precondition(RankCtx *d, const PcgBox &B, int pre, int post, real_t *z, real_t *r, const char *who, Cycle vcycle)
 {
-	cedar_amd_pcg_settings p;
-	cedar_amd_default_pcg_settings(&p);
-	if (dist_pcg_refused(pre, post, p, who)) return;
+	if (dist_pcg_refused(pre, post, pcg_settings_or_default(nullptr), who)) return;
 	CEDAR_HIP_CHECK(hipMemsetAsync(z, 0, B.npts * sizeof(real_t), current_stream()));
 	vcycle(z, r);
 	halo_exchange(d, *B.halo, B.II, B.JJ, B.KK, z, 1, 0);

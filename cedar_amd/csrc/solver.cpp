@@ -192,14 +192,18 @@ bool ilv_wanted(const Level &L)
 	return ilv_doubles(L.II, L.JJ, L.KK) * sizeof(real_t) + tot / 10 < fr;
 }
 
+// the view of a 27-point level that its kernels read: the row-interleaved copy where the level keeps one, else the planes
+Op3 op3_of(const Level &L)
+{
+	return L.Ailv ? op3_ilv(L.Ailv, L.II, L.JJ, L.KK) : op3_cedar(L.A, L.SOR0, L.II, L.JJ, L.KK);
+}
+
 void residual(const cedar_amd_solver *s, const Level &L, const real_t *x, const real_t *b, real_t *r, hipStream_t st)
 {
 	if (s->nd == 2) residual2(L.A, b, x, r, L.II, L.JJ, L.nst, st, Batch{s->nb, L.npts});
-	else if (s->nb > 1 && L.nst == 14)
-		residual27_many(L.Ailv ? op3_ilv(L.Ailv, L.II, L.JJ, L.KK) : op3_cedar(L.A, L.SOR0, L.II, L.JJ, L.KK), b, x, r, L.II, L.JJ,
-		                L.KK, st, Batch{s->nb, L.npts});
+	else if (s->nb > 1 && L.nst == 14) residual27_many(op3_of(L), b, x, r, L.II, L.JJ, L.KK, st, Batch{s->nb, L.npts});
 	else if (s->nb > 1) residual7_many(L.A, b, x, r, L.II, L.JJ, L.KK, st, Batch{s->nb, L.npts});
-	else if (L.Ailv) residual27_op(op3_ilv(L.Ailv, L.II, L.JJ, L.KK), b, x, r, L.II, L.JJ, L.KK, st);
+	else if (L.Ailv) residual27_op(op3_of(L), b, x, r, L.II, L.JJ, L.KK, st);
 	else residual3(L.A, b, x, r, L.II, L.JJ, L.KK, L.nst, st);
 }
 
@@ -217,12 +221,24 @@ void lines_y(const Level &L, real_t *x, const real_t *b, const real_t *sor, int 
 	relax_lines_yt(L.At, L.bt, x, L.xt, sor, L.II, L.JJ, L.nst, updown, st, L.PFy, bt);
 }
 
+double l2_dev(cedar_amd_solver *s, const Level &L, const real_t *v)
+{
+	sumsq_interior(v, L.II, L.JJ, L.KK, s->red, s->red + 4096, current_stream());
+	double ss = 0;
+	CEDAR_HIP_CHECK(hipMemcpyAsync(&ss, s->red + 4096, sizeof(double), hipMemcpyDeviceToHost, current_stream()));
+	CEDAR_HIP_CHECK(hipStreamSynchronize(current_stream()));
+	return std::sqrt(ss);
+}
+
 // ------------------------------------------------------------------ plane relaxation
+// a plane sweep runs cycles of its 2D solvers, and a 3D cycle runs plane sweeps: the two below are defined after the cycle
 void cycle_on(cedar_amd_solver *s, real_t *x, const real_t *b, hipStream_t st);
 bool graph_prepare(cedar_amd_solver *s, real_t *x, const real_t *b, hipStream_t st);
-bool graph_ready(const cedar_amd_solver *s, const real_t *x, const real_t *b);
-double l2_dev(cedar_amd_solver *s, const Level &L, const real_t *v);
-void residual(const cedar_amd_solver *s, const Level &L, const real_t *x, const real_t *b, real_t *r, hipStream_t st);
+
+bool graph_ready(const cedar_amd_solver *s, const real_t *x, const real_t *b)
+{
+	return !s->use_graph || (s->gexec && s->gx == x && s->gb == b && s->gnb == s->nb);
+}
 
 // a solver on the same operator as `proto` that shares its set-up products and owns only its vectors
 cedar_amd_solver *clone_vectors(const cedar_amd_solver *proto)
@@ -376,15 +392,12 @@ void smooth(const cedar_amd_solver *s, const Level &L, real_t *x, const real_t *
 		}
 		if (s->nd == 3 && s->nb > 1) { // a batch of right-hand sides: reference order, operator fetched once (many3d.hip)
 			const Batch bt{s->nb, L.npts};
-			if (L.nst == 14)
-				relax3_gs27_many(L.Ailv ? op3_ilv(L.Ailv, L.II, L.JJ, L.KK) : op3_cedar(L.A, L.SOR0, L.II, L.JJ, L.KK), b, x, L.II,
-				                 L.JJ, L.KK, updown, st, bt);
+			if (L.nst == 14) relax3_gs27_many(op3_of(L), b, x, L.II, L.JJ, L.KK, updown, st, bt);
 			else relax3_gs7_many(L.A, b, x, L.SOR0, L.II, L.JJ, L.KK, updown, st, bt);
 			continue;
 		}
 		if (s->nd == 3) {
-			if (L.Ailv) relax3_gs27_op(op3_ilv(L.Ailv, L.II, L.JJ, L.KK), b, x, L.II, L.JJ, L.KK, updown, st, L.T);
-			else if (L.T) relax3_gs27_op(op3_cedar(L.A, L.SOR0, L.II, L.JJ, L.KK), b, x, L.II, L.JJ, L.KK, updown, st, L.T);
+			if (L.Ailv || L.T) relax3_gs27_op(op3_of(L), b, x, L.II, L.JJ, L.KK, updown, st, L.T);
 			else relax3_gs(L.A, b, x, L.SOR0, L.II, L.JJ, L.KK, L.nst, updown, st);
 			continue;
 		}
@@ -414,6 +427,21 @@ void smooth(const cedar_amd_solver *s, const Level &L, real_t *x, const real_t *
 	}
 }
 
+// the side streams of plane relaxation with their fork / join events; CEDAR_AMD_PLANE_STREAMS: how many (1 .. 64, default 8)
+void plane_streams_create(cedar_amd_solver *s)
+{
+	const char *es = getenv("CEDAR_AMD_PLANE_STREAMS");
+	int S = es ? atoi(es) : 8;
+	S = S < 1 ? 1 : S > 64 ? 64 : S;
+	s->pstreams.resize(S);
+	s->pevents.resize(S);
+	for (int t = 0; t < S; t++) {
+		CEDAR_HIP_CHECK(hipStreamCreateWithFlags(&s->pstreams[t], hipStreamNonBlocking));
+		CEDAR_HIP_CHECK(hipEventCreateWithFlags(&s->pevents[t], hipEventDisableTiming));
+	}
+	CEDAR_HIP_CHECK(hipEventCreateWithFlags(&s->pfork, hipEventDisableTiming));
+}
+
 void coarse_solve(cedar_amd_solver *s, real_t *x, const real_t *b, hipStream_t st)
 {
 	const Level &C = s->lv.back();
@@ -421,6 +449,31 @@ void coarse_solve(cedar_amd_solver *s, real_t *x, const real_t *b, hipStream_t s
 	else if (s->nd == 2) solve_cg2(x, b, C.II, C.JJ, s->ABD, s->bbd, s->nabd1, s->nabd2, st, Batch{s->nb, C.npts});
 	else if (s->st.ibc) solve_cg3_per(x, b, C.II, C.JJ, C.KK, s->ABD, s->bbd, s->nabd1, s->st.ibc, st);
 	else solve_cg3(x, b, C.II, C.JJ, C.KK, s->ABD, s->bbd, s->nabd1, s->nabd2, st, Batch{s->nb, C.npts});
+}
+
+// The transfers between a level L and the next coarser K, the one place that chooses their kernels by dimension, boundary
+// code and batch count.  restrict_to: K.b := P^T src; the periodic kernels first refresh the ghosts of src (restrict.f90:
+// 78-103), so it is not const.  interp_add_from: x += P K.x, with the residual correction from L.res.
+void restrict_to(const cedar_amd_solver *s, const Level &L, const Level &K, real_t *src, hipStream_t st)
+{
+	const int ibc = s->st.ibc;
+	const Batch bf{s->nb, L.npts}, bc{s->nb, K.npts};
+	if (s->nd == 2 && ibc) restrict2_per(src, K.b, K.P, L.II, L.JJ, K.II, K.JJ, ibc, st);
+	else if (s->nd == 2) restrict2(src, K.b, K.P, L.II, L.JJ, K.II, K.JJ, st, bf, bc);
+	else if (ibc) restrict3_per(src, K.b, K.P, L.II, L.JJ, L.KK, K.II, K.JJ, K.KK, ibc, st);
+	else if (s->nb > 1) restrict3_many(src, K.b, K.P, L.II, L.JJ, L.KK, K.II, K.JJ, K.KK, st, bf, bc);
+	else restrict3(src, K.b, K.P, L.II, L.JJ, L.KK, K.II, K.JJ, K.KK, st);
+}
+
+void interp_add_from(const cedar_amd_solver *s, const Level &L, const Level &K, real_t *x, hipStream_t st)
+{
+	const int ibc = s->st.ibc;
+	const Batch bf{s->nb, L.npts}, bc{s->nb, K.npts};
+	if (s->nd == 2 && ibc) interp_add2_per(x, K.x, L.res, L.A, K.P, K.II, K.JJ, L.II, L.JJ, ibc, st);
+	else if (s->nd == 2) interp_add2(x, K.x, L.res, L.A, K.P, K.II, K.JJ, L.II, L.JJ, st, bf, bc);
+	else if (ibc) interp_add3_per(x, K.x, L.A, L.res, K.P, K.II, K.JJ, K.KK, L.II, L.JJ, L.KK, ibc, st);
+	else if (s->nb > 1) interp_add3_many(x, K.x, L.A, L.res, K.P, K.II, K.JJ, K.KK, L.II, L.JJ, L.KK, st, bf, bc);
+	else interp_add3(x, K.x, L.A, L.res, K.P, K.II, K.JJ, K.KK, L.II, L.JJ, L.KK, st);
 }
 
 void ncycle(cedar_amd_solver *s, int lvl, real_t *x, const real_t *b, hipStream_t st)
@@ -438,12 +491,7 @@ void ncycle(cedar_amd_solver *s, int lvl, real_t *x, const real_t *b, hipStream_
 	} else {
 	smooth(s, L, x, b, BMG_DOWN, s->st.nrelax_pre, st);
 	residual(s, L, x, b, L.res, st);
-	if (s->nd == 2 && s->st.ibc) restrict2_per(L.res, K.b, K.P, L.II, L.JJ, K.II, K.JJ, s->st.ibc, st);
-	else if (s->nd == 2) restrict2(L.res, K.b, K.P, L.II, L.JJ, K.II, K.JJ, st, Batch{s->nb, L.npts}, Batch{s->nb, K.npts});
-	else if (s->st.ibc) restrict3_per(L.res, K.b, K.P, L.II, L.JJ, L.KK, K.II, K.JJ, K.KK, s->st.ibc, st);
-	else if (s->nb > 1)
-		restrict3_many(L.res, K.b, K.P, L.II, L.JJ, L.KK, K.II, K.JJ, K.KK, st, Batch{s->nb, L.npts}, Batch{s->nb, K.npts});
-	else restrict3(L.res, K.b, K.P, L.II, L.JJ, L.KK, K.II, K.JJ, K.KK, st);
+	restrict_to(s, L, K, L.res, st);
 	clear(K.x, K.npts * (size_t)s->nb, st); // coarse_x.set(0.0)
 	}
 	if (lvl + 1 == (int)s->lv.size() - 1) coarse_solve(s, K.x, K.b, st);
@@ -453,12 +501,7 @@ void ncycle(cedar_amd_solver *s, int lvl, real_t *x, const real_t *b, hipStream_
 		            Batch{s->nb, L.npts}, Batch{s->nb, K.npts});
 		return;
 	}
-	if (s->nd == 2 && s->st.ibc) interp_add2_per(x, K.x, L.res, L.A, K.P, K.II, K.JJ, L.II, L.JJ, s->st.ibc, st);
-	else if (s->nd == 2) interp_add2(x, K.x, L.res, L.A, K.P, K.II, K.JJ, L.II, L.JJ, st, Batch{s->nb, L.npts}, Batch{s->nb, K.npts});
-	else if (s->st.ibc) interp_add3_per(x, K.x, L.A, L.res, K.P, K.II, K.JJ, K.KK, L.II, L.JJ, L.KK, s->st.ibc, st);
-	else if (s->nb > 1)
-		interp_add3_many(x, K.x, L.A, L.res, K.P, K.II, K.JJ, K.KK, L.II, L.JJ, L.KK, st, Batch{s->nb, L.npts}, Batch{s->nb, K.npts});
-	else interp_add3(x, K.x, L.A, L.res, K.P, K.II, K.JJ, K.KK, L.II, L.JJ, L.KK, st);
+	interp_add_from(s, L, K, x, st);
 	smooth(s, L, x, b, BMG_UP, s->st.nrelax_post, st);
 }
 
@@ -472,20 +515,14 @@ void fmg_cycle(cedar_amd_solver *s, int lvl, real_t *x, const real_t *b, hipStre
 		return;
 	}
 	Level &L = s->lv[lvl], &K = s->lv[lvl + 1];
-	// periodic: the kernels of the V-cycle; the periodic restriction refreshes the ghosts of the vector it restricts
-	// (restrict.f90:78-103) -- here the right-hand side itself, which the reference's binding reaches through a const_cast
-	const int ibc = s->st.ibc;
-	if (s->nd == 2 && ibc) restrict2_per(const_cast<real_t *>(b), K.b, K.P, L.II, L.JJ, K.II, K.JJ, ibc, st);
-	else if (s->nd == 2) restrict2(b, K.b, K.P, L.II, L.JJ, K.II, K.JJ, st);
-	else if (ibc) restrict3_per(const_cast<real_t *>(b), K.b, K.P, L.II, L.JJ, L.KK, K.II, K.JJ, K.KK, ibc, st);
-	else restrict3(b, K.b, K.P, L.II, L.JJ, L.KK, K.II, K.JJ, K.KK, st);
+	// the transfers of the V-cycle (an F-cycle handle holds one right-hand side: solver_create); the periodic restriction
+	// refreshes the ghosts of the vector it restricts -- here the right-hand side itself, which the reference's binding
+	// reaches through a const_cast
+	restrict_to(s, L, K, const_cast<real_t *>(b), st);
 	fmg_cycle(s, lvl + 1, K.x, K.b, st);
 	zero_fill(x, L.npts, st);
 	zero_fill(L.res, L.npts, st);
-	if (s->nd == 2 && ibc) interp_add2_per(x, K.x, L.res, L.A, K.P, K.II, K.JJ, L.II, L.JJ, ibc, st);
-	else if (s->nd == 2) interp_add2(x, K.x, L.res, L.A, K.P, K.II, K.JJ, L.II, L.JJ, st);
-	else if (ibc) interp_add3_per(x, K.x, L.A, L.res, K.P, K.II, K.JJ, K.KK, L.II, L.JJ, L.KK, ibc, st);
-	else interp_add3(x, K.x, L.A, L.res, K.P, K.II, K.JJ, K.KK, L.II, L.JJ, L.KK, st);
+	interp_add_from(s, L, K, x, st);
 	ncycle(s, lvl, x, b, st);
 }
 
@@ -496,8 +533,23 @@ void cycle_launch(cedar_amd_solver *s, real_t *x, const real_t *b, hipStream_t s
 	else ncycle(s, 0, x, b, st);
 }
 
+// milliseconds, by HIP events, of what fn enqueues on st
+template <class F> float timed(hipStream_t st, F fn)
+{
+	hipEvent_t e0, e1;
+	CEDAR_HIP_CHECK(hipEventCreate(&e0));
+	CEDAR_HIP_CHECK(hipEventCreate(&e1));
+	CEDAR_HIP_CHECK(hipEventRecord(e0, st));
+	fn();
+	CEDAR_HIP_CHECK(hipEventRecord(e1, st));
+	CEDAR_HIP_CHECK(hipEventSynchronize(e1));
+	float ms = 0;
+	CEDAR_HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
+	(void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+	return ms;
+}
+
 // run one V-cycle on device pointers: graph replay when possible
-void cycle_on(cedar_amd_solver *s, real_t *x, const real_t *b, hipStream_t st);
 void cycle_dev(cedar_amd_solver *s, real_t *x, const real_t *b) { cycle_on(s, x, b, current_stream()); }
 
 // make s->gexec the instantiated graph of one cycle on (x, b) with the current batch count; returns true if it had to be
@@ -541,11 +593,6 @@ bool graph_prepare(cedar_amd_solver *s, real_t *x, const real_t *b, hipStream_t 
 	return true;
 }
 
-bool graph_ready(const cedar_amd_solver *s, const real_t *x, const real_t *b)
-{
-	return !s->use_graph || (s->gexec && s->gx == x && s->gb == b && s->gnb == s->nb);
-}
-
 void cycle_on(cedar_amd_solver *s, real_t *x, const real_t *b, hipStream_t st)
 {
 	if (!s->use_graph) {
@@ -554,15 +601,6 @@ void cycle_on(cedar_amd_solver *s, real_t *x, const real_t *b, hipStream_t st)
 	}
 	graph_prepare(s, x, b, st);
 	CEDAR_HIP_CHECK(hipGraphLaunch(s->gexec, st));
-}
-
-double l2_dev(cedar_amd_solver *s, const Level &L, const real_t *v)
-{
-	sumsq_interior(v, L.II, L.JJ, L.KK, s->red, s->red + 4096, current_stream());
-	double ss = 0;
-	CEDAR_HIP_CHECK(hipMemcpyAsync(&ss, s->red + 4096, sizeof(double), hipMemcpyDeviceToHost, current_stream()));
-	CEDAR_HIP_CHECK(hipStreamSynchronize(current_stream()));
-	return std::sqrt(ss);
 }
 
 } // namespace
@@ -619,17 +657,7 @@ static cedar_amd_solver *solver_create(int nd, len_t nx, len_t ny, len_t nz, int
 		// the plane solves of a colour run on side streams and replay graphs of their own: the 3D cycle is launched
 		// eagerly (capturing it would nest graph launches)
 		s->use_graph = false;
-		const char *es = getenv("CEDAR_AMD_PLANE_STREAMS");
-		int S = es ? atoi(es) : 8;
-		if (S < 1) S = 1;
-		if (S > 64) S = 64;
-		s->pstreams.resize(S);
-		s->pevents.resize(S);
-		for (int t = 0; t < S; t++) {
-			CEDAR_HIP_CHECK(hipStreamCreateWithFlags(&s->pstreams[t], hipStreamNonBlocking));
-			CEDAR_HIP_CHECK(hipEventCreateWithFlags(&s->pevents[t], hipEventDisableTiming));
-		}
-		CEDAR_HIP_CHECK(hipEventCreateWithFlags(&s->pfork, hipEventDisableTiming));
+		plane_streams_create(s);
 	}
 	if (s->st.ibc != 0) {
 		// periodic boundary conditions (V- and F-cycles).  2D: ibc 1..3, point relaxation keeps a row in the default LDS
@@ -1082,123 +1110,55 @@ static void pcg_precondition(cedar_amd_solver *s, int nmg, hipStream_t st)
 	for (int c = 0; c < nmg; c++) cycle_on(s, s->kz, s->kr, st);
 }
 
-static void pcg_scalars(cedar_amd_solver *s, double *sc, hipStream_t st)
+// The iteration of cedar_amd_solver_pcg / _pcg_many on nrhs right-hand sides in lockstep.  nrhs == 1: the single-vector
+// passes of krylov.hip and the single-vector cycle (partial-sum sweeps included) on item 0's storage; else every pass
+// batched (krylov.hip *_many) and the preconditioner the batched cycle on the handle's own nrhs pairs (z, r).  One host
+// read of nrhs scalar blocks per iteration.  An item that met its stop test, broke down or had nothing to do leaves the
+// `active` mask: its x, r, scalars stay as they are from then on (it still rides through the batched cycle, which has no
+// mask; its z is unused).  hist: rows of max_iter + 1 entries, those after an item's last iteration unwritten; iters
+// (may be null): the items' counts.  Returns the largest.
+static int pcg_run(cedar_amd_solver *s, int nrhs, const real_t *b, real_t *x, const cedar_amd_pcg_settings &p, real_t *hist,
+                   int *iters, const char *who)
 {
-	CEDAR_HIP_CHECK(hipMemcpyAsync(sc, s->ksc, PCG_NSC * sizeof(double), hipMemcpyDeviceToHost, st));
-	CEDAR_HIP_CHECK(hipStreamSynchronize(st));
-}
-
-int cedar_amd_solver_pcg(cedar_amd_solver *s, const real_t *b, real_t *x, const cedar_amd_pcg_settings *settings, real_t *hist)
-{
-	if (null_handle(s, "cedar_amd_solver_pcg")) return -1;
-	cedar_amd_pcg_settings p;
-	if (settings) p = *settings;
-	else cedar_amd_default_pcg_settings(&p);
-	if (pcg_refused(s, p, "cedar_amd_solver_pcg")) return -1;
-	pcg_alloc(s);
-	Level &L = s->lv[0];
-	hipStream_t st = current_stream();
-	Staged sx(x, L.npts, true, true), sb(b, L.npts, true, false);
-	real_t *X = sx.get();
-	const int zm = p.precon == CEDAR_AMD_PCG_PRECON_NONE ? 0 : p.precon == CEDAR_AMD_PCG_PRECON_DIAG ? 1 : 2;
-	real_t *Z = zm == 0 ? s->kr : s->kz;
-	const Op3 ilv = L.Ailv ? op3_ilv(L.Ailv, L.II, L.JJ, L.KK) : Op3{};
-	const bool mnorm = p.stop_test >= CEDAR_AMD_PCG_STOP_ABS_RES_M2;
-	const bool rel = p.stop_test == CEDAR_AMD_PCG_STOP_REL_RES_L2 || p.stop_test == CEDAR_AMD_PCG_STOP_REL_RES_M2;
-	double sc[PCG_NSC];
-
-	// r0 = b - A x0, z0 = M^-1 r0, rho0 = r0.z0 (pcg_update without the update)
-	zero_fill(s->ksc, PCG_NSC, st);
-	residual(s, L, X, sb.get(), s->kr, st);
-	if (zm == 2) pcg_precondition(s, p.nmg_cycles, st);
-	pcg_update(zm, false, X, s->kr, nullptr, nullptr, Z, L.A, L.II, L.JJ, L.KK, true, s->kslab, s->ksc, st);
-	pcg_scalars(s, sc, st);
-	const double r0 = std::sqrt(sc[PCG_RR]), m0 = std::sqrt(sc[PCG_RZ] > 0 ? sc[PCG_RZ] : 0.0);
-	if (hist) hist[0] = r0;
-	auto stop = [&](double rr, double rz) {
-		const double v = mnorm ? std::sqrt(rz > 0 ? rz : 0.0) : std::sqrt(rr);
-		return (rel ? v / (mnorm ? m0 : r0) : v) < p.tol;
-	};
-	// b = A x0 exactly, r0.z0 <= 0 (M not positive definite on r0), or already converged
-	if (r0 == 0.0 || !(sc[PCG_RZ] > 0) || stop(sc[PCG_RR], sc[PCG_RZ])) {
-		launch_check("cedar_amd_solver_pcg");
-		return 0;
-	}
-	int it = 0;
-	for (int k = 0; k < p.max_iter; k++) {
-		real_t *pold = s->kp[(k + 1) & 1], *pn = s->kp[k & 1];
-		pcg_direction(L.A, L.Ailv ? &ilv : nullptr, Z, pold, pn, s->kw, s->nd, L.nst, L.II, L.JJ, L.KK, k == 0, s->kslab,
-		              s->ksc, st);
-		pcg_update(zm == 2 ? 3 : zm, true, X, s->kr, pn, s->kw, Z, L.A, L.II, L.JJ, L.KK, false, s->kslab, s->ksc, st);
-		const bool last = k + 1 == p.max_iter;
-		if (zm == 2 && mnorm) { // the M-norm of the new residual needs its preconditioned form first
-			pcg_precondition(s, p.nmg_cycles, st);
-			pcg_update(2, false, X, s->kr, nullptr, nullptr, Z, L.A, L.II, L.JJ, L.KK, false, s->kslab, s->ksc, st);
-		}
-		pcg_scalars(s, sc, st);
-		if (sc[PCG_FLAG] != 0) break; // breakdown (p.Ap <= 0 or rho = 0): alpha was 0, x is as it was
-		it = k + 1;
-		if (hist) hist[it] = std::sqrt(sc[PCG_RR]) / r0;
-		if (stop(sc[PCG_RR], sc[PCG_RZ])) break;
-		if (zm == 2 && !mnorm && !last) {
-			pcg_precondition(s, p.nmg_cycles, st);
-			pcg_update(2, false, X, s->kr, nullptr, nullptr, Z, L.A, L.II, L.JJ, L.KK, false, s->kslab, s->ksc, st);
-		}
-	}
-	launch_check("cedar_amd_solver_pcg");
-	return it;
-}
-
-// cedar_amd_solver_pcg on nrhs right-hand sides in lockstep: the loop above with every pass batched (krylov.hip *_many;
-// the preconditioner is the batched cycle on the handle's own nrhs pairs (z, r)).  One host read of nrhs scalar blocks
-// per iteration.  An item that met its stop test, broke down or had nothing to do leaves the `active` mask: its x, r,
-// scalars stay as they are from then on (it still rides through the batched cycle, which has no mask; its z is unused).
-int cedar_amd_solver_pcg_many(cedar_amd_solver *s, int nrhs, const real_t *b, real_t *x, const cedar_amd_pcg_settings *settings,
-                              real_t *hist, int *iters)
-{
-	const char *who = "cedar_amd_solver_pcg_many";
-	if (null_handle(s, who) || many_refused(s, nrhs, who)) return -1;
-	cedar_amd_pcg_settings p;
-	if (settings) p = *settings;
-	else cedar_amd_default_pcg_settings(&p);
-	if (pcg_refused(s, p, who)) return -1;
-	if (nrhs == 1) { // the single-vector path, partial-sum sweeps included
-		const int it = cedar_amd_solver_pcg(s, b, x, &p, hist);
-		if (iters && it >= 0) iters[0] = it;
-		return it;
-	}
-	pcg_alloc(s, s->nb_alloc);
+	pcg_alloc(s, nrhs == 1 ? 1 : s->nb_alloc);
 	Level &L = s->lv[0];
 	hipStream_t st = current_stream();
 	BatchScope scope(s, nrhs);
 	Staged sx(x, L.npts * nrhs, true, true), sb(b, L.npts * nrhs, true, false);
 	real_t *X = sx.get();
 	const Batch bt{nrhs, L.npts};
-	const int zm = p.precon == CEDAR_AMD_PCG_PRECON_NONE ? 0 : p.precon == CEDAR_AMD_PCG_PRECON_DIAG ? 1 : 2;
+	const PcgRule rule = pcg_rule(p);
+	const int zm = rule.zm;
 	real_t *Z = zm == 0 ? s->kr : s->kz;
-	const Op3 ilv = L.Ailv ? op3_ilv(L.Ailv, L.II, L.JJ, L.KK) : Op3{};
-	const bool mnorm = p.stop_test >= CEDAR_AMD_PCG_STOP_ABS_RES_M2;
-	const bool rel = p.stop_test == CEDAR_AMD_PCG_STOP_REL_RES_L2 || p.stop_test == CEDAR_AMD_PCG_STOP_REL_RES_M2;
+	const Op3 view = op3_of(L);
 	const size_t ld = (size_t)p.max_iter + 1; // row length of hist
 	double sc[CEDAR_AMD_MAX_RHS * PCG_NSC], r0[CEDAR_AMD_MAX_RHS], m0[CEDAR_AMD_MAX_RHS];
 	int itm[CEDAR_AMD_MAX_RHS];
+	unsigned active = nrhs >= 32 ? ~0u : (1u << nrhs) - 1u;
+	// the two passes on the active items; update: pn = nullptr leaves x and r where they are (dot products only)
+	auto direction = [&](const real_t *pold, real_t *pn, bool first) {
+		if (nrhs == 1)
+			pcg_direction(L.A, L.Ailv ? &view : nullptr, Z, pold, pn, s->kw, s->nd, L.nst, L.II, L.JJ, L.KK, first, s->kslab, s->ksc, st);
+		else
+			pcg_direction_many(L.A, L.Ailv ? &view : nullptr, Z, pold, pn, s->kw, s->nd, L.nst, L.II, L.JJ, L.KK, first, s->kslab,
+			                   s->ksc, st, bt, active);
+	};
+	auto update = [&](int zmode, const real_t *pn, bool first) {
+		const real_t *w = pn ? s->kw : nullptr;
+		if (nrhs == 1) pcg_update(zmode, pn != nullptr, X, s->kr, pn, w, Z, L.A, L.II, L.JJ, L.KK, first, s->kslab, s->ksc, st);
+		else pcg_update_many(zmode, pn != nullptr, X, s->kr, pn, w, Z, L.A, L.II, L.JJ, L.KK, first, s->kslab, s->ksc, st, bt, active);
+	};
 	auto scalars = [&]() {
 		CEDAR_HIP_CHECK(hipMemcpyAsync(sc, s->ksc, (size_t)nrhs * PCG_NSC * sizeof(double), hipMemcpyDeviceToHost, st));
 		CEDAR_HIP_CHECK(hipStreamSynchronize(st));
 	};
-	auto stop = [&](int m, double rr, double rz) {
-		const double v = mnorm ? std::sqrt(rz > 0 ? rz : 0.0) : std::sqrt(rr);
-		return (rel ? v / (mnorm ? m0[m] : r0[m]) : v) < p.tol;
-	};
-	const unsigned all = nrhs >= 32 ? ~0u : (1u << nrhs) - 1u;
 
-	// r0 = b - A x0, z0 = M^-1 r0, rho0 = r0.z0 of every item
+	// r0 = b - A x0, z0 = M^-1 r0, rho0 = r0.z0 of every item (the update pass without the update)
 	zero_fill(s->ksc, (size_t)PCG_NSC * nrhs, st);
 	residual(s, L, X, sb.get(), s->kr, st);
 	if (zm == 2) pcg_precondition(s, p.nmg_cycles, st);
-	pcg_update_many(zm, false, X, s->kr, nullptr, nullptr, Z, L.A, L.II, L.JJ, L.KK, true, s->kslab, s->ksc, st, bt, all);
+	update(zm, nullptr, true);
 	scalars();
-	unsigned active = 0;
 	for (int m = 0; m < nrhs; m++) {
 		const double *q = sc + (size_t)m * PCG_NSC;
 		r0[m] = std::sqrt(q[PCG_RR]);
@@ -1206,31 +1166,28 @@ int cedar_amd_solver_pcg_many(cedar_amd_solver *s, int nrhs, const real_t *b, re
 		itm[m] = 0;
 		if (hist) hist[m * ld] = r0[m];
 		// b = A x0 exactly, r0.z0 <= 0 (M not positive definite on r0), or already converged: nothing to do for this item
-		if (!(r0[m] == 0.0 || !(q[PCG_RZ] > 0) || stop(m, q[PCG_RR], q[PCG_RZ]))) active |= 1u << m;
+		if (r0[m] == 0.0 || !(q[PCG_RZ] > 0) || rule.stop(q[PCG_RR], q[PCG_RZ], r0[m], m0[m])) active &= ~(1u << m);
 	}
 	for (int k = 0; k < p.max_iter && active; k++) {
 		real_t *pold = s->kp[(k + 1) & 1], *pn = s->kp[k & 1];
-		pcg_direction_many(L.A, L.Ailv ? &ilv : nullptr, Z, pold, pn, s->kw, s->nd, L.nst, L.II, L.JJ, L.KK, k == 0, s->kslab,
-		                   s->ksc, st, bt, active);
-		pcg_update_many(zm == 2 ? 3 : zm, true, X, s->kr, pn, s->kw, Z, L.A, L.II, L.JJ, L.KK, false, s->kslab, s->ksc, st, bt,
-		                active);
-		const bool last = k + 1 == p.max_iter;
-		if (zm == 2 && mnorm) { // the M-norm of the new residuals needs their preconditioned form first
+		direction(pold, pn, k == 0);
+		update(zm == 2 ? 3 : zm, pn, false);
+		if (zm == 2 && rule.mnorm) { // the M-norm of the new residuals needs their preconditioned form first
 			pcg_precondition(s, p.nmg_cycles, st);
-			pcg_update_many(2, false, X, s->kr, nullptr, nullptr, Z, L.A, L.II, L.JJ, L.KK, false, s->kslab, s->ksc, st, bt, active);
+			update(2, nullptr, false);
 		}
 		scalars();
 		for (int m = 0; m < nrhs; m++) {
 			if (!((active >> m) & 1u)) continue;
 			const double *q = sc + (size_t)m * PCG_NSC;
-			if (q[PCG_FLAG] != 0) { active &= ~(1u << m); continue; } // breakdown: alpha was 0, x is as it was
+			if (q[PCG_FLAG] != 0) { active &= ~(1u << m); continue; } // breakdown (p.Ap <= 0 or rho = 0): alpha was 0, x is as it was
 			itm[m] = k + 1;
 			if (hist) hist[m * ld + itm[m]] = std::sqrt(q[PCG_RR]) / r0[m];
-			if (stop(m, q[PCG_RR], q[PCG_RZ])) active &= ~(1u << m);
+			if (rule.stop(q[PCG_RR], q[PCG_RZ], r0[m], m0[m])) active &= ~(1u << m);
 		}
-		if (zm == 2 && !mnorm && !last && active) {
+		if (zm == 2 && !rule.mnorm && k + 1 < p.max_iter && active) { // z of the new residuals, for the next direction
 			pcg_precondition(s, p.nmg_cycles, st);
-			pcg_update_many(2, false, X, s->kr, nullptr, nullptr, Z, L.A, L.II, L.JJ, L.KK, false, s->kslab, s->ksc, st, bt, active);
+			update(2, nullptr, false);
 		}
 	}
 	launch_check(who);
@@ -1242,12 +1199,30 @@ int cedar_amd_solver_pcg_many(cedar_amd_solver *s, int nrhs, const real_t *b, re
 	return most;
 }
 
+int cedar_amd_solver_pcg(cedar_amd_solver *s, const real_t *b, real_t *x, const cedar_amd_pcg_settings *settings, real_t *hist)
+{
+	const char *who = "cedar_amd_solver_pcg";
+	if (null_handle(s, who)) return -1;
+	const cedar_amd_pcg_settings p = pcg_settings_or_default(settings);
+	if (pcg_refused(s, p, who)) return -1;
+	return pcg_run(s, 1, b, x, p, hist, nullptr, who);
+}
+
+// served where the other batched entry points are (many_refused); one right-hand side takes the single-vector path
+int cedar_amd_solver_pcg_many(cedar_amd_solver *s, int nrhs, const real_t *b, real_t *x, const cedar_amd_pcg_settings *settings,
+                              real_t *hist, int *iters)
+{
+	const char *who = "cedar_amd_solver_pcg_many";
+	if (null_handle(s, who) || many_refused(s, nrhs, who)) return -1;
+	const cedar_amd_pcg_settings p = pcg_settings_or_default(settings);
+	if (pcg_refused(s, p, who)) return -1;
+	return pcg_run(s, nrhs, b, x, p, hist, iters, who);
+}
+
 void cedar_amd_solver_precondition(cedar_amd_solver *s, real_t *z, const real_t *r)
 {
 	if (null_handle(s, "cedar_amd_solver_precondition")) return;
-	cedar_amd_pcg_settings p;
-	cedar_amd_default_pcg_settings(&p);
-	if (pcg_refused(s, p, "cedar_amd_solver_precondition")) return;
+	if (pcg_refused(s, pcg_settings_or_default(nullptr), "cedar_amd_solver_precondition")) return;
 	pcg_alloc(s);
 	const Level &L = s->lv[0];
 	hipStream_t st = current_stream();
@@ -1290,16 +1265,7 @@ cedar_amd_planes *cedar_amd_planes_create(int dir, len_t nx, len_t ny, len_t nz,
 	p->L.npts = (size_t)p->L.II * p->L.JJ * p->L.KK;
 	p->host = new cedar_amd_solver;
 	p->host->nd = 3;
-	const char *es = getenv("CEDAR_AMD_PLANE_STREAMS");
-	int S = es ? atoi(es) : 8;
-	S = S < 1 ? 1 : S > 64 ? 64 : S;
-	p->host->pstreams.resize(S);
-	p->host->pevents.resize(S);
-	for (int t = 0; t < S; t++) {
-		CEDAR_HIP_CHECK(hipStreamCreateWithFlags(&p->host->pstreams[t], hipStreamNonBlocking));
-		CEDAR_HIP_CHECK(hipEventCreateWithFlags(&p->host->pevents[t], hipEventDisableTiming));
-	}
-	CEDAR_HIP_CHECK(hipEventCreateWithFlags(&p->host->pfork, hipEventDisableTiming));
+	plane_streams_create(p->host);
 	{
 		Staged sso(so, p->L.npts * nstencil, true, false);
 		p->ps = planes_setup(dir, sso.get(), p->L.II, p->L.JJ, p->L.KK, nstencil, pst, st);
@@ -1333,18 +1299,9 @@ void cedar_amd_planes_destroy(cedar_amd_planes *p)
 float cedar_amd_solver_time_vcycles(cedar_amd_solver *s, real_t *x_dev, const real_t *b_dev, int n)
 {
 	if (null_handle(s, "cedar_amd_solver_time_vcycles")) return 0.f;
-	hipStream_t st = current_stream();
-	hipEvent_t e0, e1;
-	CEDAR_HIP_CHECK(hipEventCreate(&e0));
-	CEDAR_HIP_CHECK(hipEventCreate(&e1));
-	CEDAR_HIP_CHECK(hipEventRecord(e0, st));
-	for (int i = 0; i < n; i++) cycle_dev(s, x_dev, b_dev);
-	CEDAR_HIP_CHECK(hipEventRecord(e1, st));
-	CEDAR_HIP_CHECK(hipEventSynchronize(e1));
-	float ms = 0;
-	CEDAR_HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
-	(void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-	return ms;
+	return timed(current_stream(), [&] {
+		for (int i = 0; i < n; i++) cycle_dev(s, x_dev, b_dev);
+	});
 }
 
 float cedar_amd_solver_time_relax(cedar_amd_solver *s, real_t *x_dev, const real_t *b_dev, int n)
@@ -1352,20 +1309,12 @@ float cedar_amd_solver_time_relax(cedar_amd_solver *s, real_t *x_dev, const real
 	if (null_handle(s, "cedar_amd_solver_time_relax")) return 0.f;
 	hipStream_t st = current_stream();
 	const Level &L = s->lv[0];
-	hipEvent_t e0, e1;
-	CEDAR_HIP_CHECK(hipEventCreate(&e0));
-	CEDAR_HIP_CHECK(hipEventCreate(&e1));
-	CEDAR_HIP_CHECK(hipEventRecord(e0, st));
-	for (int i = 0; i < n; i++) {
-		L.bt_fresh = false; // every timed sweep pays for its own transpose of b (a V(2,1) visit pays two per three sweeps)
-		smooth(s, L, x_dev, b_dev, (i & 1) ? BMG_UP : BMG_DOWN, 1, st);
-	}
-	CEDAR_HIP_CHECK(hipEventRecord(e1, st));
-	CEDAR_HIP_CHECK(hipEventSynchronize(e1));
-	float ms = 0;
-	CEDAR_HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
-	(void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-	return ms;
+	return timed(st, [&] {
+		for (int i = 0; i < n; i++) {
+			L.bt_fresh = false; // every timed sweep pays for its own transpose of b (a V(2,1) visit pays two per three sweeps)
+			smooth(s, L, x_dev, b_dev, (i & 1) ? BMG_UP : BMG_DOWN, 1, st);
+		}
+	});
 }
 
 // n launches of one level-0 transfer / residual kernel: op 1 = residual (res := b - A x), 2 = restriction of res to level 1,
@@ -1376,30 +1325,13 @@ float cedar_amd_solver_time_op(cedar_amd_solver *s, real_t *x_dev, const real_t 
 	if (s->lv.size() < 2 || op < 1 || op > 3) return 0.f;
 	hipStream_t st = current_stream();
 	Level &L = s->lv[0], &K = s->lv[1];
-	const int ibc = s->st.ibc;
-	hipEvent_t e0, e1;
-	CEDAR_HIP_CHECK(hipEventCreate(&e0));
-	CEDAR_HIP_CHECK(hipEventCreate(&e1));
-	CEDAR_HIP_CHECK(hipEventRecord(e0, st));
-	for (int i = 0; i < n; i++) {
-		if (op == 1) residual(s, L, x_dev, b_dev, L.res, st);
-		else if (op == 2) {
-			if (s->nd == 2 && ibc) restrict2_per(L.res, K.b, K.P, L.II, L.JJ, K.II, K.JJ, ibc, st);
-			else if (s->nd == 2) restrict2(L.res, K.b, K.P, L.II, L.JJ, K.II, K.JJ, st, Batch{s->nb, L.npts}, Batch{s->nb, K.npts});
-			else if (ibc) restrict3_per(L.res, K.b, K.P, L.II, L.JJ, L.KK, K.II, K.JJ, K.KK, ibc, st);
-			else restrict3(L.res, K.b, K.P, L.II, L.JJ, L.KK, K.II, K.JJ, K.KK, st);
-		} else {
-			if (s->nd == 2 && ibc) interp_add2_per(x_dev, K.x, L.res, L.A, K.P, K.II, K.JJ, L.II, L.JJ, ibc, st);
-			else if (s->nd == 2) interp_add2(x_dev, K.x, L.res, L.A, K.P, K.II, K.JJ, L.II, L.JJ, st, Batch{s->nb, L.npts}, Batch{s->nb, K.npts});
-			else if (ibc) interp_add3_per(x_dev, K.x, L.A, L.res, K.P, K.II, K.JJ, K.KK, L.II, L.JJ, L.KK, ibc, st);
-			else interp_add3(x_dev, K.x, L.A, L.res, K.P, K.II, K.JJ, K.KK, L.II, L.JJ, L.KK, st);
+	const float ms = timed(st, [&] {
+		for (int i = 0; i < n; i++) {
+			if (op == 1) residual(s, L, x_dev, b_dev, L.res, st);
+			else if (op == 2) restrict_to(s, L, K, L.res, st);
+			else interp_add_from(s, L, K, x_dev, st);
 		}
-	}
-	CEDAR_HIP_CHECK(hipEventRecord(e1, st));
-	CEDAR_HIP_CHECK(hipEventSynchronize(e1));
-	float ms = 0;
-	CEDAR_HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
-	(void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+	});
 	launch_check("cedar_amd_solver_time_op");
 	return ms;
 }

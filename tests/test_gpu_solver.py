@@ -349,3 +349,61 @@ def test_random_small_2d_solvers_follow_the_oracle(capi, oracle, nx, ny, relax, 
     assert len(h) == len(ho)
     np.testing.assert_allclose(h, ho, rtol=1e-9, atol=1e-12)
     assert np.max(np.abs(x - xo)) <= 1e-9 * max(np.max(np.abs(xo)), 1e-300)
+
+
+TIME_OP = {
+    "fe27_17x12x9": (lambda: pb.fe3(17, 12, 9), {}),
+    "poisson7_16x9x10": (lambda: pb.poisson3(16, 9, 10), {}),
+    "fe9_33x20": (lambda: pb.fe2(33, 20), {}),
+    "random9_32x16_per_xy": (lambda: pb.periodic_random_op(32, 16, 5, (True, True), 77), dict(ibc=3)),
+}
+
+
+@pytest.mark.parametrize("name", list(TIME_OP), ids=str)
+def test_time_op_launches_the_level0_kernels_of_the_cycle(capi, name):
+    """cedar_amd_solver_time_op runs one level-0 kernel of the cycle on the handle's own arrays: the residual into level
+    0's res, the restriction of that res into level 1's b, interpolation-and-add from level 1's x onto the caller's x.
+    Each equals the standalone kernel on the same inputs bit for bit (two levels at least, ragged extents; one cycle on
+    another vector in between leaves a non-zero level-1 x behind for the interpolation)."""
+    mk_op, st = TIME_OP[name]
+    so = mk_op()
+    ibc = st.get("ibc", 0)
+    nd = so.ndim - 1
+    K = capi.Kernels()
+    s = capi.Solver(so, **st)
+    assert s.nlevels() >= 2
+    g = so.shape[1:]
+    x, b = pb.uniform(g, 5, -1, 1), pb.uniform(g, 6, -1, 1)
+    dx, db = capi.DeviceArray.from_numpy(x), capi.DeviceArray.from_numpy(b)
+    bits = lambda a: np.ascontiguousarray(a).view(np.int64)
+
+    s.time_op(dx, db, "residual", 1)
+    res = s.array(0, "res")[0]
+    want = np.zeros(g)
+    (K.residual2 if nd == 2 else K.residual3)(so, b, x, want)
+    assert np.array_equal(bits(res), bits(want))
+    assert np.any(res != 0)
+
+    P1 = np.ascontiguousarray(s.array(1, "P"))
+    s.time_op(dx, db, "restrict", 1)
+    q, want = res.copy(), np.zeros(P1.shape[1:])  # the periodic restriction refreshes the ghosts of what it restricts
+    (K.restrict2 if nd == 2 else K.restrict3)(q, want, P1, ibc)
+    assert np.array_equal(bits(s.array(1, "b")[0]), bits(want))
+    assert np.array_equal(bits(s.array(0, "res")[0]), bits(q))
+    assert np.any(want != 0)
+
+    dy = capi.DeviceArray(g)
+    dy.zero()
+    s.vcycle(dy, db)  # level 1's x now holds a coarse correction, level 0's res the residual it came from
+    xc, res = s.array(1, "x")[0].copy(), s.array(0, "res")[0].copy()
+    assert np.any(xc != 0)
+    s.time_op(dx, db, "interp_add", 1)
+    want = x.copy()
+    if nd == 2:
+        K.interp_add2(want, xc, res, so, P1, ibc)
+    else:
+        K.interp_add3(want, xc, so, res, P1, ibc)
+    got = dx.numpy()
+    s.close()
+    assert np.array_equal(bits(got), bits(want))
+    assert not np.array_equal(got, x)
