@@ -778,6 +778,18 @@ void relax3_planes27(const real_t *so, const real_t *qf, real_t *q, const real_t
 	const int nrk = (KK - 2 - kb + 1) / 2;
 	if (II < 3 || JJ < 3 || nrk <= 0) return;
 	const int npairs = (II - 2 + 1) / 2;
+	if (npairs > 512) { // rows too long for the row kernels: whole colours, every plane of the parity with the shell --
+		// also where the face mask leaves the parity without a shell plane (part 1 has done nothing)
+		if (part == 1) return;
+		for (int c = 0; c < 4; c++) {
+			const int jb = (c >> 1) == 0 ? (up ? 0 : 1) : (up ? 1 : 0), ib = (c & 1) == 0 ? (up ? 0 : 1) : (up ? 1 : 0);
+			int ni = (II - 2 - ib + 1) / 2, nj = (JJ - 2 - jb + 1) / 2;
+			if (ni <= 0 || nj <= 0) continue;
+			hipLaunchKernelGGL(relax27_colour, dim3(cap_grid((size_t)ni * nj * nrk, 256)), dim3(256), 0, st,
+			                   A, qf, q, II, JJ, KK, ib, jb, kb);
+		}
+		return;
+	}
 	const int klo = (kb == 0 && (sides & 4)) ? 1 : 0;
 	const int khi = (1 + kb + 2 * (nrk - 1) == KK - 2 && (sides & 8)) ? nrk - 1 : nrk;
 	const int nki = khi - klo > 0 ? khi - klo : 0;
@@ -810,17 +822,7 @@ void relax3_planes27(const real_t *so, const real_t *qf, real_t *q, const real_t
 		if (npairs <= 64) planes_bs<64>(up, A, qf, q, II, JJ, KK, kb, pc[0], pc[1], st);
 		else if (npairs <= 128) planes_bs<128>(up, A, qf, q, II, JJ, KK, kb, pc[0], pc[1], st);
 		else if (npairs <= 256) planes_bs<256>(up, A, qf, q, II, JJ, KK, kb, pc[0], pc[1], st);
-		else if (npairs <= 512) planes_bs<512>(up, A, qf, q, II, JJ, KK, kb, pc[0], pc[1], st);
-		else if (part != 1) { // rows too long for the row kernels: whole colours, everything with the shell
-			for (int c = 0; c < 4; c++) {
-				const int jb = (c >> 1) == 0 ? (up ? 0 : 1) : (up ? 1 : 0), ib = (c & 1) == 0 ? (up ? 0 : 1) : (up ? 1 : 0);
-				int ni = (II - 2 - ib + 1) / 2, nj = (JJ - 2 - jb + 1) / 2;
-				if (ni <= 0 || nj <= 0) continue;
-				hipLaunchKernelGGL(relax27_colour, dim3(cap_grid((size_t)ni * nj * nrk, 256)), dim3(256), 0, st,
-				                   A, qf, q, II, JJ, KK, ib, jb, kb);
-			}
-			break;
-		}
+		else planes_bs<512>(up, A, qf, q, II, JJ, KK, kb, pc[0], pc[1], st);
 	}
 }
 

@@ -216,6 +216,9 @@ ODD_CASES = [
     ("slab-321-rows-plane-fused", (13, 321, 8), (1, 1, 2), 96, 64, {}, "rand27", 0),
     # overlap_min = 4: shell planes / interior planes around the halo on the side stream; level 0 (11, 13, 8), level 1 (6, 7, 4)
     ("slab-odd-nx-ny-overlap", (11, 13, 8), (1, 1, 2), 4, 64, {}, "rand27", 0),
+    # rows of 600 points (300 pairs: the 512-lane row kernels under cedar_amd_relax3_planes; cedar_amd_relax3_masked_ok
+    # refuses more than 512 points, so no level may take the chain): level 0 (600, 16, 16), level 1 (300, 8, 8) gathered
+    ("slab-600-point-rows", (600, 16, 16), (1, 1, 2), 96, 64, FRUN2, "rand27", 0),
     # -- row-class passes asked for outright
     # x split: relax3_fixup on the column next to the neighbour; level 0 (16, 9, 7), level 1 (8, 5, 4) gathered
     ("rowclass-x-odd-ny-nz", (16, 9, 7), (2, 1, 1), 96, 64, NOCHAIN, "rand27", 0),
