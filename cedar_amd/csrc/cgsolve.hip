@@ -4,12 +4,19 @@
 // BMG3_SymStd_SETUP_cg_LU (src/3d/ftn/BMG3_SymStd_SETUP_cg_LU.f90:111-198) and
 // BMG3_SymStd_SOLVE_cg (src/3d/ftn/BMG3_SymStd_SOLVE_cg.f90:100-150), including the
 // LAPACK they call (DPBTRF/DPBTRS, UPLO='U'; system LAPACK in the reference, not
-// vendored).  The coarsest grid holds a few dozen unknowns (16 in 2D, 64 in 3D
-// for every configuration here), far below DPBTRF's blocking threshold, so the
-// published unblocked DPBTF2 / DTBSV recurrences are restated.  The factorisation
-// (set-up, once) runs on one lane in sequential order; the solve (every cycle) runs
-// on one wavefront out of LDS (~10 us), on the device: no PCIe round trip inside
-// the cycle.  The band is packed by the whole workgroup.
+// vendored).  The coarsest grid of a cube holds a few dozen unknowns (16 in 2D, 64
+// in 3D); elongated grids, min_coarse and the gathered levels of the distributed
+// drivers give it thousands (4096 unknowns under a band of 1024 further down).  The
+// published unblocked DPBTF2 / DTBSV recurrences are restated at every size (DPBTRF
+// blocks from a band of 33: agreement with it is to rounding there).  The
+// factorisation (set-up, once) runs on one workgroup of 256 threads, the solve
+// (every cycle) on one wavefront, out of LDS (~10 us) while the factor fits into
+// 60 KiB and out of global memory beyond, on the device: no PCIe round trip inside
+// the cycle.  The band is packed by the whole workgroup.  Both are held bit for bit
+// against the sequential loops, and against the operator, for bands of 3 to 521
+// under 60 to 1560 unknowns -- either side of the 64-lane and 256-thread trips and
+// of the LDS switch, leading dimensions beyond kd + 1, batches of three
+// (tests/test_gpu_coarse_solve.py).
 #include "common.h"
 
 namespace cedar_amd {
