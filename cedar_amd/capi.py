@@ -240,6 +240,19 @@ class Kernels:
         assert nst == 14
         return lib.cedar_amd_relax3_gs_psum(_p(so), _p(qf), _p(q), _p(sor), C.cast(None, P), u(II), u(JJ), u(KK), updown)
 
+    def relax3_op32(self, so, qf, q, sor, updown, frun=0):
+        """27-point sweep on the operator and 1/diag rounded to single precision (cedar_amd_relax3_gs_op32): frun > 0 the
+        partial-sum sweep with that run length, 0 the reference order; returns 1 if the partial-sum path ran, -1 if refused"""
+        nst, KK, JJ, II = so.shape
+        assert nst == 14
+        return lib.cedar_amd_relax3_gs_op32(_p(so), _p(qf), _p(q), _p(sor), C.cast(None, P), u(II), u(JJ), u(KK), updown, int(frun))
+
+    def residual3_op32(self, so, qf, q, res):
+        """27-point residual on the operator rounded to single precision (cedar_amd_residual3_op32); -1 if refused"""
+        nst, KK, JJ, II = so.shape
+        assert nst == 14
+        return lib.cedar_amd_residual3_op32(_p(so), _p(qf), _p(q), _p(res), u(II), u(JJ), u(KK))
+
     def residual3(self, so, qf, q, res):
         nst, KK, JJ, II = so.shape
         lib.BMG3_SymStd_residual(1, 1, int(nst == 4), _p(q), _p(qf), _p(so), _p(res), u(II), u(JJ), u(KK), nst)
@@ -470,6 +483,10 @@ lib.cedar_amd_solver_precondition.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p
 lib.cedar_amd_solver_pcg_many.restype = C.c_int
 lib.cedar_amd_solver_pcg_many.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(PcgSettings), C.c_void_p,
                                           C.POINTER(C.c_int)]
+lib.cedar_amd_solver_use_fp32_operator.restype = C.c_int
+lib.cedar_amd_solver_use_fp32_operator.argtypes = [C.c_void_p, C.c_int]
+lib.cedar_amd_solver_fp32_levels.restype = C.c_int
+lib.cedar_amd_solver_fp32_levels.argtypes = [C.c_void_p]
 
 
 class Solver:
@@ -597,6 +614,15 @@ class Solver:
     def precondition(self, z, r):
         """z = M^-1 r: one cycle from z = 0 (cedar_amd_solver_precondition)"""
         lib.cedar_amd_solver_precondition(self.h, _vp(z), _vp(r))
+
+    def use_fp32_operator(self, min_rows=0):
+        """keep the 27-point operator of the cycle in single precision on every smoothed level with at least min_rows
+        rows (0: the default; cedar_amd_solver_use_fp32_operator).  Returns the number of levels that read a float copy,
+        -1 when the library refuses (the reason is printed, the handle is unchanged)"""
+        return lib.cedar_amd_solver_use_fp32_operator(self.h, int(min_rows))
+
+    def fp32_levels(self):
+        return lib.cedar_amd_solver_fp32_levels(self.h)
 
     def time_vcycles(self, x, b, n):
         return lib.cedar_amd_solver_time_vcycles(self.h, x.ptr, b.ptr, n)

@@ -586,6 +586,82 @@ int cedar_amd_relax3_gs_psum(real_t *so, real_t *qf, real_t *q, real_t *sor, rea
 	return 1;
 }
 
+// ---- the 27-point sweep and residual on a single-precision copy of the operator (include/cedar_amd.h): the copy is
+// built for the call and dropped after it
+namespace {
+
+// temporary float copy (common.h Op3f) of so and sor's reciprocal plane; nullptr = refused (reported)
+float *op32_copy_get(const real_t *so, const real_t *sor_msor, int II, int JJ, int KK, const char *who)
+{
+	char buf[200];
+	if (II < 3 || JJ < 3 || KK < 3 || (II - 2 + 1) / 2 > 512) {
+		snprintf(buf, sizeof(buf), "%s: extents %d x %d x %d (ghosts included) are not served (rows of 1 .. 1024 points); nothing done",
+		         who, II, JJ, KK);
+		report(buf);
+		return nullptr;
+	}
+	hipStream_t st = current_stream();
+	const size_t bytes = ilv32_floats(II, JJ, KK) * sizeof(float);
+	float *c = static_cast<float *>(pool_get(bytes));
+	int *flag = static_cast<int *>(pool_get(sizeof(int))), host = 0;
+	CEDAR_HIP_CHECK(hipMemsetAsync(flag, 0, sizeof(int), st));
+	ilv32_build(so, sor_msor, c, II, JJ, KK, flag, st);
+	CEDAR_HIP_CHECK(hipMemcpyAsync(&host, flag, sizeof(int), hipMemcpyDeviceToHost, st));
+	CEDAR_HIP_CHECK(hipStreamSynchronize(st));
+	pool_put(flag, sizeof(int));
+	if (host) {
+		pool_put(c, bytes);
+		snprintf(buf, sizeof(buf), "%s: an entry of the operator or of 1/diag overflows single precision; nothing done", who);
+		report(buf);
+		return nullptr;
+	}
+	return c;
+}
+
+} // namespace
+
+int cedar_amd_relax3_gs_op32(real_t *so, real_t *qf, real_t *q, real_t *sor, real_t *scratch, len_t ii, len_t jj, len_t kk,
+                             int updown, int frun)
+{
+	const int II = (int)ii, JJ = (int)jj, KK = (int)kk;
+	const size_t P = (size_t)ii * jj * kk;
+	Staged sso(so, P * 14, true, false), sqf(qf, P, true, false), sq(q, P, true, true), ssor(sor, P * 2, true, false);
+	float *c = op32_copy_get(sso.get(), ssor.get() + P, II, JJ, KK, "cedar_amd_relax3_gs_op32");
+	if (!c) return -1;
+	const Op3f A = op3f_ilv(c, II, JJ, KK);
+	hipStream_t st = current_stream();
+	// the run length as relax3_psum_frun applies CEDAR_AMD_FRUN: a plane needs at least four runs
+	const int run = (frun > 0 && JJ - 2 >= 4 * frun) ? frun : 0;
+	int took = 0;
+	if (relax3_psum_ok(II, JJ, KK, run)) {
+		real_t *T = scratch && is_device_ptr(scratch) ? scratch : static_cast<real_t *>(pool_get(P * sizeof(real_t)));
+		relax3_gs27_psum(A, sqf.get(), sq.get(), T, II, JJ, KK, updown, run, st);
+		CEDAR_HIP_CHECK(hipStreamSynchronize(st));
+		if (T != scratch) pool_put(T, P * sizeof(real_t));
+		took = 1;
+	} else {
+		relax3_gs27_op(A, sqf.get(), sq.get(), II, JJ, KK, updown, st); // reference order: plane-fused or row kernels
+		CEDAR_HIP_CHECK(hipStreamSynchronize(st));
+	}
+	pool_put(c, ilv32_floats(II, JJ, KK) * sizeof(float));
+	return took;
+}
+
+int cedar_amd_residual3_op32(real_t *so, real_t *qf, real_t *q, real_t *res, len_t ii, len_t jj, len_t kk)
+{
+	const int II = (int)ii, JJ = (int)jj, KK = (int)kk;
+	const size_t P = (size_t)ii * jj * kk;
+	Staged sso(so, P * 14, true, false), sqf(qf, P, true, false), sq(q, P, true, false), sres(res, P, true, true);
+	// 1/diag is not read by the residual: the copy's reciprocal row is filled from the operator's centre plane
+	float *c = op32_copy_get(sso.get(), sso.get(), II, JJ, KK, "cedar_amd_residual3_op32");
+	if (!c) return -1;
+	hipStream_t st = current_stream();
+	residual27_op(op3f_ilv(c, II, JJ, KK), sqf.get(), sq.get(), sres.get(), II, JJ, KK, st);
+	CEDAR_HIP_CHECK(hipStreamSynchronize(st));
+	pool_put(c, ilv32_floats(II, JJ, KK) * sizeof(float));
+	return 0;
+}
+
 void cedar_amd_relax3_colour7(real_t *so, real_t *qf, real_t *q, real_t *sor, len_t ii, len_t jj, len_t kk, int pts)
 {
 	size_t P = (size_t)ii * jj * kk;

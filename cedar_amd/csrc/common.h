@@ -75,6 +75,29 @@ static inline Op3 op3_ilv(const real_t *a, int II, int JJ, int KK)
 	(void)KK;
 	return Op3{a, RS, NS3 * RS, NS3 * RS * (size_t)JJ, a + ILV_SOR * RS, NS3 * RS, NS3 * RS * (size_t)JJ};
 }
+// The row-interleaved copy with the entries kept in single precision (cedar_amd_solver_use_fp32_operator; DESIGN.md
+// section 12): same 16 slot-rows per grid row, rows padded to a multiple of 32 floats (every slot-row on a 128-byte
+// line).  The kernels promote an entry to double when they load it -- exact -- so a sweep on this view is the FP64
+// sweep on the operator rounded to float, bit for bit, at 84 instead of 136 bytes per point.
+struct Op3f {
+	const float *so;
+	size_t SS, SJ, SK;
+	const float *sor;
+	size_t rSJ, rSK;
+};
+// pair of floats at any element offset: the [i]-pattern pairs start at odd offsets (4-byte aligned dwordx2)
+typedef float f2u __attribute__((ext_vector_type(2), aligned(4)));
+static inline size_t ilv32_row_stride(int II) { return ((size_t)II + 31) / 32 * 32; }
+static inline size_t ilv32_floats(int II, int JJ, int KK) { return ilv32_row_stride(II) * NS3 * (size_t)JJ * KK; }
+static inline Op3f op3f_ilv(const float *a, int II, int JJ, int KK)
+{
+	const size_t RS = ilv32_row_stride(II);
+	(void)KK;
+	return Op3f{a, RS, NS3 * RS, NS3 * RS * (size_t)JJ, a + ILV_SOR * RS, NS3 * RS, NS3 * RS * (size_t)JJ};
+}
+// build it (round to nearest even); *overflow (device int, cleared by the caller) is set to 1 when a finite entry of the
+// operator or of 1/diag rounds to +-inf (relax3d.hip)
+void ilv32_build(const real_t *so, const real_t *sor_msor, float *ilv, int II, int JJ, int KK, int *overflow, hipStream_t st);
 // register / drop a row-interleaved solve copy for an operator outside a resident solver (relax3d.hip); prepare
 // returns 1 when a copy was built (levels with at least min_rows rows that fit the card's free memory)
 int relax3_prepare(const real_t *so, const real_t *sor, int II, int JJ, int KK, int min_rows, hipStream_t st);
@@ -102,6 +125,10 @@ void relax3_gs(const real_t *so, const real_t *qf, real_t *q, const real_t *sor,
 void relax3_gs27_op(const Op3 &A, const real_t *qf, real_t *q, int II, int JJ, int KK, int updown, hipStream_t st,
                     real_t *T = nullptr);
 void residual27_op(const Op3 &A, const real_t *qf, const real_t *q, real_t *res, int II, int JJ, int KK, hipStream_t st);
+// the same kernels on the single-precision view (rows of at most 1024 points: the row kernels only)
+void relax3_gs27_op(const Op3f &A, const real_t *qf, real_t *q, int II, int JJ, int KK, int updown, hipStream_t st,
+                    real_t *T = nullptr);
+void residual27_op(const Op3f &A, const real_t *qf, const real_t *q, real_t *res, int II, int JJ, int KK, hipStream_t st);
 void relax3_planes27(const real_t *so, const real_t *qf, real_t *q, const real_t *sor,
                      int II, int JJ, int KK, int kb, int up, int part, hipStream_t st);
 void relax3_pass27(const real_t *so, const real_t *qf, real_t *q, const real_t *sor,
@@ -210,6 +237,7 @@ void galerkin3(const real_t *so, real_t *soc, const real_t *ci, int IIF, int JJF
 // that PyTorch loads first (the multi-GPU path always imports torch) it left non-zero bit patterns in the cleared
 // arrays (profiles/r01_memset_under_torch_runtime.log)
 void zero_fill(real_t *p, size_t n, hipStream_t st);
+void vec_add(real_t *x, const real_t *z, size_t n, hipStream_t st); // x += z
 // lines.hip
 void setup_lines_x(const real_t *so, real_t *sor, int II, int JJ, hipStream_t st, int fold = 0);
 void setup_lines_y(const real_t *so, real_t *sor, int II, int JJ, hipStream_t st, int fold = 0);

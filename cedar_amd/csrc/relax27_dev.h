@@ -63,6 +63,17 @@ __device__ __forceinline__ void ldpair(const real_t *__restrict__ p, bool two, r
 	}
 }
 
+// the same from a single-precision operator row (common.h Op3f): an 8-byte pair, promoted to double -- exact
+__device__ __forceinline__ void ldpair(const float *__restrict__ p, bool two, real_t &a, real_t &b)
+{
+	if (two) {
+		f2u v = *reinterpret_cast<const f2u *>(p);
+		a = (real_t)v.x; b = (real_t)v.y;
+	} else {
+		a = (real_t)p[0]; b = 0.0;
+	}
+}
+
 // operator rows are used by exactly one workgroup of a launch: stream them past the caches
 // (non-temporal) so that the q rows, which neighbouring workgroups share, stay resident
 template <bool NT>
@@ -74,6 +85,18 @@ __device__ __forceinline__ void ldpair_so(const real_t *__restrict__ p, bool two
 		a = v.x; b = v.y;
 	} else {
 		a = __builtin_nontemporal_load(p); b = 0.0;
+	}
+}
+
+template <bool NT>
+__device__ __forceinline__ void ldpair_so(const float *__restrict__ p, bool two, real_t &a, real_t &b)
+{
+	if (!NT) { ldpair(p, two, a, b); return; }
+	if (two) {
+		f2u v = __builtin_nontemporal_load(reinterpret_cast<const f2u *>(p));
+		a = (real_t)v.x; b = (real_t)v.y;
+	} else {
+		a = (real_t)__builtin_nontemporal_load(p); b = 0.0;
 	}
 }
 
@@ -90,11 +113,12 @@ __device__ __forceinline__ void ldpair_so(const real_t *__restrict__ p, bool two
 // the caches and the timing shows what removing that traffic would be worth.  8 = the k-pair walk of relax27_plane.
 #define WI_SLOT(slot) ((size_t)(((WI & 4) && ((slot) == KB || (slot) >= KBW)) ? KPW : (slot)))
 // the operator part: the 26 coefficients of both points (shared by every right-hand side of a batch, many3d.hip)
-template <bool NT, bool NTP = NT, bool NTO = NT, int WI = 0>
-__device__ __forceinline__ void load_coef27(const Op3 &A, size_t rowA, int ie, int io, bool two, C27 &ce, C27 &co)
+// OP: the operator view, Op3 or the single-precision Op3f (entries promoted to double by the pair loads)
+template <bool NT, bool NTP = NT, bool NTO = NT, int WI = 0, typename OP = Op3>
+__device__ __forceinline__ void load_coef27(const OP &A, size_t rowA, int ie, int io, bool two, C27 &ce, C27 &co)
 {
 	// operator entry (slot, i, j+dj, k+dk) = A.so[slot*A.SS + rowA + dj*A.SJ + dk*A.SK + i]
-	const real_t *__restrict__ so = A.so;
+	const auto *__restrict__ so = A.so;
 	const size_t PS = A.SS, aj = A.SJ, ak = (WI & 2) ? 0 : A.SK;
 	// ---- [i]-pattern streams: (value at ie, value at io)
 #define LD_I_(N, slot, off, fe, fo)                                                    \
@@ -164,8 +188,8 @@ __device__ __forceinline__ void load_vec27(const real_t *__restrict__ qf, const 
 		}
 }
 
-template <bool NT, bool NTP = NT, bool NTO = NT, int WI = 0>
-__device__ __forceinline__ void load_pair27(const Op3 &A, const real_t *__restrict__ qf,
+template <bool NT, bool NTP = NT, bool NTO = NT, int WI = 0, typename OP = Op3>
+__device__ __forceinline__ void load_pair27(const OP &A, const real_t *__restrict__ qf,
                                             const real_t *__restrict__ q, size_t rowA, size_t row, size_t sj, size_t sk,
                                             int ie, int io, bool two, C27 &ce, C27 &co,
                                             real_t (&qe)[3][3][3], real_t (&qo)[3][3][3], real_t &qfe, real_t &qfo)
@@ -196,8 +220,8 @@ __device__ __forceinline__ void skip27_lane(unsigned skm, int p, int P, bool &sk
 //   point of the second colour takes the fresh first point from LDS, and the two ghost cells are written at the end.
 //   MSK / skm: points of the row that were relaxed AHEAD of this launch (boundary-first chain of a rank grid with an
 //   x / y split, dist3.cpp) keep their value -- see skip27_lane.
-template <int BS, bool EFIRST, bool NT, bool NTP = NT, int WI = 0, bool PERX = false, bool MSK = false>
-__device__ __forceinline__ void relax27_row_task(const Op3 &A, const real_t *__restrict__ qf,
+template <int BS, bool EFIRST, bool NT, bool NTP = NT, int WI = 0, bool PERX = false, bool MSK = false, typename OP = Op3>
+__device__ __forceinline__ void relax27_row_task(const OP &A, const real_t *__restrict__ qf,
                                                  real_t *__restrict__ q, int II, size_t sj, size_t sk,
                                                  size_t j, size_t k, real_t *xch, unsigned skm = 0)
 {

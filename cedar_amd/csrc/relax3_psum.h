@@ -11,6 +11,9 @@ bool relax3_psum_ok(int II, int JJ, int KK, int frun);
 bool relax3_psum_wanted(int II, int JJ, int KK); // the level takes it by default (CEDAR_AMD_PSUM, run length, row length)
 void relax3_gs27_psum(const Op3 &A, const real_t *qf, real_t *q, real_t *T, int II, int JJ, int KK, int updown, int frun,
                       hipStream_t st);
+// the same sweep on the single-precision operator view (common.h Op3f): T, the vectors and the arithmetic stay FP64
+void relax3_gs27_psum(const Op3f &A, const real_t *qf, real_t *q, real_t *T, int II, int JJ, int KK, int updown, int frun,
+                      hipStream_t st);
 // Points of a k-parity of planes that a launch leaves as they are: relaxed ahead of it by the boundary-first chain of a
 // rank grid with an x / y split (dist3.cpp).  Per row class of the walk a mask over the first and the last four points
 // of a row (relax27_dev.h skip27_lane), and up to three whole rows.

@@ -22,6 +22,7 @@
 #include "relax27_dev.h"
 #include "relax3_psum.h"
 #include <map>
+#include <type_traits>
 
 namespace cedar_amd {
 
@@ -80,6 +81,35 @@ void ilv_build(const real_t *so, const real_t *sor_msor, real_t *ilv, int II, in
 {
 	hipLaunchKernelGGL(ilv_build_kernel, dim3((unsigned)((size_t)JJ * KK)), dim3(256), 0, st, so, sor_msor, ilv, II, JJ, KK,
 	                   ilv_row_stride(II));
+}
+
+// the single-precision copy (common.h Op3f): same walk, entries rounded to nearest even.  A finite entry that leaves
+// float's range raises *overflow (an ordinary store of 1: every writer stores the same value); the caller refuses the copy.
+__global__ __launch_bounds__(256) void ilv32_build_kernel(const real_t *__restrict__ so, const real_t *__restrict__ sor,
+                                                           float *__restrict__ out, int II, int JJ, int KK, size_t RS,
+                                                           int *__restrict__ overflow)
+{
+	const size_t row = blockIdx.x; // j + JJ*k
+	const size_t PS = (size_t)II * JJ * KK;
+	const real_t *src = so + row * (size_t)II;
+	float *dst = out + row * (size_t)NS3 * RS;
+	bool bad = false;
+	for (int s = 0; s < NS3; s++) {
+		const real_t *from = s < 14 ? src + (size_t)s * PS : (s == ILV_SOR ? sor + row * (size_t)II : nullptr);
+		for (size_t i = threadIdx.x; i < RS; i += 256) {
+			const real_t v = (from && i < (size_t)II) ? from[i] : 0.0;
+			const float f = (float)v; // v_cvt_f32_f64: round to nearest even
+			bad = bad || (isinf(f) && !isinf(v));
+			dst[(size_t)s * RS + i] = f;
+		}
+	}
+	if (bad) *overflow = 1;
+}
+
+void ilv32_build(const real_t *so, const real_t *sor_msor, float *ilv, int II, int JJ, int KK, int *overflow, hipStream_t st)
+{
+	hipLaunchKernelGGL(ilv32_build_kernel, dim3((unsigned)((size_t)JJ * KK)), dim3(256), 0, st, so, sor_msor, ilv, II, JJ, KK,
+	                   ilv32_row_stride(II), overflow);
 }
 
 // Solve copies registered for operators that live outside a resident solver (the per-rank arrays of the
@@ -200,8 +230,8 @@ __global__ void relax27_colour(const Op3 A, const real_t *__restrict__ qf, real_
 
 // fast path: one workgroup = one grid row, both i-colours.  Rows j = j0 + jstep*jr, jr < nrj, of the
 // planes k = 1 + kb + 2*(kr + kr0), kr < nrk.
-template <int BS, bool EFIRST, bool NT, bool PERX = false>
-__global__ __launch_bounds__(BS) void relax27_rows(const Op3 A, const real_t *__restrict__ qf,
+template <int BS, bool EFIRST, bool NT, bool PERX = false, typename OP = Op3>
+__global__ __launch_bounds__(BS) void relax27_rows(const OP A, const real_t *__restrict__ qf,
                                                     real_t *__restrict__ q,
                                                     int II, int JJ, int KK, int j0, int jstep, int kb, int nrj, int nrk,
                                                     TileShape ts, int kr0)
@@ -251,8 +281,8 @@ __global__ __launch_bounds__(BS) void relax27_rows_shell(const Op3 A, const real
 // neighbours in different workgroups: it is left to a small second launch (relax27_rows over those
 // rows, j0 = first such row, jstep = 2*frun).  Same arithmetic per point, same values read =>
 // results identical to the four-launch order.
-template <int BS, bool EFIRST, bool NT, int WI = 0>
-__global__ __launch_bounds__(BS) void relax27_plane(const Op3 A, const real_t *__restrict__ qf,
+template <int BS, bool EFIRST, bool NT, int WI = 0, typename OP = Op3>
+__global__ __launch_bounds__(BS) void relax27_plane(const OP A, const real_t *__restrict__ qf,
                                                      real_t *__restrict__ q,
                                                      int II, int JJ, int KK, int jbF, int kb, int nrk, int frun, int nrun,
                                                      int kr0)
@@ -335,8 +365,8 @@ __global__ void relax7_colour(const real_t *__restrict__ so, const real_t *__res
 // 27-point residual with the same lane layout as the relax row kernel: lane p owns the pair
 // (2p+1, 2p+2) of its row, every stream is read with 16-byte loads, one 16-byte store.
 // (BMG3_SymStd_residual.f90:77-104; bit-identical term order.)
-template <int BS, bool NT>
-__global__ __launch_bounds__(BS) void residual27_rows(const Op3 A, const real_t *__restrict__ qf,
+template <int BS, bool NT, typename OP = Op3>
+__global__ __launch_bounds__(BS) void residual27_rows(const OP A, const real_t *__restrict__ qf,
                                                        const real_t *__restrict__ q, real_t *__restrict__ res,
                                                        int II, int JJ, int KK, unsigned nblk, TileShape ts)
 {
@@ -365,18 +395,29 @@ __global__ __launch_bounds__(BS) void residual27_rows(const Op3 A, const real_t 
 	}
 }
 
-void residual27_op(const Op3 &A, const real_t *qf, const real_t *q, real_t *res, int II, int JJ, int KK, hipStream_t st)
+template <typename OP>
+static void residual27_op_t(const OP &A, const real_t *qf, const real_t *q, real_t *res, int II, int JJ, int KK, hipStream_t st)
 {
-	const Op3 so = A;
+	const OP so = A;
 	const TileShape ts = tile_shape_resid();
 	unsigned nrows = tile_blocks((unsigned)(JJ - 2), (unsigned)(KK - 2), ts);
 	const int npairs = (II - 2 + 1) / 2;
 	const char *e = getenv("CEDAR_AMD_RESID_NT");
 	const bool nt = e ? atoi(e) != 0 : false;
-	if (npairs <= 64) hipLaunchKernelGGL((residual27_rows<64, false>), dim3(xcd_grid(nrows)), dim3(64), 0, st, so, qf, q, res, II, JJ, KK, nrows, ts);
-	else if (npairs <= 128) hipLaunchKernelGGL((residual27_rows<128, false>), dim3(xcd_grid(nrows)), dim3(128), 0, st, so, qf, q, res, II, JJ, KK, nrows, ts);
-	else if (nt) hipLaunchKernelGGL((residual27_rows<256, true>), dim3(xcd_grid(nrows)), dim3(256), 0, st, so, qf, q, res, II, JJ, KK, nrows, ts);
-	else hipLaunchKernelGGL((residual27_rows<256, false>), dim3(xcd_grid(nrows)), dim3(256), 0, st, so, qf, q, res, II, JJ, KK, nrows, ts);
+	if (npairs <= 64) hipLaunchKernelGGL((residual27_rows<64, false, OP>), dim3(xcd_grid(nrows)), dim3(64), 0, st, so, qf, q, res, II, JJ, KK, nrows, ts);
+	else if (npairs <= 128) hipLaunchKernelGGL((residual27_rows<128, false, OP>), dim3(xcd_grid(nrows)), dim3(128), 0, st, so, qf, q, res, II, JJ, KK, nrows, ts);
+	else if (nt) hipLaunchKernelGGL((residual27_rows<256, true, OP>), dim3(xcd_grid(nrows)), dim3(256), 0, st, so, qf, q, res, II, JJ, KK, nrows, ts);
+	else hipLaunchKernelGGL((residual27_rows<256, false, OP>), dim3(xcd_grid(nrows)), dim3(256), 0, st, so, qf, q, res, II, JJ, KK, nrows, ts);
+}
+
+void residual27_op(const Op3 &A, const real_t *qf, const real_t *q, real_t *res, int II, int JJ, int KK, hipStream_t st)
+{
+	residual27_op_t(A, qf, q, res, II, JJ, KK, st);
+}
+
+void residual27_op(const Op3f &A, const real_t *qf, const real_t *q, real_t *res, int II, int JJ, int KK, hipStream_t st)
+{
+	residual27_op_t(A, qf, q, res, II, JJ, KK, st);
 }
 
 void residual27_fast(const real_t *so, const real_t *qf, const real_t *q, real_t *res, int II, int JJ, int KK, hipStream_t st)
@@ -393,8 +434,8 @@ static inline unsigned cap_grid(size_t n, unsigned bs)
 }
 
 // rows j = j0 + jstep*jr (jr < nrj) of the planes kr0 .. kr0+nrk-1 (in units of planes of parity kb)
-template <int BS>
-static void launch_rows_at(bool efirst, const Op3 &A, const real_t *qf, real_t *q,
+template <int BS, typename OP>
+static void launch_rows_at(bool efirst, const OP &A, const real_t *qf, real_t *q,
                            int II, int JJ, int KK, int j0, int jstep, int nrj, int kb, int nrk, hipStream_t st, int kr0 = 0)
 {
 	if (nrj <= 0 || nrk <= 0) return;
@@ -403,11 +444,11 @@ static void launch_rows_at(bool efirst, const Op3 &A, const real_t *qf, real_t *
 	// non-temporal operator loads: measured -1.8 % per launch at 512^3 (profiles/r01_experiment_nt_loads.log)
 	static const bool nt = getenv("CEDAR_AMD_NT") ? atoi(getenv("CEDAR_AMD_NT")) != 0 : true;
 	if (efirst) {
-		if (nt) hipLaunchKernelGGL((relax27_rows<BS, true, true>), dim3(grid), dim3(BS), 0, st, A, qf, q, II, JJ, KK, j0, jstep, kb, nrj, nrk, ts, kr0);
-		else hipLaunchKernelGGL((relax27_rows<BS, true, false>), dim3(grid), dim3(BS), 0, st, A, qf, q, II, JJ, KK, j0, jstep, kb, nrj, nrk, ts, kr0);
+		if (nt) hipLaunchKernelGGL((relax27_rows<BS, true, true, false, OP>), dim3(grid), dim3(BS), 0, st, A, qf, q, II, JJ, KK, j0, jstep, kb, nrj, nrk, ts, kr0);
+		else hipLaunchKernelGGL((relax27_rows<BS, true, false, false, OP>), dim3(grid), dim3(BS), 0, st, A, qf, q, II, JJ, KK, j0, jstep, kb, nrj, nrk, ts, kr0);
 	} else {
-		if (nt) hipLaunchKernelGGL((relax27_rows<BS, false, true>), dim3(grid), dim3(BS), 0, st, A, qf, q, II, JJ, KK, j0, jstep, kb, nrj, nrk, ts, kr0);
-		else hipLaunchKernelGGL((relax27_rows<BS, false, false>), dim3(grid), dim3(BS), 0, st, A, qf, q, II, JJ, KK, j0, jstep, kb, nrj, nrk, ts, kr0);
+		if (nt) hipLaunchKernelGGL((relax27_rows<BS, false, true, false, OP>), dim3(grid), dim3(BS), 0, st, A, qf, q, II, JJ, KK, j0, jstep, kb, nrj, nrk, ts, kr0);
+		else hipLaunchKernelGGL((relax27_rows<BS, false, false, false, OP>), dim3(grid), dim3(BS), 0, st, A, qf, q, II, JJ, KK, j0, jstep, kb, nrj, nrk, ts, kr0);
 	}
 }
 
@@ -425,8 +466,8 @@ static void launch_rows_perx(bool efirst, const Op3 &A, const real_t *qf, real_t
 }
 
 // the rows of class (jb,kb)
-template <int BS>
-static void launch_rows(bool efirst, const Op3 &A, const real_t *qf, real_t *q,
+template <int BS, typename OP>
+static void launch_rows(bool efirst, const OP &A, const real_t *qf, real_t *q,
                         int II, int JJ, int KK, int jb, int kb, hipStream_t st)
 {
 	launch_rows_at<BS>(efirst, A, qf, q, II, JJ, KK, 1 + jb, 2, (JJ - 2 - jb + 1) / 2, kb, (KK - 2 - kb + 1) / 2, st);
@@ -434,8 +475,8 @@ static void launch_rows(bool efirst, const Op3 &A, const real_t *qf, real_t *q,
 
 // plane-fused pass over the planes of parity kb: F rows (parity jbF) and the S rows between them in
 // one launch, the S rows between two workgroups' runs in a second small one (see relax27_plane)
-template <int BS>
-static void launch_plane(bool efirst, const Op3 &A, const real_t *qf, real_t *q,
+template <int BS, typename OP>
+static void launch_plane(bool efirst, const OP &A, const real_t *qf, real_t *q,
                          int II, int JJ, int KK, int jbF, int kb, int frun, hipStream_t st, int kr0 = 0, int nrk_sub = -1)
 {
 	const int nF = (JJ - 2 - jbF + 1) / 2;
@@ -444,7 +485,7 @@ static void launch_plane(bool efirst, const Op3 &A, const real_t *qf, real_t *q,
 	const int nrun = (nF + frun - 1) / frun;
 	static const bool nt = getenv("CEDAR_AMD_NT") ? atoi(getenv("CEDAR_AMD_NT")) != 0 : true;
 	const unsigned grid = xcd_grid((unsigned)nrk * (unsigned)nrun);
-	if (BS == 256) { // experiments: CEDAR_AMD_WHATIF=1..7 (see load_pair27), plane-fused launch only
+	if constexpr (BS == 256 && std::is_same<OP, Op3>::value) { // experiments: CEDAR_AMD_WHATIF=1..7 (see load_pair27), plane-fused launch only
 		const char *ew = getenv("CEDAR_AMD_WHATIF");
 		const int wi = ew ? atoi(ew) : 0;
 #define WI_CASE(W)                                                                                                          \
@@ -460,11 +501,11 @@ static void launch_plane(bool efirst, const Op3 &A, const real_t *qf, real_t *q,
 #undef WI_CASE
 	}
 	if (efirst) {
-		if (nt) hipLaunchKernelGGL((relax27_plane<BS, true, true>), dim3(grid), dim3(BS), 0, st, A, qf, q, II, JJ, KK, jbF, kb, nrk, frun, nrun, kr0);
-		else hipLaunchKernelGGL((relax27_plane<BS, true, false>), dim3(grid), dim3(BS), 0, st, A, qf, q, II, JJ, KK, jbF, kb, nrk, frun, nrun, kr0);
+		if (nt) hipLaunchKernelGGL((relax27_plane<BS, true, true, 0, OP>), dim3(grid), dim3(BS), 0, st, A, qf, q, II, JJ, KK, jbF, kb, nrk, frun, nrun, kr0);
+		else hipLaunchKernelGGL((relax27_plane<BS, true, false, 0, OP>), dim3(grid), dim3(BS), 0, st, A, qf, q, II, JJ, KK, jbF, kb, nrk, frun, nrun, kr0);
 	} else {
-		if (nt) hipLaunchKernelGGL((relax27_plane<BS, false, true>), dim3(grid), dim3(BS), 0, st, A, qf, q, II, JJ, KK, jbF, kb, nrk, frun, nrun, kr0);
-		else hipLaunchKernelGGL((relax27_plane<BS, false, false>), dim3(grid), dim3(BS), 0, st, A, qf, q, II, JJ, KK, jbF, kb, nrk, frun, nrun, kr0);
+		if (nt) hipLaunchKernelGGL((relax27_plane<BS, false, true, 0, OP>), dim3(grid), dim3(BS), 0, st, A, qf, q, II, JJ, KK, jbF, kb, nrk, frun, nrun, kr0);
+		else hipLaunchKernelGGL((relax27_plane<BS, false, false, 0, OP>), dim3(grid), dim3(BS), 0, st, A, qf, q, II, JJ, KK, jbF, kb, nrk, frun, nrun, kr0);
 	}
 	// S rows between runs: jbF = 0: j = 2 frun (r+1); jbF = 1: j = 1 + 2 frun (r+1), r = 0 .. nrun-2
 	launch_rows_at<BS>(efirst, A, qf, q, II, JJ, KK, (jbF ? 1 : 0) + 2 * frun, 2 * frun, nrun - 1, kb, nrk, st, kr0);
@@ -879,7 +920,8 @@ bool relax3_psum_wanted(int II, int JJ, int KK)
 	return relax3_psum_ok(II, JJ, KK, relax3_psum_frun(JJ));
 }
 
-void relax3_gs27_op(const Op3 &A, const real_t *qf, real_t *q, int II, int JJ, int KK, int updown, hipStream_t st, real_t *T)
+template <typename OP>
+static void relax3_gs27_op_t(const OP &A, const real_t *qf, real_t *q, int II, int JJ, int KK, int updown, hipStream_t st, real_t *T)
 {
 	if (II < 3 || JJ < 3 || KK < 3) return;
 	const char *ew0 = getenv("CEDAR_AMD_WHATIF"), *ec0 = getenv("CEDAR_AMD_KCHUNK");
@@ -933,7 +975,7 @@ void relax3_gs27_op(const Op3 &A, const real_t *qf, real_t *q, int II, int JJ, i
 				else if (npairs <= 256) launch_rows<256>(up, A, qf, q, II, JJ, KK, jb, kb, st);
 				else launch_rows<512>(up, A, qf, q, II, JJ, KK, jb, kb, st);
 			}
-		} else {
+		} else if constexpr (std::is_same<OP, Op3>::value) { // (the single-precision view is kept for the row kernels only)
 			for (int c = 0; c < 8; c++) {
 				int pts = up ? c : 7 - c;
 				int ib = pts & 1, jb = (pts >> 1) & 1, kb = (pts >> 2) & 1;
@@ -944,6 +986,16 @@ void relax3_gs27_op(const Op3 &A, const real_t *qf, real_t *q, int II, int JJ, i
 			}
 		}
 	}
+}
+
+void relax3_gs27_op(const Op3 &A, const real_t *qf, real_t *q, int II, int JJ, int KK, int updown, hipStream_t st, real_t *T)
+{
+	relax3_gs27_op_t(A, qf, q, II, JJ, KK, updown, st, T);
+}
+
+void relax3_gs27_op(const Op3f &A, const real_t *qf, real_t *q, int II, int JJ, int KK, int updown, hipStream_t st, real_t *T)
+{
+	relax3_gs27_op_t(A, qf, q, II, JJ, KK, updown, st, T);
 }
 
 void relax3_gs(const real_t *so, const real_t *qf, real_t *q, const real_t *sor,

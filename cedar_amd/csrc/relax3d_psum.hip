@@ -121,8 +121,8 @@ struct PsumLds {
 //   ISF: an F row of the walk -- the first contributor of the targets j and j+1 (assign), the second of j-1 (add);
 //        an S row adds to all three and completes the targets j-1 and j, which are stored if lo+1 <= row <= hi-1.
 //   stU / stD: the B plane above / below takes partial sums (it is not next to a ghost plane)
-template <int BS, bool EFIRST, bool NT>
-__device__ __forceinline__ void relax27_row_task_A(const Op3 &A, const real_t *__restrict__ qf, real_t *__restrict__ q,
+template <int BS, bool EFIRST, bool NT, typename OP = Op3>
+__device__ __forceinline__ void relax27_row_task_A(const OP &A, const real_t *__restrict__ qf, real_t *__restrict__ q,
                                                    real_t *__restrict__ T, int II, size_t sj, size_t sk, size_t j, size_t k,
                                                    PsumLds<BS> &S, int t, bool isf, int lo, int hi, bool stU, bool stD,
                                                    unsigned skm)
@@ -190,7 +190,7 @@ __device__ __forceinline__ void relax27_row_task_A(const Op3 &A, const real_t *_
 	const real_t se = e_new, so_ = o_ok ? o_new : ghostR;
 	const bool last_o = o_ok && io == II - 2; // the right ghost column is this lane's "next" source
 	real_t own_e[6], own_o[6];
-	const real_t *__restrict__ sop = A.so;
+	const auto *__restrict__ sop = A.so;
 	const size_t PS = A.SS, aj = A.SJ, ak = A.SK;
 	if (e_ok) {
 #define GROUP(SIDE, DJ)                                                                                           \
@@ -263,8 +263,8 @@ __device__ __forceinline__ void relax27_row_task_A(const Op3 &A, const real_t *_
 }
 
 // A launch: the plane-fused walk of relax27_plane over the planes of the first k-parity, with the partial sums
-template <int BS, bool EFIRST, bool NT>
-__global__ __launch_bounds__(BS) void relax27_planeA(const Op3 A, const real_t *__restrict__ qf, real_t *__restrict__ q,
+template <int BS, bool EFIRST, bool NT, typename OP = Op3>
+__global__ __launch_bounds__(BS) void relax27_planeA(const OP A, const real_t *__restrict__ qf, real_t *__restrict__ q,
                                                       real_t *__restrict__ T, int II, int JJ, int KK, int kb, int kr0,
                                                       int nrk, int nbr, PsumGeom gm, PsumSkip skp)
 {
@@ -308,8 +308,8 @@ __global__ __launch_bounds__(BS) void relax27_planeA(const Op3 A, const real_t *
 
 // B task: row (j,k) of a plane of the second k-parity from its partial sums.  Term order: qf, the eight in-plane terms
 // in the reference's order (relax_GS.f90:104-112), then Tb, then Tt.
-template <int BS, bool EFIRST, bool NT>
-__device__ __forceinline__ void relax27_row_task_B(const Op3 &A, const real_t *__restrict__ qf, real_t *__restrict__ q,
+template <int BS, bool EFIRST, bool NT, typename OP = Op3>
+__device__ __forceinline__ void relax27_row_task_B(const OP &A, const real_t *__restrict__ qf, real_t *__restrict__ q,
                                                    const real_t *__restrict__ T, int II, size_t sj, size_t sk, size_t j,
                                                    size_t k, real_t *xch, unsigned skm)
 {
@@ -319,7 +319,7 @@ __device__ __forceinline__ void relax27_row_task_B(const Op3 &A, const real_t *_
 	const bool e_ok = ie <= II - 2;
 	const bool o_ok = io <= II - 2;
 	const bool two = io + 1 <= II - 1;
-	const real_t *__restrict__ so = A.so;
+	const auto *__restrict__ so = A.so;
 	const size_t PS = A.SS, aj = A.SJ;
 
 	real_t pw_e = 0, pw_o = 0, ps_e = 0, ps_o = 0, psw_e = 0, psw_o = 0, pnwn_e = 0, pnwn_o = 0, psn_e = 0, psn_o = 0;
@@ -419,8 +419,8 @@ __device__ __forceinline__ void relax27_row_task_B(const Op3 &A, const real_t *_
 
 // B launch: the walk over the planes kr0 .. kr0+nrk-1 of the second k-parity; only rows with complete partial sums
 // (the others were / will be relaxed by relax27_rows_sel in the reference order)
-template <int BS, bool EFIRST, bool NT>
-__global__ __launch_bounds__(BS) void relax27_planeB(const Op3 A, const real_t *__restrict__ qf, real_t *__restrict__ q,
+template <int BS, bool EFIRST, bool NT, typename OP = Op3>
+__global__ __launch_bounds__(BS) void relax27_planeB(const OP A, const real_t *__restrict__ qf, real_t *__restrict__ q,
                                                       const real_t *__restrict__ T, int II, int JJ, int KK, int kb, int kr0,
                                                       int nrk, PsumGeom gm, PsumSkip skp)
 {
@@ -462,8 +462,8 @@ __global__ __launch_bounds__(BS) void relax27_planeB(const Op3 A, const real_t *
 //   Workgroups [0, nx*nrows): every row of the class in the nx <= 2 planes x0, x1 that take no partial sums at all; then per
 //   partial-sum plane kr in [elo, ehi) ncand candidates: cls 0: the first and the last F row of every run; cls 1: the S row
 //   after every run but the last, row 1 (jbF = 1), the S row beyond the last F.
-template <int BS, bool EFIRST, bool NT>
-__global__ __launch_bounds__(BS) void relax27_rows_sel(const Op3 A, const real_t *__restrict__ qf, real_t *__restrict__ q,
+template <int BS, bool EFIRST, bool NT, typename OP = Op3>
+__global__ __launch_bounds__(BS) void relax27_rows_sel(const OP A, const real_t *__restrict__ qf, real_t *__restrict__ q,
                                                         int II, int JJ, int KK, int kb, int elo, int ehi, int x0, int x1,
                                                         PsumGeom gm, int cls, PsumSkip skp)
 {
@@ -509,8 +509,8 @@ __global__ __launch_bounds__(BS) void relax27_rows_sel(const Op3 A, const real_t
 }
 
 // rows j = j0 + jstep*jr of all planes of parity kb, reference order (the S rows between the runs of the A launch)
-template <int BS, bool EFIRST, bool NT>
-__global__ __launch_bounds__(BS) void relax27_rows_between(const Op3 A, const real_t *__restrict__ qf, real_t *__restrict__ q,
+template <int BS, bool EFIRST, bool NT, typename OP = Op3>
+__global__ __launch_bounds__(BS) void relax27_rows_between(const OP A, const real_t *__restrict__ qf, real_t *__restrict__ q,
                                                             int II, int JJ, int KK, int j0, int jstep, int nrj, int kb, int kr0,
                                                             int nrk, PsumSkip skp)
 {
@@ -526,22 +526,22 @@ __global__ __launch_bounds__(BS) void relax27_rows_between(const Op3 A, const re
 
 // A phase on the planes kr0 .. kr0+nrk-1 of the first k-parity kb: the plane-fused walk with partial sums, then the S rows
 // between runs (reference order)
-template <int BS, bool EFIRST>
-static void phase_a(const Op3 &A, const real_t *qf, real_t *q, real_t *T, int II, int JJ, int KK, int kb, int kr0, int nrk,
+template <int BS, bool EFIRST, typename OP>
+static void phase_a(const OP &A, const real_t *qf, real_t *q, real_t *T, int II, int JJ, int KK, int kb, int kr0, int nrk,
                     int nbr, const PsumGeom &gm, hipStream_t st, const PsumSkip &skp)
 {
 	if (nrk <= 0) return;
-	hipLaunchKernelGGL((relax27_planeA<BS, EFIRST, true>), dim3(xcd_grid((unsigned)nrk * (unsigned)gm.nrun)), dim3(BS), 0, st,
+	hipLaunchKernelGGL((relax27_planeA<BS, EFIRST, true, OP>), dim3(xcd_grid((unsigned)nrk * (unsigned)gm.nrun)), dim3(BS), 0, st,
 	                   A, qf, q, T, II, JJ, KK, kb, kr0, nrk, nbr, gm, skp);
 	if (gm.nrun > 1)
-		hipLaunchKernelGGL((relax27_rows_between<BS, EFIRST, true>), dim3((unsigned)((gm.nrun - 1) * nrk)), dim3(BS), 0, st,
+		hipLaunchKernelGGL((relax27_rows_between<BS, EFIRST, true, OP>), dim3((unsigned)((gm.nrun - 1) * nrk)), dim3(BS), 0, st,
 		                   A, qf, q, II, JJ, KK, (gm.jbF ? 1 : 0) + 2 * gm.frun, 2 * gm.frun, gm.nrun - 1, kb, kr0, nrk, skp);
 }
 
 // B phase on the planes kr0 .. kr0+nrk-1 of the second k-parity kb: the planes that take partial sums form a contiguous
 // range; at most one plane at either end of the piece keeps the reference order altogether
-template <int BS, bool EFIRST>
-static void phase_b(const Op3 &A, const real_t *qf, real_t *q, real_t *T, int II, int JJ, int KK, int kb, int kr0, int nrk,
+template <int BS, bool EFIRST, typename OP>
+static void phase_b(const OP &A, const real_t *qf, real_t *q, real_t *T, int II, int JJ, int KK, int kb, int kr0, int nrk,
                     int nbr, const PsumGeom &gm, hipStream_t st, const PsumSkip &skp)
 {
 	if (nrk <= 0) return;
@@ -563,19 +563,19 @@ static void phase_b(const Op3 &A, const real_t *qf, real_t *q, real_t *T, int II
 		const int nxp = (x0 >= 0 ? 1 : 0) + (x1 >= 0 ? 1 : 0);
 		for (int cls = 0; cls < 2; cls++) {
 			if (cls == 1 && first && nel > 0)
-				hipLaunchKernelGGL((relax27_planeB<BS, EFIRST, true>), dim3(xcd_grid((unsigned)nel * (unsigned)gm.nrun)), dim3(BS), 0, st,
+				hipLaunchKernelGGL((relax27_planeB<BS, EFIRST, true, OP>), dim3(xcd_grid((unsigned)nel * (unsigned)gm.nrun)), dim3(BS), 0, st,
 				                   A, qf, q, T, II, JJ, KK, kb, elo, nel, gm, skp);
 			const int nrows = cls ? gm.nS : gm.nF, ncand = cls ? gm.nrun + 1 : 2 * gm.nrun;
 			const int nwg = nxp * nrows + (first ? nel * ncand : 0);
 			if (nwg > 0)
-				hipLaunchKernelGGL((relax27_rows_sel<BS, EFIRST, true>), dim3((unsigned)nwg), dim3(BS), 0, st,
+				hipLaunchKernelGGL((relax27_rows_sel<BS, EFIRST, true, OP>), dim3((unsigned)nwg), dim3(BS), 0, st,
 				                   A, qf, q, II, JJ, KK, kb, first ? elo : 0, first ? ehi : 0, x0, x1, gm, cls, skp);
 		}
 	} while (done < exact.size());
 }
 
-template <int BS, bool EFIRST>
-static void sweep_psum(const Op3 &A, const real_t *qf, real_t *q, real_t *T, int II, int JJ, int KK, int frun, hipStream_t st)
+template <int BS, bool EFIRST, typename OP>
+static void sweep_psum(const OP &A, const real_t *qf, real_t *q, real_t *T, int II, int JJ, int KK, int frun, hipStream_t st)
 {
 	const bool up = EFIRST; // UP: even i, j-parity 0 rows, k-parity 0 planes first; DOWN the reverse
 	const int jbF = up ? 0 : 1, kbA = up ? 0 : 1, kbB = 1 - kbA;
@@ -616,8 +616,9 @@ bool relax3_psum_ok(int II, int JJ, int KK, int frun)
 	return frun > 0 && II >= 3 && JJ >= 3 && KK >= 3 && (II - 2 + 1) / 2 <= 256;
 }
 
-void relax3_gs27_psum(const Op3 &A, const real_t *qf, real_t *q, real_t *T, int II, int JJ, int KK, int updown, int frun,
-                      hipStream_t st)
+template <typename OP>
+static void relax3_gs27_psum_t(const OP &A, const real_t *qf, real_t *q, real_t *T, int II, int JJ, int KK, int updown, int frun,
+                               hipStream_t st)
 {
 	const int npairs = (II - 2 + 1) / 2;
 	const bool up = updown == BMG_UP;
@@ -630,6 +631,18 @@ void relax3_gs27_psum(const Op3 &A, const real_t *qf, real_t *q, real_t *T, int 
 	else if (npairs <= 128) PSUM_BS(128);
 	else PSUM_BS(256);
 #undef PSUM_BS
+}
+
+void relax3_gs27_psum(const Op3 &A, const real_t *qf, real_t *q, real_t *T, int II, int JJ, int KK, int updown, int frun,
+                      hipStream_t st)
+{
+	relax3_gs27_psum_t(A, qf, q, T, II, JJ, KK, updown, frun, st);
+}
+
+void relax3_gs27_psum(const Op3f &A, const real_t *qf, real_t *q, real_t *T, int II, int JJ, int KK, int updown, int frun,
+                      hipStream_t st)
+{
+	relax3_gs27_psum_t(A, qf, q, T, II, JJ, KK, updown, frun, st);
 }
 
 } // namespace cedar_amd

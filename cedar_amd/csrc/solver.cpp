@@ -44,6 +44,9 @@ struct Level {
 	real_t *PFx = nullptr, *PFy = nullptr;
 	// 3D 27-point: row-interleaved solve copy of A and 1/diag (common.h Op3) read by relax and residual
 	real_t *Ailv = nullptr;
+	// the same copy in single precision (common.h Op3f) after cedar_amd_solver_use_fp32_operator: it replaces Ailv, and
+	// the level's sweeps and the cycle's residual read it; A itself stays FP64
+	float *A32 = nullptr;
 	// 3D 27-point: partial-sum scratch of the relax sweep (relax3d_psum.hip), one vector
 	real_t *T = nullptr;
 	// the set-up products (A, P, SOR, At, PF*) belong to another solver of the same operator (plane relaxation:
@@ -198,13 +201,23 @@ Op3 op3_of(const Level &L)
 	return L.Ailv ? op3_ilv(L.Ailv, L.II, L.JJ, L.KK) : op3_cedar(L.A, L.SOR0, L.II, L.JJ, L.KK);
 }
 
+// the cycle's residual on a level: with the level's solve copy where it keeps one (A32: the operator rounded to float)
 void residual(const cedar_amd_solver *s, const Level &L, const real_t *x, const real_t *b, real_t *r, hipStream_t st)
 {
 	if (s->nd == 2) residual2(L.A, b, x, r, L.II, L.JJ, L.nst, st, Batch{s->nb, L.npts});
 	else if (s->nb > 1 && L.nst == 14) residual27_many(op3_of(L), b, x, r, L.II, L.JJ, L.KK, st, Batch{s->nb, L.npts});
 	else if (s->nb > 1) residual7_many(L.A, b, x, r, L.II, L.JJ, L.KK, st, Batch{s->nb, L.npts});
+	else if (L.A32) residual27_op(op3f_ilv(L.A32, L.II, L.JJ, L.KK), b, x, r, L.II, L.JJ, L.KK, st);
 	else if (L.Ailv) residual27_op(op3_of(L), b, x, r, L.II, L.JJ, L.KK, st);
 	else residual3(L.A, b, x, r, L.II, L.JJ, L.KK, L.nst, st);
+}
+
+// r = b - A x with the operator the caller gave: what a solve reports and what the Krylov recurrence starts from.  On a
+// level that keeps the single-precision copy this reads the FP64 planes, not the copy
+void residual_true(const cedar_amd_solver *s, const Level &L, const real_t *x, const real_t *b, real_t *r, hipStream_t st)
+{
+	if (L.A32) residual3(L.A, b, x, r, L.II, L.JJ, L.KK, L.nst, st);
+	else residual(s, L, x, b, r, st);
 }
 
 // one y-line sweep: on the transposed arrays when the level keeps them
@@ -397,7 +410,8 @@ void smooth(const cedar_amd_solver *s, const Level &L, real_t *x, const real_t *
 			continue;
 		}
 		if (s->nd == 3) {
-			if (L.Ailv || L.T) relax3_gs27_op(op3_of(L), b, x, L.II, L.JJ, L.KK, updown, st, L.T);
+			if (L.A32) relax3_gs27_op(op3f_ilv(L.A32, L.II, L.JJ, L.KK), b, x, L.II, L.JJ, L.KK, updown, st, L.T);
+			else if (L.Ailv || L.T) relax3_gs27_op(op3_of(L), b, x, L.II, L.JJ, L.KK, updown, st, L.T);
 			else relax3_gs(L.A, b, x, L.SOR0, L.II, L.JJ, L.KK, L.nst, updown, st);
 			continue;
 		}
@@ -824,6 +838,7 @@ void cedar_amd_solver_destroy(cedar_amd_solver *s)
 		if (L.ownA) (void)hipFree(L.A);
 		if (!L.shared) {
 			(void)hipFree(L.P); (void)hipFree(L.SOR0); (void)hipFree(L.SOR1); (void)hipFree(L.At); (void)hipFree(L.Ailv);
+			(void)hipFree(L.A32);
 			(void)hipFree(L.PFx); (void)hipFree(L.PFy);
 		}
 		(void)hipFree(L.res); (void)hipFree(L.yscr); (void)hipFree(L.bt); (void)hipFree(L.xt); (void)hipFree(L.T);
@@ -877,6 +892,103 @@ size_t cedar_amd_solver_get(const cedar_amd_solver *s, int lvl, const char *what
 	return n;
 }
 
+static void pcg_alloc(cedar_amd_solver *s, int items = 1);
+static void pcg_precondition(cedar_amd_solver *s, int nmg, hipStream_t st);
+
+// ---- single-precision operator copies (include/cedar_amd.h cedar_amd_solver_use_fp32_operator)
+static int fp32_count(const cedar_amd_solver *s)
+{
+	int n = 0;
+	for (const Level &L : s->lv) n += L.A32 ? 1 : 0;
+	return n;
+}
+
+// no captured cycle survives a change of the arrays its launches name
+static void graphs_drop(cedar_amd_solver *s)
+{
+	CEDAR_HIP_CHECK(hipDeviceSynchronize());
+	if (s->gexec) CEDAR_HIP_CHECK(hipGraphExecDestroy(s->gexec));
+	if (s->gexec2) CEDAR_HIP_CHECK(hipGraphExecDestroy(s->gexec2));
+	s->gexec = s->gexec2 = nullptr;
+}
+
+// (re)build the float copy of a level into `out`; true = an entry of A or 1/diag does not fit float
+static bool op32_build(cedar_amd_solver *s, const Level &L, float *out, hipStream_t st)
+{
+	int *flag = s->dinfo + 1, host = 0; // (dinfo[0]: the coarse factorisation's info)
+	CEDAR_HIP_CHECK(hipMemsetAsync(flag, 0, sizeof(int), st));
+	ilv32_build(L.A, L.SOR0 + L.npts, out, L.II, L.JJ, L.KK, flag, st);
+	CEDAR_HIP_CHECK(hipMemcpyAsync(&host, flag, sizeof(int), hipMemcpyDeviceToHost, st));
+	CEDAR_HIP_CHECK(hipStreamSynchronize(st));
+	return host != 0;
+}
+
+// Smallest row count from which a level takes the copy by default.  Measured (tools/op32_time.py, profiles/op32_time.json;
+// DESIGN.md section 12): adding the level with 128 rows shortens the V-cycle on every handle measured, adding the one with
+// 64 rows lengthens it (such a level is launch-bound, and the Cedar-layout kernels it otherwise runs are the better fit)
+enum { OP32_DEFAULT_MIN_ROWS = 128 };
+
+int cedar_amd_solver_fp32_levels(const cedar_amd_solver *s)
+{
+	return null_handle(s, "cedar_amd_solver_fp32_levels") ? 0 : fp32_count(s);
+}
+
+int cedar_amd_solver_use_fp32_operator(cedar_amd_solver *s, int min_rows)
+{
+	const char *who = "cedar_amd_solver_use_fp32_operator";
+	if (null_handle(s, who)) return -1;
+	const char *why = nullptr;
+	if (s->nd != 3) why = "2D handles are not supported";
+	else if (s->st.ibc != 0) why = "periodic boundary conditions (ibc != 0) are not supported";
+	else if (s->st.relaxation != CEDAR_AMD_RELAX_POINT) why = "plane relaxation is not supported";
+	else if (s->nb_alloc > 1) why = "handles of cedar_amd_solver_create_many are not supported";
+	else if (min_rows < 0) why = "min_rows must not be negative";
+	auto refuse = [&](const char *reason) {
+		char msg[256];
+		snprintf(msg, sizeof(msg), "%s: %s; the handle is unchanged", who, reason);
+		print_error(msg);
+		return -1;
+	};
+	if (why) return refuse(why);
+	if (min_rows == 0) {
+		const char *e = getenv("CEDAR_AMD_OP32_MIN_ROWS"); // read per call, like CEDAR_AMD_PSUM
+		min_rows = e && atoi(e) > 0 ? atoi(e) : (int)OP32_DEFAULT_MIN_ROWS;
+	}
+	// every smoothed 27-point level (all but the coarsest) with at least min_rows rows, rows within the row kernels' reach;
+	// all copies are built and checked before the handle changes
+	hipStream_t st = current_stream();
+	std::vector<std::pair<int, float *>> fresh;
+	auto undo = [&]() {
+		for (auto &f : fresh) (void)hipFree(f.second);
+	};
+	for (int l = 0; l + 1 < (int)s->lv.size(); l++) {
+		const Level &L = s->lv[l];
+		if (L.A32 || L.nst != 14 || L.ny < min_rows || (L.II - 2 + 1) / 2 > 512) continue;
+		float *c = nullptr;
+		if (hipMalloc((void **)&c, ilv32_floats(L.II, L.JJ, L.KK) * sizeof(float)) != hipSuccess) {
+			(void)hipGetLastError();
+			undo();
+			return refuse("out of device memory for the single-precision copy");
+		}
+		fresh.emplace_back(l, c);
+		if (op32_build(s, L, c, st)) {
+			undo();
+			return refuse("an entry of the operator or of 1/diag overflows single precision");
+		}
+	}
+	if (!fresh.empty()) {
+		graphs_drop(s);
+		for (auto &f : fresh) {
+			Level &L = s->lv[f.first];
+			L.A32 = f.second;
+			(void)hipFree(L.Ailv);
+			L.Ailv = nullptr;
+		}
+	}
+	launch_check(who);
+	return fp32_count(s);
+}
+
 // levels[lvl].A / .P / .SOR / ABD are public members of the reference's solver (include/cedar/level.h:14-41,
 // include/cedar/2d/solver.h:56): a caller may replace a set-up product.  Solver-internal copies that derive from the
 // array (row-interleaved solve copy, transposed y-line planes, scan-ordered line factors) are rebuilt.
@@ -898,6 +1010,15 @@ size_t cedar_amd_solver_set(cedar_amd_solver *s, int lvl, const char *what, cons
 	else cedar_amd_memcpy_h2d(dst, in, n * sizeof(real_t));
 	if (L.Ailv && (!strcmp(what, "A") || !strcmp(what, "SOR0")))
 		ilv_build(L.A, L.SOR0 + L.npts, L.Ailv, L.II, L.JJ, L.KK, st);
+	if (L.A32 && (!strcmp(what, "A") || !strcmp(what, "SOR0")) && op32_build(s, L, L.A32, st)) {
+		// the new entries do not fit float: the level goes back to the FP64 planes (the captured cycle names the copy)
+		char msg[] = "cedar_amd_solver_set: an entry of the new array overflows single precision; the level reads the FP64 "
+		             "operator again";
+		print_error(msg);
+		graphs_drop(s);
+		(void)hipFree(L.A32);
+		L.A32 = nullptr;
+	}
 	if (L.At && !strcmp(what, "A")) setup_lines_yt(L.A, L.At, L.II, L.JJ, L.nst, st);
 	if (L.PFx && !strcmp(what, "SOR0")) lines_permute(L.SOR0, L.PFx, L.nx, L.II, L.ny, L.npts, st);
 	if (L.PFy && !strcmp(what, s->st.relaxation == CEDAR_AMD_RELAX_LINE_Y ? "SOR0" : "SOR1"))
@@ -926,14 +1047,25 @@ int cedar_amd_solver_solve(cedar_amd_solver *s, const real_t *b, real_t *x, real
 	Level &L = s->lv[0];
 	Staged sx(x, L.npts, true, true), sb(b, L.npts, true, false);
 	hipStream_t st = current_stream();
-	residual(s, L, sx.get(), sb.get(), L.res, st);
-	const double res0 = l2_dev(s, L, L.res);
+	// A handle whose cycle reads a single-precision operator (cedar_amd_solver_use_fp32_operator) iterates in
+	// defect-correction form on the Krylov storage: r = b - A x with the FP64 operator (the residual the norm needs
+	// anyway), z = cycle(0, r), x += z -- the fixed point is the solution of A, not of the rounded operator.  An F-cycle
+	// starts every cycle from x = 0 (fmg_cycle), so there is no iterate to correct: it keeps the plain form.
+	const bool defect = s->st.cycle == 0 && s->lv.size() > 1 && fp32_count(s) > 0;
+	if (defect) pcg_alloc(s);
+	real_t *res = defect ? s->kr : L.res;
+	residual_true(s, L, sx.get(), sb.get(), res, st);
+	const double res0 = l2_dev(s, L, res);
 	rel[0] = res0;
 	int it = 0;
 	for (it = 0; it < s->st.max_iter; it++) {
-		cycle_dev(s, sx.get(), sb.get());
-		residual(s, L, sx.get(), sb.get(), L.res, st);
-		const double r = l2_dev(s, L, L.res) / res0;
+		if (defect) {
+			pcg_precondition(s, 1, st);
+			vec_add(sx.get(), s->kz, L.npts, st);
+		} else
+			cycle_dev(s, sx.get(), sb.get());
+		residual_true(s, L, sx.get(), sb.get(), res, st);
+		const double r = l2_dev(s, L, res) / res0;
 		rel[it + 1] = r;
 		if (r < s->st.tol) { it++; break; }
 	}
@@ -1085,7 +1217,7 @@ static bool pcg_refused(const cedar_amd_solver *s, const cedar_amd_pcg_settings 
 
 // the Krylov storage for `items` right-hand sides (item-major; the single-vector calls work on item 0's set).  Growing it
 // frees the smaller set first: a captured cycle on the old (z, r) pair is re-recorded by graph_prepare when they moved.
-static void pcg_alloc(cedar_amd_solver *s, int items = 1)
+static void pcg_alloc(cedar_amd_solver *s, int items)
 {
 	if (s->kr && s->kitems >= items) return;
 	if (s->kr) {
@@ -1155,7 +1287,7 @@ static int pcg_run(cedar_amd_solver *s, int nrhs, const real_t *b, real_t *x, co
 
 	// r0 = b - A x0, z0 = M^-1 r0, rho0 = r0.z0 of every item (the update pass without the update)
 	zero_fill(s->ksc, (size_t)PCG_NSC * nrhs, st);
-	residual(s, L, X, sb.get(), s->kr, st);
+	residual_true(s, L, X, sb.get(), s->kr, st);
 	if (zm == 2) pcg_precondition(s, p.nmg_cycles, st);
 	update(zm, nullptr, true);
 	scalars();

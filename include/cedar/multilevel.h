@@ -225,6 +225,19 @@ public:
 		history = histories[0];
 	}
 
+	// keep the 27-point operator of the cycle in single precision on the smoothed levels with at least min_rows rows
+	// (0: the library's default; cedar_amd_solver_use_fp32_operator).  Returns the number of levels that read a float
+	// copy, -1 when refused (3D Dirichlet point relaxation only; the handle is unchanged).  Resident path only.
+	int use_fp32_operator(int min_rows = 0)
+	{
+		if (!resident()) {
+			log::error << "use_fp32_operator: needs the device-resident solver (every kernel \"hip\")" << std::endl;
+			return -1;
+		}
+		return cedar_amd_solver_use_fp32_operator(h, min_rows);
+	}
+	int fp32_levels() const { return h ? cedar_amd_solver_fp32_levels(h) : 0; }
+
 	void vcycle(grid_func & x, const grid_func & b)
 	{
 		if (resident()) { cedar_amd_solver_vcycle(h, x.data(), b.data()); return; }

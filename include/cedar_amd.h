@@ -186,6 +186,16 @@ void cedar_amd_relax3_release(const real_t *so);
  * reference-order sweep was run instead. */
 int cedar_amd_relax3_gs_psum(real_t *so, real_t *qf, real_t *q, real_t *sor, real_t *scratch, len_t ii, len_t jj, len_t kk,
                              int updown);
+/* One 27-point sweep / residual with the operator and 1/diag rounded to single precision (what a level of a solver
+ * after cedar_amd_solver_use_fp32_operator runs): a row-interleaved float copy is built for the call, the kernels
+ * promote its entries to double on load, vectors and arithmetic stay FP64 -- bit for bit the FP64 kernels on the
+ * rounded arrays.  frun > 0: the partial-sum sweep with runs of frun rows where the level can take it (at least four
+ * runs per plane, rows of at most 512 points; returns 1), else -- and with frun = 0 -- the reference order (returns 0;
+ * CEDAR_AMD_FRUN picks the plane-fused or the row kernels as for BMG3_SymStd_relax_GS).  Rows longer than 1024 points
+ * or an entry that overflows float: print_error, -1, q / res untouched.  scratch as for cedar_amd_relax3_gs_psum. */
+int cedar_amd_relax3_gs_op32(real_t *so, real_t *qf, real_t *q, real_t *sor, real_t *scratch, len_t ii, len_t jj, len_t kk,
+                             int updown, int frun);
+int cedar_amd_residual3_op32(real_t *so, real_t *qf, real_t *q, real_t *res, len_t ii, len_t jj, len_t kk);
 /* The 2D analogue for nine-point operators (BMG2_SymStd_relax_GS.f90:89-114): the band-fused sweep whose S rows take the
  * six couplings to the two neighbouring F rows as ONE partial-sum row kept in LDS by the workgroup that has just relaxed
  * those F rows.  Same contract as cedar_amd_relax3_gs_psum; the resident solver runs it on levels with at least 4096 rows
@@ -392,6 +402,31 @@ int cedar_amd_solver_pcg(cedar_amd_solver *s, const real_t *b, real_t *x, const 
 /* z = M^-1 r: one cycle of the solver from z = 0 (the preconditioner of cedar_amd_solver_pcg with nmg_cycles = 1);
  * z, r host or device.  Refused (z untouched) on the settings cedar_amd_solver_pcg refuses for precon = 3. */
 void cedar_amd_solver_precondition(cedar_amd_solver *s, real_t *z, const real_t *r);
+
+/* Keep the 27-point operator of the cycle in single precision (3D, Dirichlet, point relaxation).  Every smoothed
+ * 27-point level (all but the coarsest) with at least min_rows rows gets a row-interleaved copy of A and 1/diag rounded
+ * to float (round to nearest even; rows of at most 1024 points) and releases its FP64 solve copy; the level's sweeps
+ * and the cycle's residual then stream 84 instead of 136 bytes per point.  The kernels promote an entry to double when
+ * they load it and do all arithmetic, and keep all vectors, in FP64: the cycle is exactly the FP64 cycle of the
+ * rounded operator.  Interpolation, restriction, the coarsest solve and 7-point levels are unchanged.
+ *   min_rows 0 = the default (128; CEDAR_AMD_OP32_MIN_ROWS overrides it, read at the call).
+ * Returns the number of levels that now read a float copy (0 is valid; the call may be repeated and never switches a
+ * level back).  Refused -- print_error, -1, handle unchanged -- for a NULL or 2D handle, ibc != 0, plane relaxation, a
+ * handle of cedar_amd_solver_create_many, and when an entry of A or 1/diag overflows float.
+ * What the other calls do on such a handle:
+ *   cedar_amd_solver_vcycle        the plain cycle of the ROUNDED operator: iterating it converges to the rounded
+ *                                  operator's solution (relative error of order 6e-8 times the condition number);
+ *   cedar_amd_solver_pcg, _precondition  the cycle is the preconditioner; the Krylov recurrence and its residuals use
+ *                                  the FP64 operator given at creation, so the solve converges to its solution;
+ *   cedar_amd_solver_solve         V-cycle handles iterate in defect-correction form, r = b - A x with the FP64
+ *                                  operator, x += cycle(0, r), and report that residual; the first call allocates the
+ *                                  vectors of cedar_amd_solver_pcg.  F-cycle handles start every cycle from x = 0 as
+ *                                  before and report the FP64 residual;
+ *   cedar_amd_solver_set           "A" / "SOR0" on a switched level rebuild its float copy (an overflow is reported
+ *                                  and the level goes back to the FP64 arrays). */
+int cedar_amd_solver_use_fp32_operator(cedar_amd_solver *s, int min_rows);
+/* the number of levels whose cycle reads a float copy (0 before the call above, or for a NULL handle) */
+int cedar_amd_solver_fp32_levels(const cedar_amd_solver *s);
 
 /* Several right-hand sides at once on one resident hierarchy.  The operator, 1/diag and the interpolation weights are
  * the same for every right-hand side, so the batched 3D kernels (many3d.hip) fetch them once per workgroup task and apply
