@@ -327,6 +327,20 @@ class Kernels:
         self._many("cedar_amd_residual3_many",
                    lib.cedar_amd_residual3_many(q.shape[0] if nrhs is None else nrhs, _p(so), _p(qf), _p(q), _p(res), u(II), u(JJ), u(KK), nst))
 
+    def relax3_many_op32(self, so, qf, q, sor, updown, nrhs=None):
+        """the batched 27-point sweep on the operator and 1/diag rounded to single precision
+        (cedar_amd_relax3_gs_many_op32), reference order; 0, or -1 if refused (q untouched)"""
+        grid = q.shape[1:]
+        KK, JJ, II = grid
+        return lib.cedar_amd_relax3_gs_many_op32(q.shape[0] if nrhs is None else nrhs, _p(so), _p(qf), _p(q), _p(sor), u(II), u(JJ), u(KK), updown)
+
+    def residual3_many_op32(self, so, qf, q, res, nrhs=None):
+        """the batched 27-point residual on the operator rounded to single precision (cedar_amd_residual3_many_op32);
+        0, or -1 if refused (res untouched)"""
+        grid = q.shape[1:]
+        KK, JJ, II = grid
+        return lib.cedar_amd_residual3_many_op32(q.shape[0] if nrhs is None else nrhs, _p(so), _p(qf), _p(q), _p(res), u(II), u(JJ), u(KK))
+
     def restrict3_many(self, q, qc, ci, nrhs=None):
         n, KK, JJ, II = q.shape
         nc, KKC, JJC, IIC = qc.shape
@@ -485,6 +499,8 @@ lib.cedar_amd_solver_pcg_many.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_v
                                           C.POINTER(C.c_int)]
 lib.cedar_amd_solver_use_fp32_operator.restype = C.c_int
 lib.cedar_amd_solver_use_fp32_operator.argtypes = [C.c_void_p, C.c_int]
+lib.cedar_amd_solver_use_fp32_operator_many.restype = C.c_int
+lib.cedar_amd_solver_use_fp32_operator_many.argtypes = [C.c_void_p, C.c_int]
 lib.cedar_amd_solver_fp32_levels.restype = C.c_int
 lib.cedar_amd_solver_fp32_levels.argtypes = [C.c_void_p]
 
@@ -620,6 +636,11 @@ class Solver:
         rows (0: the default; cedar_amd_solver_use_fp32_operator).  Returns the number of levels that read a float copy,
         -1 when the library refuses (the reason is printed, the handle is unchanged)"""
         return lib.cedar_amd_solver_use_fp32_operator(self.h, int(min_rows))
+
+    def use_fp32_operator_many(self, min_rows=0):
+        """use_fp32_operator for a handle made with max_rhs > 1 (cedar_amd_solver_use_fp32_operator_many): the batched cycle
+        of vcycle_many / solve_many / pcg_many then reads the float copies.  With max_rhs == 1 it is use_fp32_operator"""
+        return lib.cedar_amd_solver_use_fp32_operator_many(self.h, int(min_rows))
 
     def fp32_levels(self):
         return lib.cedar_amd_solver_fp32_levels(self.h)

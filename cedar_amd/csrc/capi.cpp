@@ -888,6 +888,40 @@ int cedar_amd_residual3_many(int nrhs, real_t *so, real_t *qf, real_t *q, real_t
 	return 0;
 }
 
+// the two 27-point ones on a single-precision copy of the operator built for the call (op32_copy_get), reference order
+int cedar_amd_relax3_gs_many_op32(int nrhs, real_t *so, real_t *qf, real_t *q, real_t *sor, len_t ii, len_t jj, len_t kk, int updown)
+{
+	const char *who = "cedar_amd_relax3_gs_many_op32";
+	if (many_args_refused(nrhs, so && qf && q && sor, true, who)) return -1;
+	const int II = (int)ii, JJ = (int)jj, KK = (int)kk;
+	const size_t P = (size_t)ii * jj * kk;
+	Staged sso(so, P * 14, true, false), sqf(qf, P * nrhs, true, false), sq(q, P * nrhs, true, true), ssor(sor, P * 2, true, false);
+	float *c = op32_copy_get(sso.get(), ssor.get() + P, II, JJ, KK, who);
+	if (!c) return -1;
+	hipStream_t st = current_stream();
+	relax3_gs27_many(op3f_ilv(c, II, JJ, KK), sqf.get(), sq.get(), II, JJ, KK, updown, st, Batch{nrhs, P});
+	CEDAR_HIP_CHECK(hipStreamSynchronize(st));
+	pool_put(c, ilv32_floats(II, JJ, KK) * sizeof(float));
+	return 0;
+}
+
+int cedar_amd_residual3_many_op32(int nrhs, real_t *so, real_t *qf, real_t *q, real_t *res, len_t ii, len_t jj, len_t kk)
+{
+	const char *who = "cedar_amd_residual3_many_op32";
+	if (many_args_refused(nrhs, so && qf && q && res, true, who)) return -1;
+	const int II = (int)ii, JJ = (int)jj, KK = (int)kk;
+	const size_t P = (size_t)ii * jj * kk;
+	Staged sso(so, P * 14, true, false), sqf(qf, P * nrhs, true, false), sq(q, P * nrhs, true, false), sr(res, P * nrhs, true, true);
+	// 1/diag is not read by the residual: the copy's reciprocal row is filled from the operator's centre plane
+	float *c = op32_copy_get(sso.get(), sso.get(), II, JJ, KK, who);
+	if (!c) return -1;
+	hipStream_t st = current_stream();
+	residual27_many(op3f_ilv(c, II, JJ, KK), sqf.get(), sq.get(), sr.get(), II, JJ, KK, st, Batch{nrhs, P});
+	CEDAR_HIP_CHECK(hipStreamSynchronize(st));
+	pool_put(c, ilv32_floats(II, JJ, KK) * sizeof(float));
+	return 0;
+}
+
 int cedar_amd_restrict3_many(int nrhs, real_t *q, real_t *qc, real_t *ci, len_t ii, len_t jj, len_t kk, len_t iic, len_t jjc,
                              len_t kkc)
 {

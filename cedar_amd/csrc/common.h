@@ -343,6 +343,10 @@ void pcg_ghost_shell(const real_t *z, const real_t *p, real_t *pn, const real_t 
 // of the single-vector reference-order kernels on item m alone.  bf / bc: batch strides of the fine / coarse vectors.
 void relax3_gs27_many(const Op3 &A, const real_t *qf, real_t *q, int II, int JJ, int KK, int updown, hipStream_t st, Batch bt);
 void residual27_many(const Op3 &A, const real_t *qf, const real_t *q, real_t *res, int II, int JJ, int KK, hipStream_t st, Batch bt);
+// the same two on the single-precision view; the sweep serves rows of at most 1024 points and launches nothing on longer
+// ones (no level with such rows takes the float copy, and cedar_amd_relax3_gs_many_op32 refuses them)
+void relax3_gs27_many(const Op3f &A, const real_t *qf, real_t *q, int II, int JJ, int KK, int updown, hipStream_t st, Batch bt);
+void residual27_many(const Op3f &A, const real_t *qf, const real_t *q, real_t *res, int II, int JJ, int KK, hipStream_t st, Batch bt);
 void relax3_gs7_many(const real_t *so, const real_t *qf, real_t *q, const real_t *sor, int II, int JJ, int KK, int updown,
                      hipStream_t st, Batch bt);
 void residual7_many(const real_t *so, const real_t *qf, const real_t *q, real_t *res, int II, int JJ, int KK, hipStream_t st, Batch bt);

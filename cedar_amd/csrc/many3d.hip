@@ -10,6 +10,7 @@
 // the items it would buy little).
 #include "common.h"
 #include "relax27_dev.h"
+#include <type_traits>
 
 namespace cedar_amd {
 
@@ -18,8 +19,10 @@ namespace cedar_amd {
 // coefficients and reciprocals stay in registers across the item loop, the q windows are per item.  xch: two LDS rows
 // of BS+2 doubles used in turn, so that an item's first-colour values are not overwritten while a slower wave still
 // reads the previous item's (one __syncthreads per item; every wave of the workgroup must call this).
-template <int BS, bool EFIRST, bool NT>
-__device__ __forceinline__ void relax27_row_task_many(const Op3 &A, const real_t *__restrict__ qf, real_t *__restrict__ q,
+// OP: the operator view, Op3 or the single-precision Op3f (common.h; entries promoted to double by the pair loads, so
+// the items see the FP64 sweep of the operator rounded to float).
+template <int BS, bool EFIRST, bool NT, typename OP = Op3>
+__device__ __forceinline__ void relax27_row_task_many(const OP &A, const real_t *__restrict__ qf, real_t *__restrict__ q,
                                                       int II, size_t sj, size_t sk, size_t j, size_t k, real_t (*xch)[BS + 2],
                                                       int nitems, size_t stride)
 {
@@ -80,8 +83,8 @@ __device__ __forceinline__ void relax27_row_task_many(const Op3 &A, const real_t
 }
 
 // one workgroup = one grid row of the class (jb,kb), all items (relax27_rows of relax3d.hip)
-template <int BS, bool EFIRST, bool NT>
-__global__ __launch_bounds__(BS) void relax27_rows_many(const Op3 A, const real_t *__restrict__ qf, real_t *__restrict__ q,
+template <int BS, bool EFIRST, bool NT, typename OP = Op3>
+__global__ __launch_bounds__(BS) void relax27_rows_many(const OP A, const real_t *__restrict__ qf, real_t *__restrict__ q,
                                                          int II, int JJ, int KK, int jb, int kb, int nrj, int nrk, TileShape ts,
                                                          int nitems, size_t stride)
 {
@@ -94,8 +97,8 @@ __global__ __launch_bounds__(BS) void relax27_rows_many(const Op3 A, const real_
 	relax27_row_task_many<BS, EFIRST, NT>(A, qf, q, II, (size_t)II, (size_t)II * JJ, j, k, xch, nitems, stride);
 }
 
-template <int BS>
-static void launch_rows_many(bool efirst, const Op3 &A, const real_t *qf, real_t *q, int II, int JJ, int KK, int jb, int kb,
+template <int BS, typename OP = Op3>
+static void launch_rows_many(bool efirst, const OP &A, const real_t *qf, real_t *q, int II, int JJ, int KK, int jb, int kb,
                              hipStream_t st, Batch bt)
 {
 	const int nrj = (JJ - 2 - jb + 1) / 2, nrk = (KK - 2 - kb + 1) / 2;
@@ -103,17 +106,21 @@ static void launch_rows_many(bool efirst, const Op3 &A, const real_t *qf, real_t
 	const TileShape ts = tile_shape_relax();
 	const unsigned grid = xcd_grid(tile_blocks((unsigned)nrj, (unsigned)nrk, ts));
 	// operator rows are read by exactly one task of a launch: streamed past the caches as in the single-vector sweep
-	if (efirst) hipLaunchKernelGGL((relax27_rows_many<BS, true, true>), dim3(grid), dim3(BS), 0, st, A, qf, q, II, JJ, KK, jb, kb, nrj, nrk, ts, bt.n, bt.stride);
-	else hipLaunchKernelGGL((relax27_rows_many<BS, false, true>), dim3(grid), dim3(BS), 0, st, A, qf, q, II, JJ, KK, jb, kb, nrj, nrk, ts, bt.n, bt.stride);
+	if (efirst) hipLaunchKernelGGL((relax27_rows_many<BS, true, true, OP>), dim3(grid), dim3(BS), 0, st, A, qf, q, II, JJ, KK, jb, kb, nrj, nrk, ts, bt.n, bt.stride);
+	else hipLaunchKernelGGL((relax27_rows_many<BS, false, true, OP>), dim3(grid), dim3(BS), 0, st, A, qf, q, II, JJ, KK, jb, kb, nrj, nrk, ts, bt.n, bt.stride);
 }
 
-void relax3_gs27_many(const Op3 &A, const real_t *qf, real_t *q, int II, int JJ, int KK, int updown, hipStream_t st, Batch bt)
+template <typename OP = Op3>
+static void relax3_gs27_many_t(const OP &A, const real_t *qf, real_t *q, int II, int JJ, int KK, int updown, hipStream_t st, Batch bt)
 {
 	if (II < 3 || JJ < 3 || KK < 3 || bt.n < 1) return;
 	const bool up = (updown == BMG_UP);
 	const int npairs = (II - 2 + 1) / 2;
 	if (npairs > 512) { // rows too long for the row kernel: the single-vector colour kernels item by item (reference order)
-		for (int m = 0; m < bt.n; m++) relax3_gs27_op(A, qf + m * bt.stride, q + m * bt.stride, II, JJ, KK, updown, st);
+		// (those kernels have no single-precision twin: a level with such rows never takes the float copy, solver.cpp, and
+		// cedar_amd_relax3_gs_many_op32 refuses it)
+		if constexpr (std::is_same<OP, Op3>::value)
+			for (int m = 0; m < bt.n; m++) relax3_gs27_op(A, qf + m * bt.stride, q + m * bt.stride, II, JJ, KK, updown, st);
 		return;
 	}
 	// colour pairs in sweep order: UP (j,k) parities 00,10,01,11 with even-i first; DOWN the reverse
@@ -126,10 +133,20 @@ void relax3_gs27_many(const Op3 &A, const real_t *qf, real_t *q, int II, int JJ,
 	}
 }
 
+void relax3_gs27_many(const Op3 &A, const real_t *qf, real_t *q, int II, int JJ, int KK, int updown, hipStream_t st, Batch bt)
+{
+	relax3_gs27_many_t(A, qf, q, II, JJ, KK, updown, st, bt);
+}
+
+void relax3_gs27_many(const Op3f &A, const real_t *qf, real_t *q, int II, int JJ, int KK, int updown, hipStream_t st, Batch bt)
+{
+	relax3_gs27_many_t(A, qf, q, II, JJ, KK, updown, st, bt);
+}
+
 // ------------------------------------------------------------------ 27-point residual
 // residual27_rows of relax3d.hip with the item loop inside: coefficients and diagonal of the pair once
-template <int BS>
-__global__ __launch_bounds__(BS) void residual27_rows_many(const Op3 A, const real_t *__restrict__ qf, const real_t *__restrict__ q,
+template <int BS, typename OP = Op3>
+__global__ __launch_bounds__(BS) void residual27_rows_many(const OP A, const real_t *__restrict__ qf, const real_t *__restrict__ q,
                                                             real_t *__restrict__ res, int II, int JJ, int KK, unsigned nblk,
                                                             TileShape ts, int nitems, size_t stride)
 {
@@ -162,15 +179,26 @@ __global__ __launch_bounds__(BS) void residual27_rows_many(const Op3 A, const re
 	}
 }
 
-void residual27_many(const Op3 &A, const real_t *qf, const real_t *q, real_t *res, int II, int JJ, int KK, hipStream_t st, Batch bt)
+template <typename OP = Op3>
+static void residual27_many_t(const OP &A, const real_t *qf, const real_t *q, real_t *res, int II, int JJ, int KK, hipStream_t st, Batch bt)
 {
 	if (II < 3 || JJ < 3 || KK < 3 || bt.n < 1) return;
 	const TileShape ts = tile_shape_resid();
 	const unsigned nrows = tile_blocks((unsigned)(JJ - 2), (unsigned)(KK - 2), ts);
 	const int npairs = (II - 2 + 1) / 2;
-	if (npairs <= 64) hipLaunchKernelGGL((residual27_rows_many<64>), dim3(xcd_grid(nrows)), dim3(64), 0, st, A, qf, q, res, II, JJ, KK, nrows, ts, bt.n, bt.stride);
-	else if (npairs <= 128) hipLaunchKernelGGL((residual27_rows_many<128>), dim3(xcd_grid(nrows)), dim3(128), 0, st, A, qf, q, res, II, JJ, KK, nrows, ts, bt.n, bt.stride);
-	else hipLaunchKernelGGL((residual27_rows_many<256>), dim3(xcd_grid(nrows)), dim3(256), 0, st, A, qf, q, res, II, JJ, KK, nrows, ts, bt.n, bt.stride);
+	if (npairs <= 64) hipLaunchKernelGGL((residual27_rows_many<64, OP>), dim3(xcd_grid(nrows)), dim3(64), 0, st, A, qf, q, res, II, JJ, KK, nrows, ts, bt.n, bt.stride);
+	else if (npairs <= 128) hipLaunchKernelGGL((residual27_rows_many<128, OP>), dim3(xcd_grid(nrows)), dim3(128), 0, st, A, qf, q, res, II, JJ, KK, nrows, ts, bt.n, bt.stride);
+	else hipLaunchKernelGGL((residual27_rows_many<256, OP>), dim3(xcd_grid(nrows)), dim3(256), 0, st, A, qf, q, res, II, JJ, KK, nrows, ts, bt.n, bt.stride);
+}
+
+void residual27_many(const Op3 &A, const real_t *qf, const real_t *q, real_t *res, int II, int JJ, int KK, hipStream_t st, Batch bt)
+{
+	residual27_many_t(A, qf, q, res, II, JJ, KK, st, bt);
+}
+
+void residual27_many(const Op3f &A, const real_t *qf, const real_t *q, real_t *res, int II, int JJ, int KK, hipStream_t st, Batch bt)
+{
+	residual27_many_t(A, qf, q, res, II, JJ, KK, st, bt);
 }
 
 // ------------------------------------------------------------------ 7-point sweep and residual

@@ -205,6 +205,8 @@ Op3 op3_of(const Level &L)
 void residual(const cedar_amd_solver *s, const Level &L, const real_t *x, const real_t *b, real_t *r, hipStream_t st)
 {
 	if (s->nd == 2) residual2(L.A, b, x, r, L.II, L.JJ, L.nst, st, Batch{s->nb, L.npts});
+	// (A32 before op3_of: a level that keeps the float copy has released Ailv, and op3_of would hand out the unrounded planes)
+	else if (s->nb > 1 && L.A32) residual27_many(op3f_ilv(L.A32, L.II, L.JJ, L.KK), b, x, r, L.II, L.JJ, L.KK, st, Batch{s->nb, L.npts});
 	else if (s->nb > 1 && L.nst == 14) residual27_many(op3_of(L), b, x, r, L.II, L.JJ, L.KK, st, Batch{s->nb, L.npts});
 	else if (s->nb > 1) residual7_many(L.A, b, x, r, L.II, L.JJ, L.KK, st, Batch{s->nb, L.npts});
 	else if (L.A32) residual27_op(op3f_ilv(L.A32, L.II, L.JJ, L.KK), b, x, r, L.II, L.JJ, L.KK, st);
@@ -213,10 +215,12 @@ void residual(const cedar_amd_solver *s, const Level &L, const real_t *x, const 
 }
 
 // r = b - A x with the operator the caller gave: what a solve reports and what the Krylov recurrence starts from.  On a
-// level that keeps the single-precision copy this reads the FP64 planes, not the copy
+// level that keeps the single-precision copy this reads the FP64 planes, not the copy (a batch: every item)
 void residual_true(const cedar_amd_solver *s, const Level &L, const real_t *x, const real_t *b, real_t *r, hipStream_t st)
 {
-	if (L.A32) residual3(L.A, b, x, r, L.II, L.JJ, L.KK, L.nst, st);
+	if (L.A32 && s->nb > 1)
+		residual27_many(op3_cedar(L.A, L.SOR0, L.II, L.JJ, L.KK), b, x, r, L.II, L.JJ, L.KK, st, Batch{s->nb, L.npts});
+	else if (L.A32) residual3(L.A, b, x, r, L.II, L.JJ, L.KK, L.nst, st);
 	else residual(s, L, x, b, r, st);
 }
 
@@ -405,7 +409,8 @@ void smooth(const cedar_amd_solver *s, const Level &L, real_t *x, const real_t *
 		}
 		if (s->nd == 3 && s->nb > 1) { // a batch of right-hand sides: reference order, operator fetched once (many3d.hip)
 			const Batch bt{s->nb, L.npts};
-			if (L.nst == 14) relax3_gs27_many(op3_of(L), b, x, L.II, L.JJ, L.KK, updown, st, bt);
+			if (L.A32) relax3_gs27_many(op3f_ilv(L.A32, L.II, L.JJ, L.KK), b, x, L.II, L.JJ, L.KK, updown, st, bt); // before op3_of
+			else if (L.nst == 14) relax3_gs27_many(op3_of(L), b, x, L.II, L.JJ, L.KK, updown, st, bt);
 			else relax3_gs7_many(L.A, b, x, L.SOR0, L.II, L.JJ, L.KK, updown, st, bt);
 			continue;
 		}
@@ -926,6 +931,8 @@ static bool op32_build(cedar_amd_solver *s, const Level &L, float *out, hipStrea
 // Smallest row count from which a level takes the copy by default.  Measured (tools/op32_time.py, profiles/op32_time.json;
 // DESIGN.md section 12): adding the level with 128 rows shortens the V-cycle on every handle measured, adding the one with
 // 64 rows lengthens it (such a level is launch-bound, and the Cedar-layout kernels it otherwise runs are the better fit)
+// A batch handle (cedar_amd_solver_use_fp32_operator_many) has the same break-even level at 1, 2, 4 and 8 right-hand sides
+// (tools/op32_many_time.py, profiles/op32_many_time.json) and takes the same default
 enum { OP32_DEFAULT_MIN_ROWS = 128 };
 
 int cedar_amd_solver_fp32_levels(const cedar_amd_solver *s)
@@ -933,15 +940,16 @@ int cedar_amd_solver_fp32_levels(const cedar_amd_solver *s)
 	return null_handle(s, "cedar_amd_solver_fp32_levels") ? 0 : fp32_count(s);
 }
 
-int cedar_amd_solver_use_fp32_operator(cedar_amd_solver *s, int min_rows)
+// the body of cedar_amd_solver_use_fp32_operator (batch false: a handle of cedar_amd_solver_create_many is refused) and
+// of cedar_amd_solver_use_fp32_operator_many on a batch handle
+static int op32_switch(cedar_amd_solver *s, int min_rows, bool batch, const char *who)
 {
-	const char *who = "cedar_amd_solver_use_fp32_operator";
 	if (null_handle(s, who)) return -1;
 	const char *why = nullptr;
 	if (s->nd != 3) why = "2D handles are not supported";
 	else if (s->st.ibc != 0) why = "periodic boundary conditions (ibc != 0) are not supported";
 	else if (s->st.relaxation != CEDAR_AMD_RELAX_POINT) why = "plane relaxation is not supported";
-	else if (s->nb_alloc > 1) why = "handles of cedar_amd_solver_create_many are not supported";
+	else if (s->nb_alloc > 1 && !batch) why = "handles of cedar_amd_solver_create_many are not supported";
 	else if (min_rows < 0) why = "min_rows must not be negative";
 	auto refuse = [&](const char *reason) {
 		char msg[256];
@@ -987,6 +995,22 @@ int cedar_amd_solver_use_fp32_operator(cedar_amd_solver *s, int min_rows)
 	}
 	launch_check(who);
 	return fp32_count(s);
+}
+
+int cedar_amd_solver_use_fp32_operator(cedar_amd_solver *s, int min_rows)
+{
+	return op32_switch(s, min_rows, false, "cedar_amd_solver_use_fp32_operator");
+}
+
+// A batch handle takes the same copies: its batched sweeps and residual (many3d.hip) read them through the same view.  A
+// handle that holds one right-hand side -- made so, or a batch request the handle could not serve (periodic, planes) --
+// goes through the single call, refusals included.
+int cedar_amd_solver_use_fp32_operator_many(cedar_amd_solver *s, int min_rows)
+{
+	const char *who = "cedar_amd_solver_use_fp32_operator_many";
+	if (null_handle(s, who)) return -1;
+	if (s->nb_alloc == 1) return cedar_amd_solver_use_fp32_operator(s, min_rows);
+	return op32_switch(s, min_rows, true, who);
 }
 
 // levels[lvl].A / .P / .SOR / ABD are public members of the reference's solver (include/cedar/level.h:14-41,
@@ -1144,8 +1168,13 @@ int cedar_amd_solver_solve_many(cedar_amd_solver *s, int nrhs, const real_t *b, 
 	const size_t ld = (size_t)(maxit > 0 ? maxit : 0) + 1; // row length of rel
 	double res0[CEDAR_AMD_MAX_RHS], nrm[CEDAR_AMD_MAX_RHS];
 	bool met[CEDAR_AMD_MAX_RHS];
-	residual(s, L, sx.get(), sb.get(), L.res, st);
-	l2_many(s, L, L.res, res0);
+	// a handle whose cycle reads a single-precision operator: defect correction on the Krylov storage, as
+	// cedar_amd_solver_solve does -- r = b - A x with the FP64 operator on every item, z = cycle(0, r) batched, x += z
+	const bool defect = s->lv.size() > 1 && fp32_count(s) > 0;
+	if (defect) pcg_alloc(s, nrhs == 1 ? 1 : s->nb_alloc);
+	real_t *res = defect ? s->kr : L.res;
+	residual_true(s, L, sx.get(), sb.get(), res, st);
+	l2_many(s, L, res, res0);
 	int open = 0;
 	for (int m = 0; m < nrhs; m++) {
 		rel[m * ld] = res0[m];
@@ -1155,9 +1184,13 @@ int cedar_amd_solver_solve_many(cedar_amd_solver *s, int nrhs, const real_t *b, 
 	}
 	int it = 0;
 	while (open > 0 && it < maxit) {
-		cycle_dev(s, sx.get(), sb.get());
-		residual(s, L, sx.get(), sb.get(), L.res, st);
-		l2_many(s, L, L.res, nrm);
+		if (defect) {
+			pcg_precondition(s, 1, st);
+			vec_add(sx.get(), s->kz, L.npts * (size_t)nrhs, st); // items back to back in both
+		} else
+			cycle_dev(s, sx.get(), sb.get());
+		residual_true(s, L, sx.get(), sb.get(), res, st);
+		l2_many(s, L, res, nrm);
 		it++;
 		for (int m = 0; m < nrhs; m++) {
 			const double r = res0[m] == 0.0 ? 0.0 : nrm[m] / res0[m];

@@ -236,6 +236,16 @@ public:
 		}
 		return cedar_amd_solver_use_fp32_operator(h, min_rows);
 	}
+	// the same on a solver that holds several right-hand sides (cedar_amd_solver_use_fp32_operator_many): the batched
+	// sweeps and residual of solve_many's cycle read the float copies; with one right-hand side it is use_fp32_operator
+	int use_fp32_operator_many(int min_rows = 0)
+	{
+		if (!resident()) {
+			log::error << "use_fp32_operator_many: needs the device-resident solver (every kernel \"hip\")" << std::endl;
+			return -1;
+		}
+		return cedar_amd_solver_use_fp32_operator_many(h, min_rows);
+	}
 	int fp32_levels() const { return h ? cedar_amd_solver_fp32_levels(h) : 0; }
 
 	void vcycle(grid_func & x, const grid_func & b)

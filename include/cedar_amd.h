@@ -412,7 +412,8 @@ void cedar_amd_solver_precondition(cedar_amd_solver *s, real_t *z, const real_t 
  *   min_rows 0 = the default (128; CEDAR_AMD_OP32_MIN_ROWS overrides it, read at the call).
  * Returns the number of levels that now read a float copy (0 is valid; the call may be repeated and never switches a
  * level back).  Refused -- print_error, -1, handle unchanged -- for a NULL or 2D handle, ibc != 0, plane relaxation, a
- * handle of cedar_amd_solver_create_many, and when an entry of A or 1/diag overflows float.
+ * handle of cedar_amd_solver_create_many (those take cedar_amd_solver_use_fp32_operator_many below), and when an entry
+ * of A or 1/diag overflows float.
  * What the other calls do on such a handle:
  *   cedar_amd_solver_vcycle        the plain cycle of the ROUNDED operator: iterating it converges to the rounded
  *                                  operator's solution (relative error of order 6e-8 times the condition number);
@@ -427,6 +428,30 @@ void cedar_amd_solver_precondition(cedar_amd_solver *s, real_t *z, const real_t 
 int cedar_amd_solver_use_fp32_operator(cedar_amd_solver *s, int min_rows);
 /* the number of levels whose cycle reads a float copy (0 before the call above, or for a NULL handle) */
 int cedar_amd_solver_fp32_levels(const cedar_amd_solver *s);
+/* The same switch for a handle of cedar_amd_solver_create_many (3D, Dirichlet, point relaxation): the batched sweeps and
+ * the batched residual of the cycle (many3d.hip) read the float copies, so the operator bytes are both halved and paid
+ * once per workgroup task for all right-hand sides.  On a handle that holds one right-hand side (max_rhs 1: made by
+ * cedar_amd_solver_create, or a batch request the handle could not serve -- periodic, plane relaxation) the call forwards
+ * to cedar_amd_solver_use_fp32_operator, so a caller may always use this one.
+ *   Level selection, min_rows (0 = the default, 128; CEDAR_AMD_OP32_MIN_ROWS overrides it), the return value, repetition
+ *   and cedar_amd_solver_fp32_levels are those of cedar_amd_solver_use_fp32_operator; every copy is built and checked
+ *   before the handle changes.  Refused -- print_error, -1, handle unchanged -- for a NULL or 2D handle, ibc != 0, plane
+ *   relaxation, a negative min_rows, and when an entry of A or 1/diag overflows float.
+ * What the other calls do on a switched batch handle:
+ *   cedar_amd_solver_vcycle_many   the plain batched cycle of the ROUNDED operator (reference order; item m has the bits
+ *                                  of cedar_amd_solver_vcycle on a switched single-vector handle under CEDAR_AMD_PSUM=0);
+ *   cedar_amd_solver_pcg_many      the batched cycle is the preconditioner; the recurrences and their residuals use the
+ *                                  FP64 operator given at creation on every item;
+ *   cedar_amd_solver_solve_many    defect correction in lockstep: r = b - A x with the FP64 operator on all items,
+ *                                  z = cycle(0, r) batched on the storage of cedar_amd_solver_pcg_many (allocated by the
+ *                                  first call), x += z; the norms are those of that residual.  Converged items keep
+ *                                  cycling and a zero initial residual counts as converged, as on any batch handle;
+ *   nrhs == 1 and every single-vector entry point (_vcycle, _solve, _pcg, _precondition, _time_*) run the single-vector
+ *                                  float kernels, partial sums included, exactly as on a handle switched by
+ *                                  cedar_amd_solver_use_fp32_operator;
+ *   cedar_amd_solver_set           "A" / "SOR0" on a switched level rebuild its float copy, as above.
+ * cedar_amd_solver_use_fp32_operator itself keeps refusing batch handles. */
+int cedar_amd_solver_use_fp32_operator_many(cedar_amd_solver *s, int min_rows);
 
 /* Several right-hand sides at once on one resident hierarchy.  The operator, 1/diag and the interpolation weights are
  * the same for every right-hand side, so the batched 3D kernels (many3d.hip) fetch them once per workgroup task and apply
@@ -505,6 +530,16 @@ int cedar_amd_pcg_update_many(int nrhs, unsigned active, int zmode, int move, re
 int cedar_amd_relax3_gs_many(int nrhs, real_t *so, real_t *qf, real_t *q, real_t *sor, len_t ii, len_t jj, len_t kk, int nstncl,
                              int updown);
 int cedar_amd_residual3_many(int nrhs, real_t *so, real_t *qf, real_t *q, real_t *res, len_t ii, len_t jj, len_t kk, int nstncl);
+/* The batched 27-point sweep / residual with the operator and 1/diag rounded to single precision (what a level of a batch
+ * handle runs after cedar_amd_solver_use_fp32_operator_many): the contract of cedar_amd_relax3_gs_op32 /
+ * cedar_amd_residual3_op32 on nrhs items back to back.  The float copy is built for the call; always the reference order
+ * (the batch has no partial sums), so item m has the bits of cedar_amd_relax3_gs_op32(frun = 0) / cedar_amd_residual3_op32
+ * on item m alone, and of cedar_amd_relax3_gs_many / cedar_amd_residual3_many on the rounded arrays.  0, or -1 (print_error,
+ * q / res untouched) for nrhs outside 1 .. 32, a NULL array, rows longer than 1024 points, or an entry of so or 1/diag
+ * that overflows float. */
+int cedar_amd_relax3_gs_many_op32(int nrhs, real_t *so, real_t *qf, real_t *q, real_t *sor, len_t ii, len_t jj, len_t kk,
+                                  int updown);
+int cedar_amd_residual3_many_op32(int nrhs, real_t *so, real_t *qf, real_t *q, real_t *res, len_t ii, len_t jj, len_t kk);
 int cedar_amd_restrict3_many(int nrhs, real_t *q, real_t *qc, real_t *ci, len_t ii, len_t jj, len_t kk, len_t iic, len_t jjc,
                              len_t kkc);
 int cedar_amd_interp_add3_many(int nrhs, real_t *q, real_t *qc, real_t *so, real_t *res, real_t *ci, len_t iic, len_t jjc,
