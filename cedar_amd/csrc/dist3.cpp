@@ -18,69 +18,27 @@
 // Transport: the library's RCCL communicator (comm.cpp) -- or a caller-supplied table of three functions, the
 // counterpart of the reference's halo_exchanger plug-in (include/cedar/kernel.h:25-37, kernel_manager::add_halo):
 // the one-GPU rehearsal hands in a host-staged transport so that several ranks can share a card (RCCL refuses that).
-#include "dist_common.h"
-#include <cmath>
+#include "dist_driver.h"
 
 using namespace cedar_amd;
 using namespace cedar_amd::dist;
 
 namespace {
 
-struct DLevel {
-	int n[3] = {0, 0, 0};
-	int II = 0, JJ = 0, KK = 0, nst = 14;
-	size_t npts = 0;
-	real_t *A = nullptr, *P = nullptr, *x = nullptr, *b = nullptr, *res = nullptr, *sor = nullptr;
-	bool ownA = true, overlap = false;
+struct DLevel : LevelBase {
+	bool overlap = false;
 	real_t *strip[2] = {nullptr, nullptr}; // dense copies of the operator columns next to the low / high x face (chain levels)
 	bool chain = false; // x / y split and the level takes the partial-sum sweep: boundary-first chain + one masked launch per k-parity
-	Halo halo;
 };
 
 } // namespace
 
-struct cedar_amd_dist3 : RankCtx {
-	int pre = 2, post = 1, max_iter = 10, min_coarse = 3, overlap_min = 96, agglomerate_below = 64;
-	double tol = 1e-8;
-	int sides = 0;
-	int nlev_global = 1, la = 0;
+struct cedar_amd_dist3 : HandleBase {
+	int overlap_min = 96, sides = 0;
 	std::vector<DLevel> lv;
-	int cn[3] = {0, 0, 0};
-	int gII = 0, gJJ = 0, gKK = 0;
-	real_t *gA = nullptr, *gx = nullptr, *gb = nullptr, *cs_tmp = nullptr;
-	cedar_amd_solver *serial = nullptr;
-	std::map<long, std::pair<real_t *, real_t *>> gbuf;
 };
 
 namespace {
-
-// ---- gather of a level onto every rank (replaces the reference's redistribution solver)
-void gather_into(cedar_amd_dist3 *d, real_t *local, int lII, int lJJ, int lKK, int nplanes, real_t *glob)
-{
-	const int nx = d->cn[0], ny = d->cn[1], nz = d->cn[2];
-	const size_t blk = (size_t)nx * ny * nz;
-	auto it = d->gbuf.find(nplanes);
-	if (it == d->gbuf.end())
-		it = d->gbuf.emplace((long)nplanes, std::make_pair(dmalloc(blk * nplanes), dmalloc(blk * nplanes * d->world))).first;
-	real_t *sb = it->second.first, *rb = it->second.second;
-	const int own[6] = {1, 1, 1, nx, ny, nz};
-	const unsigned long long zero = 0;
-	cedar_amd_box_copy(local, lII, lJJ, lKK, nplanes, 1, own, &zero, sb, 0);
-	tp_allgather(d, sb, rb, blk * nplanes);
-	// unpack every rank's block at its place; the box table of one launch holds 26 boxes
-	for (int r0 = 0; r0 < d->world; r0 += 26) {
-		const int nb = d->world - r0 < 26 ? d->world - r0 : 26;
-		int boxes[26 * 6];
-		unsigned long long offs[26];
-		for (int i = 0; i < nb; i++) {
-			const int r = r0 + i, ci = r % d->p[0], cj = (r / d->p[0]) % d->p[1], ck = r / (d->p[0] * d->p[1]);
-			const int b[6] = {1 + ci * nx, 1 + cj * ny, 1 + ck * nz, nx, ny, nz};
-			memcpy(boxes + 6 * i, b, sizeof(b));
-			offs[i] = (unsigned long long)r * blk;
-		}
-		cedar_amd_box_copy(glob, d->gII, d->gJJ, d->gKK, nplanes, nb, boxes, offs, rb, 1);
-	}
-}
 
 // ---- cycle pieces
 // One k-parity of planes on a rank grid with an x / y split, partial-sum sweep (relax3d_psum.hip).  The plane-fused launch
@@ -250,47 +208,10 @@ void smooth(cedar_amd_dist3 *d, DLevel &L, real_t *x, real_t *b, int updown, int
 	side_wait(d);
 }
 
-// levels la.. : gather the right-hand side, one single-domain cycle (or the direct solve) from a zero initial guess,
-// keep the own block + ghosts straight from the global solution
-void coarse_solve(cedar_amd_dist3 *d, DLevel &C, real_t *x, real_t *b)
-{
-	gather_into(d, b, C.II, C.JJ, C.KK, 1, d->gb);
-	cedar_amd_memset(d->gx, 0, (size_t)d->gII * d->gJJ * d->gKK * sizeof(real_t));
-	cedar_amd_solver_vcycle(d->serial, d->gx, d->gb);
-	const int nx = d->cn[0], ny = d->cn[1], nz = d->cn[2];
-	const unsigned long long zero = 0;
-	const int from[6] = {d->coord[0] * nx, d->coord[1] * ny, d->coord[2] * nz, nx + 2, ny + 2, nz + 2};
-	const int to[6] = {0, 0, 0, nx + 2, ny + 2, nz + 2};
-	cedar_amd_box_copy(d->gx, d->gII, d->gJJ, d->gKK, 1, 1, from, &zero, d->cs_tmp, 0);
-	cedar_amd_box_copy(x, C.II, C.JJ, C.KK, 1, 1, to, &zero, d->cs_tmp, 1);
-}
-
-void cycle(cedar_amd_dist3 *d, int l, real_t *x, real_t *b)
-{
-	DLevel &L = d->lv[l], &K = d->lv[l + 1];
-	smooth(d, L, x, b, BMG_DOWN, d->pre);
-	BMG3_SymStd_residual(1, 1, L.nst == 4, x, b, L.A, L.res, L.II, L.JJ, L.KK, L.nst);
-	halo_exchange(d, L.halo, L.II, L.JJ, L.KK, L.res, 1, 0);
-	BMG3_SymStd_restrict(L.res, K.b, K.P, L.II, L.JJ, L.KK, K.II, K.JJ, K.KK, 0);
-	cedar_amd_memset(K.x, 0, K.npts * sizeof(real_t));
-	if (l + 1 == (int)d->lv.size() - 1) coarse_solve(d, K, K.x, K.b);
-	else cycle(d, l + 1, K.x, K.b);
-	BMG3_SymStd_interp_add(x, K.x, L.A, L.res, K.P, K.II, K.JJ, K.KK, L.II, L.JJ, L.KK, L.nst, 0);
-	halo_exchange(d, L.halo, L.II, L.JJ, L.KK, x, 1, 0);
-	smooth(d, L, x, b, BMG_UP, d->post);
-}
-
-void vcycle(cedar_amd_dist3 *d, real_t *x, real_t *b)
-{
-	if (d->lv.size() == 1) coarse_solve(d, d->lv[0], x, b);
-	else cycle(d, 0, x, b);
-}
-
-double norm(cedar_amd_dist3 *d, DLevel &L, const real_t *r)
-{
-	const double v = cedar_amd_l2norm(r, L.II, L.JJ, L.KK);
-	return std::sqrt(tp_allreduce_sum(d, v * v));
-}
+// what the shared cycle asks of a level (dist_driver.h)
+void residual(DLevel &L, real_t *x, real_t *b, real_t *r) { BMG3_SymStd_residual(1, 1, L.nst == 4, x, b, L.A, r, L.II, L.JJ, L.KK, L.nst); }
+void restrict_residual(DLevel &L, DLevel &K) { BMG3_SymStd_restrict(L.res, K.b, K.P, L.II, L.JJ, L.KK, K.II, K.JJ, K.KK, 0); }
+void interp_add(DLevel &L, DLevel &K, real_t *x) { BMG3_SymStd_interp_add(x, K.x, L.A, L.res, K.P, K.II, K.JJ, K.KK, L.II, L.JJ, L.KK, L.nst, 0); }
 
 // set-up: multilevel.h:243-265 with the MPI flavour's ghost updates
 void setup(cedar_amd_dist3 *d)
@@ -328,21 +249,7 @@ void setup(cedar_amd_dist3 *d)
 					cedar_amd_relax3_strip_build(F.A, F.sor, F.II, F.JJ, F.KK, side, F.strip[side]);
 				}
 	}
-	// level la: the global operator on every rank; the single-domain device-resident solver takes over from there
-	DLevel &C = d->lv.back();
-	for (int t = 0; t < 3; t++) d->cn[t] = C.n[t];
-	d->gII = C.n[0] * d->p[0] + 2; d->gJJ = C.n[1] * d->p[1] + 2; d->gKK = C.n[2] * d->p[2] + 2;
-	const size_t gp = (size_t)d->gII * d->gJJ * d->gKK;
-	d->gA = dmalloc(gp * C.nst);
-	gather_into(d, C.A, C.II, C.JJ, C.KK, C.nst, d->gA);
-	d->gx = dmalloc(gp);
-	d->gb = dmalloc(gp);
-	d->cs_tmp = dmalloc((size_t)(C.n[0] + 2) * (C.n[1] + 2) * (C.n[2] + 2));
-	cedar_amd_settings st;
-	cedar_amd_default_settings(&st);
-	st.nrelax_pre = d->pre; st.nrelax_post = d->post; st.min_coarse = d->min_coarse;
-	st.num_levels = d->nlev_global - d->la;
-	d->serial = cedar_amd_solver_create(3, (len_t)(d->gII - 2), (len_t)(d->gJJ - 2), (len_t)(d->gKK - 2), C.nst, d->gA, 1, &st);
+	setup_serial(d, d->lv.back(), CEDAR_AMD_RELAX_POINT);
 }
 
 } // namespace
@@ -421,91 +328,22 @@ cedar_amd_dist3 *cedar_amd_dist3_create(cedar_amd_comm *comm, const cedar_amd_tr
                                         const int pgrid[3], real_t *A_local, len_t nx, len_t ny, len_t nz, int nstencil,
                                         const cedar_amd_settings *settings, int agglomerate_below, int overlap_min)
 {
-	if (!A_local || !is_device_ptr(A_local) || (nstencil != 14 && nstencil != 4) || world < 1 || rank < 0 || rank >= world) {
-		char m[] = "cedar_amd_dist3_create: A_local must be a device array of a 7- or 27-point operator, 0 <= rank < world";
-		print_error(m);
-		return nullptr;
-	}
-	if (world > 1 && !comm && !(transport && transport->exchange && transport->allgather && transport->allreduce_sum)) {
-		char m[] = "cedar_amd_dist3_create: more than one rank needs a communicator (cedar_amd_comm_create) or a transport table";
-		print_error(m);
-		return nullptr;
-	}
-	cedar_amd_dist3 *d = new cedar_amd_dist3;
-	d->comm = comm;
-	if (transport && transport->exchange) { d->tp = *transport; d->has_tp = true; }
-	d->rank = rank; d->world = world;
-	if (pgrid) { d->p[0] = pgrid[0]; d->p[1] = pgrid[1]; d->p[2] = pgrid[2]; }
-	else cedar_amd_dist3_rank_grid(world, d->p);
-	if (d->p[0] * d->p[1] * d->p[2] != world) {
-		char m[] = "cedar_amd_dist3_create: the rank grid does not multiply to the world size";
-		print_error(m);
-		delete d;
-		return nullptr;
-	}
-	d->coord[0] = rank % d->p[0]; d->coord[1] = (rank / d->p[0]) % d->p[1]; d->coord[2] = rank / (d->p[0] * d->p[1]);
+	static const CreateSpec spec = {"cedar_amd_dist3_create", "7- or 27-point", "does not multiply to the world size", 3, {14, 4}, 0, 14, 26};
+	int pg[3];
+	if (pgrid) { pg[0] = pgrid[0]; pg[1] = pgrid[1]; pg[2] = pgrid[2]; }
+	else cedar_amd_dist3_rank_grid(world, pg);
 	cedar_amd_settings st;
-	if (settings) st = *settings;
-	else cedar_amd_default_settings(&st);
-	d->pre = st.nrelax_pre; d->post = st.nrelax_post; d->max_iter = st.max_iter; d->tol = st.tol; d->min_coarse = st.min_coarse;
-	d->agglomerate_below = agglomerate_below > 0 ? agglomerate_below : 64;
+	cedar_amd_dist3 *d = create_handle<cedar_amd_dist3>(spec, comm, transport, rank, world, pg, A_local, nstencil, settings, agglomerate_below, st);
+	if (!d) return nullptr;
 	d->overlap_min = overlap_min > 0 ? overlap_min : 96;
 	d->sides = (int)has_nb(d, 1, -1) | (int)has_nb(d, 1, +1) << 1 | (int)has_nb(d, 2, -1) << 2 | (int)has_nb(d, 2, +1) << 3;
-	d->scal = dmalloc(8);
-	int n[3] = {(int)nx, (int)ny, (int)nz};
-	// number of levels from the GLOBAL extents (include/cedar/3d/solver.h:54-72)
-	int ng = 0;
-	for (;;) {
-		ng++;
-		int m = 1 << 30;
-		for (int t = 0; t < 3; t++) {
-			const int g = n[t] * d->p[t], c = (g - 1) / (1 << ng) + 1;
-			if (c < m) m = c;
-		}
-		if (m < d->min_coarse) break;
+	const int n[3] = {(int)nx, (int)ny, (int)nz};
+	if (!plan_levels(d, spec, A_local, nstencil, n)) {
+		cedar_amd_dist3_destroy(d);
+		return nullptr;
 	}
-	d->nlev_global = ng;
-	// distributed levels 0 .. la; level la is gathered and handed to the single-domain solver
-	int la = ng - 1, m[3] = {n[0], n[1], n[2]};
-	for (int l = 1; l < ng; l++) {
-		int mn = 1 << 30;
-		for (int t = 0; t < 3; t++) {
-			m[t] = d->p[t] == 1 ? (int)((m[t] - 1) / 2.0 + 1) : m[t] / 2;
-			if (m[t] < mn) mn = m[t];
-		}
-		if (mn <= d->agglomerate_below) { la = l; break; }
-	}
-	d->la = ng > 1 ? (la > 1 ? la : 1) : 0;
-	for (int l = 0; l <= d->la; l++) {
-		DLevel L;
-		for (int t = 0; t < 3; t++) L.n[t] = n[t];
-		for (int t = 0; t < 3; t++)
-			if (d->p[t] > 1 && l < d->la && (n[t] & 1)) {
-				char msg[160];
-				snprintf(msg, sizeof(msg), "cedar_amd_dist3_create: level %d: local extent %d along a split direction must be even", l, n[t]);
-				print_error(msg);
-				cedar_amd_dist3_destroy(d);
-				return nullptr;
-			}
-		L.II = n[0] + 2; L.JJ = n[1] + 2; L.KK = n[2] + 2;
-		L.npts = (size_t)L.II * L.JJ * L.KK;
-		d->lv.push_back(L);
-		DLevel &R = d->lv.back();
-		halo_init(d, R.halo, n);
-		R.overlap = !R.halo.grp[2].idx.empty() && n[0] >= d->overlap_min && n[1] >= d->overlap_min && n[2] >= d->overlap_min;
-		R.res = dmalloc(R.npts);
-		R.sor = dmalloc(2 * R.npts);
-		if (l == 0) {
-			R.A = A_local; R.ownA = false; R.nst = nstencil;
-		} else {
-			R.nst = 14;
-			R.A = dmalloc(14 * R.npts);
-			R.P = dmalloc(26 * R.npts);
-			R.x = dmalloc(R.npts);
-			R.b = dmalloc(R.npts);
-		}
-		for (int t = 0; t < 3; t++) n[t] = d->p[t] == 1 ? (int)((n[t] - 1) / 2.0 + 1) : n[t] / 2;
-	}
+	for (DLevel &L : d->lv)
+		L.overlap = !L.halo.grp[2].idx.empty() && L.n[0] >= d->overlap_min && L.n[1] >= d->overlap_min && L.n[2] >= d->overlap_min;
 	setup(d);
 	if (!d->serial) {
 		cedar_amd_dist3_destroy(d);
@@ -518,19 +356,11 @@ cedar_amd_dist3 *cedar_amd_dist3_create(cedar_amd_comm *comm, const cedar_amd_tr
 void cedar_amd_dist3_destroy(cedar_amd_dist3 *d)
 {
 	if (!d) return;
-	cedar_amd_device_sync();
-	if (d->serial) cedar_amd_solver_destroy(d->serial);
+	destroy_shared(d);
 	for (DLevel &L : d->lv) {
-		if (L.ownA) cedar_amd_free(L.A);
-		else if (L.A) cedar_amd_relax3_release(L.A); // the caller's operator: only its registered solve copy goes
+		if (!L.ownA && L.A) cedar_amd_relax3_release(L.A); // the caller's operator: only its registered solve copy goes
 		cedar_amd_free(L.strip[0]); cedar_amd_free(L.strip[1]);
-		cedar_amd_free(L.P); cedar_amd_free(L.x); cedar_amd_free(L.b); cedar_amd_free(L.res); cedar_amd_free(L.sor);
-		for (auto &kv : L.halo.bufs) { cedar_amd_free(kv.second.first); cedar_amd_free(kv.second.second); }
 	}
-	for (auto &kv : d->gbuf) { cedar_amd_free(kv.second.first); cedar_amd_free(kv.second.second); }
-	cedar_amd_free(d->gA); cedar_amd_free(d->gx); cedar_amd_free(d->gb); cedar_amd_free(d->cs_tmp); cedar_amd_free(d->scal);
-	krylov_free(d);
-	if (d->side) cedar_amd_stream_destroy(d->side);
 	delete d;
 }
 
@@ -550,66 +380,28 @@ void cedar_amd_dist3_vcycle(cedar_amd_dist3 *d, real_t *x, real_t *b)
 	launch_check("cedar_amd_dist3_vcycle");
 }
 
-// multilevel::solve (multilevel.h:277-298) after mpi::solver::solve's halo of the iterate (3d/mpi/solver.h:76-89);
-// rel[0] = ||r0||_2, rel[i] = ||r_i||_2 / ||r0||_2; returns the number of cycles run
 int cedar_amd_dist3_solve(cedar_amd_dist3 *d, real_t *b, real_t *x, real_t *rel)
 {
-	if (!d) return 0;
-	DLevel &L = d->lv[0];
-	halo_exchange(d, L.halo, L.II, L.JJ, L.KK, x, 1, 0);
-	BMG3_SymStd_residual(1, 1, L.nst == 4, x, b, L.A, L.res, L.II, L.JJ, L.KK, L.nst);
-	const double r0 = norm(d, L, L.res);
-	rel[0] = r0;
-	int it = 0;
-	while (it < d->max_iter) {
-		vcycle(d, x, b);
-		BMG3_SymStd_residual(1, 1, L.nst == 4, x, b, L.A, L.res, L.II, L.JJ, L.KK, L.nst);
-		const double r = norm(d, L, L.res) / r0;
-		rel[++it] = r;
-		if (r < d->tol) break;
-	}
-	launch_check("cedar_amd_dist3_solve");
-	return it;
+	return d ? solve(d, b, x, rel, "cedar_amd_dist3_solve") : 0;
 }
 
-// preconditioned conjugate gradient on the rank grid (dist_common.h dist_pcg): the 7- / 27-point level-0 box, the
-// distributed V-cycle as the preconditioner; the 27-point pass reads the row-interleaved copy where setup registered one
+// the 7- / 27-point level-0 box; the 27-point pass reads the row-interleaved copy where setup registered one
 int cedar_amd_dist3_pcg(cedar_amd_dist3 *d, real_t *b, real_t *x, const cedar_amd_pcg_settings *p, real_t *hist)
 {
 	if (!d) return -1;
 	DLevel &L = d->lv[0];
 	const Op3 view = L.nst == 14 ? relax3_op_view(L.A, L.II, L.JJ, L.KK) : Op3{};
-	const PcgBox B{3, L.nst, L.II, L.JJ, L.KK, L.npts, L.A, L.nst == 14 ? &view : nullptr, &L.halo};
-	const int it = dist_pcg(d, B, d->pre, d->post, b, x, p, hist, "cedar_amd_dist3_pcg",
-	                        [&](real_t *xx, const real_t *bb, real_t *r) {
-		                        BMG3_SymStd_residual(1, 1, L.nst == 4, xx, const_cast<real_t *>(bb), L.A, r, L.II, L.JJ, L.KK, L.nst);
-	                        },
-	                        [&](real_t *xx, real_t *bb) { vcycle(d, xx, bb); });
-	launch_check("cedar_amd_dist3_pcg");
-	return it;
+	return pcg(d, b, x, p, hist, L.nst == 14 ? &view : nullptr, "cedar_amd_dist3_pcg");
 }
 
 void cedar_amd_dist3_precondition(cedar_amd_dist3 *d, real_t *z, real_t *r)
 {
-	if (!d) return;
-	DLevel &L = d->lv[0];
-	const PcgBox B{3, L.nst, L.II, L.JJ, L.KK, L.npts, L.A, nullptr, &L.halo};
-	dist_precondition(d, B, d->pre, d->post, z, r, "cedar_amd_dist3_precondition", [&](real_t *xx, real_t *bb) { vcycle(d, xx, bb); });
-	launch_check("cedar_amd_dist3_precondition");
+	if (d) precondition(d, z, r, "cedar_amd_dist3_precondition");
 }
 
-// n level-0 relax sweeps alternating DOWN / UP with their halo exchanges (the roofline microbenchmark of the
-// decomposed path); elapsed milliseconds by HIP events on the library's stream
 float cedar_amd_dist3_time_relax(cedar_amd_dist3 *d, real_t *x, real_t *b, int n)
 {
-	if (!d) return 0.f;
-	void *e0 = cedar_amd_event_record();
-	for (int i = 0; i < n; i++) smooth(d, d->lv[0], x, b, (i & 1) ? BMG_UP : BMG_DOWN, 1);
-	void *e1 = cedar_amd_event_record();
-	const float ms = cedar_amd_event_elapsed_ms(e0, e1);
-	cedar_amd_event_destroy(e0);
-	cedar_amd_event_destroy(e1);
-	return ms;
+	return d ? time_relax(d, x, b, n) : 0.f;
 }
 
 } // extern "C"

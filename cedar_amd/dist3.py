@@ -122,8 +122,63 @@ def _table_from(comm):
     return _Transport(None, *fns), fns
 
 
-class DistSolver3:
+class _DistSolver:
+    """what the two rank-grid solvers share: the transport handed to create, the calls on the handle (`_pre`: the library's
+    function prefix of the dimension)"""
+
+    def _transport(self, comm, world):
+        """(communicator handle, transport table) for create: a NativeComm goes as a handle, any other comm object as a table"""
+        if comm == "loopback":  # measuring aid: one rank of the grid talking to itself (tools/dist_overhead.py)
+            self._tab = _Transport()
+            lib.cedar_amd_transport_loopback(C.byref(self._tab), world)
+            return None, C.byref(self._tab)
+        if isinstance(comm, NativeComm):
+            return comm.h, None
+        if comm is not None and world > 1:
+            self._tab, self._keep = _table_from(comm)  # keep the callbacks alive as long as the solver
+            return None, C.byref(self._tab)
+        return None, None
+
+    def _fn(self, name):
+        return getattr(lib, self._pre + name)
+
+    def vcycle(self, x, b):
+        self._fn("vcycle")(self.h, x.ptr, b.ptr)
+
+    def solve(self, b, x):
+        rel = np.zeros(self.max_iter + 1)
+        n = self._fn("solve")(self.h, b.ptr, x.ptr, rel.ctypes.data)
+        return [float(v) for v in rel[: n + 1]]
+
+    def pcg(self, b, x, max_iter=50, tol=1e-8, stop="rel_l2", precon="mg", nmg_cycles=1):
+        """conjugate gradients preconditioned by the distributed V-cycle (cedar_amd_dist3_pcg / cedar_amd_dist2_pcg),
+        collective: x (local device box) updated in place; returns the history [||r0||, ||r1||/||r0||, ...] with global
+        norms, the same on every rank; RuntimeError on every rank when the library refuses the settings (x untouched)"""
+        return _pcg(self._fn("pcg"), self.h, b, x, max_iter, tol, stop, precon, nmg_cycles)
+
+    def precondition(self, z, r):
+        """z = M^-1 r: one distributed V-cycle from z = 0 (cedar_amd_dist3_precondition / cedar_amd_dist2_precondition),
+        collective"""
+        self._fn("precondition")(self.h, z.ptr, r.ptr)
+
+    def time_relax(self, x, b, n):
+        return float(self._fn("time_relax")(self.h, x.ptr, b.ptr, n))
+
+    def close(self):
+        if self.h:
+            self._fn("destroy")(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001
+            pass
+
+
+class DistSolver3(_DistSolver):
     """cdr3::mpi::solver on one rank's GPU: `A_local` = capi.DeviceArray (nst, nz+2, ny+2, nx+2)"""
+    _pre = "cedar_amd_dist3_"
 
     def __init__(self, comm, rank, world, A_local, pgrid=None, nrelax_pre=2, nrelax_post=1, min_coarse=3, max_iter=10,
                  tol=1e-8, agglomerate_below=64, overlap_min=96):
@@ -136,16 +191,7 @@ class DistSolver3:
         self.max_iter = max_iter
         self.p = tuple(pgrid) if pgrid else rank_grid(world)
         pg = (C.c_int * 3)(*self.p)
-        handle, table = None, None
-        if comm == "loopback":  # measuring aid: one rank of the grid talking to itself (tools/dist_overhead.py)
-            self._tab = _Transport()
-            lib.cedar_amd_transport_loopback(C.byref(self._tab), world)
-            table = C.byref(self._tab)
-        elif isinstance(comm, NativeComm):
-            handle = comm.h
-        elif comm is not None and world > 1:
-            self._tab, self._keep = _table_from(comm)  # keep the callbacks alive as long as the solver
-            table = C.byref(self._tab)
+        handle, table = self._transport(comm, world)
         self.h = lib.cedar_amd_dist3_create(handle, table, rank, world, pg, A_local.ptr, nx, ny, nz, nst, C.byref(st),
                                             agglomerate_below, overlap_min)
         if not self.h:
@@ -154,42 +200,11 @@ class DistSolver3:
         self.chain_levels = lib.cedar_amd_dist3_chain_levels(self.h)
         self.coord = (rank % self.p[0], (rank // self.p[0]) % self.p[1], rank // (self.p[0] * self.p[1]))
 
-    def vcycle(self, x, b):
-        lib.cedar_amd_dist3_vcycle(self.h, x.ptr, b.ptr)
 
-    def solve(self, b, x):
-        rel = np.zeros(self.max_iter + 1)
-        n = lib.cedar_amd_dist3_solve(self.h, b.ptr, x.ptr, rel.ctypes.data)
-        return [float(v) for v in rel[: n + 1]]
-
-    def pcg(self, b, x, max_iter=50, tol=1e-8, stop="rel_l2", precon="mg", nmg_cycles=1):
-        """conjugate gradients preconditioned by the distributed V-cycle (cedar_amd_dist3_pcg), collective: x (local
-        device box) updated in place; returns the history [||r0||, ||r1||/||r0||, ...] with global norms, the same on
-        every rank; RuntimeError on every rank when the library refuses the settings (x untouched)"""
-        return _pcg(lib.cedar_amd_dist3_pcg, self.h, b, x, max_iter, tol, stop, precon, nmg_cycles)
-
-    def precondition(self, z, r):
-        """z = M^-1 r: one distributed V-cycle from z = 0 (cedar_amd_dist3_precondition), collective"""
-        lib.cedar_amd_dist3_precondition(self.h, z.ptr, r.ptr)
-
-    def time_relax(self, x, b, n):
-        return float(lib.cedar_amd_dist3_time_relax(self.h, x.ptr, b.ptr, n))
-
-    def close(self):
-        if self.h:
-            lib.cedar_amd_dist3_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # noqa: BLE001
-            pass
-
-
-class DistSolver2:
+class DistSolver2(_DistSolver):
     """cdr2::mpi::solver on one rank's GPU (cedar_amd_dist2_*, cedar_amd/csrc/dist2.cpp): point relaxation or zebra line
     relaxation with the lines cut by the ranks; `A_local` = capi.DeviceArray (nst, ny+2, nx+2)"""
+    _pre = "cedar_amd_dist2_"
 
     def __init__(self, comm, rank, world, A_local, pgrid=None, relax="point", nrelax_pre=2, nrelax_post=1, min_coarse=3,
                  max_iter=10, tol=1e-8, agglomerate_below=64):
@@ -202,51 +217,10 @@ class DistSolver2:
         self.max_iter = max_iter
         self.p = tuple(pgrid) if pgrid else rank_grid2(world)
         pg = (C.c_int * 2)(*self.p)
-        handle, table = None, None
-        if comm == "loopback":
-            self._tab = _Transport()
-            lib.cedar_amd_transport_loopback(C.byref(self._tab), world)
-            table = C.byref(self._tab)
-        elif isinstance(comm, NativeComm):
-            handle = comm.h
-        elif comm is not None and world > 1:
-            self._tab, self._keep = _table_from(comm)
-            table = C.byref(self._tab)
+        handle, table = self._transport(comm, world)
         self.h = lib.cedar_amd_dist2_create(handle, table, rank, world, pg, A_local.ptr, nx, ny, nst, C.byref(st),
                                             agglomerate_below)
         if not self.h:
             raise RuntimeError("cedar_amd_dist2_create failed")
         self.nlev_global = lib.cedar_amd_dist2_nlevels(self.h)
         self.coord = (rank % self.p[0], rank // self.p[0])
-
-    def vcycle(self, x, b):
-        lib.cedar_amd_dist2_vcycle(self.h, x.ptr, b.ptr)
-
-    def solve(self, b, x):
-        rel = np.zeros(self.max_iter + 1)
-        n = lib.cedar_amd_dist2_solve(self.h, b.ptr, x.ptr, rel.ctypes.data)
-        return [float(v) for v in rel[: n + 1]]
-
-    def pcg(self, b, x, max_iter=50, tol=1e-8, stop="rel_l2", precon="mg", nmg_cycles=1):
-        """conjugate gradients preconditioned by the distributed V-cycle (cedar_amd_dist2_pcg), collective: x (local
-        device box) updated in place; returns the history [||r0||, ||r1||/||r0||, ...] with global norms, the same on
-        every rank; RuntimeError on every rank when the library refuses the settings (x untouched)"""
-        return _pcg(lib.cedar_amd_dist2_pcg, self.h, b, x, max_iter, tol, stop, precon, nmg_cycles)
-
-    def precondition(self, z, r):
-        """z = M^-1 r: one distributed V-cycle from z = 0 (cedar_amd_dist2_precondition), collective"""
-        lib.cedar_amd_dist2_precondition(self.h, z.ptr, r.ptr)
-
-    def time_relax(self, x, b, n):
-        return float(lib.cedar_amd_dist2_time_relax(self.h, x.ptr, b.ptr, n))
-
-    def close(self):
-        if self.h:
-            lib.cedar_amd_dist2_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # noqa: BLE001
-            pass
