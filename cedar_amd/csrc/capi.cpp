@@ -125,6 +125,38 @@ static bool even_periodic(int ipn, len_t iif, len_t jjf, len_t kkf, const char *
 	return true;
 }
 
+// run f(Op3f, stream) on a temporary float copy (common.h Op3f) of so and sor's reciprocal plane: built for the call, back
+// in the pool once the stream has drained.  false = refused (reported), f not run
+template <class F>
+static bool with_op32_copy(const real_t *so, const real_t *sor_msor, int II, int JJ, int KK, const char *who, F &&f)
+{
+	char buf[200];
+	if (II < 3 || JJ < 3 || KK < 3 || (II - 2 + 1) / 2 > 512) {
+		snprintf(buf, sizeof(buf), "%s: extents %d x %d x %d (ghosts included) are not served (rows of 1 .. 1024 points); nothing done",
+		         who, II, JJ, KK);
+		report(buf);
+		return false;
+	}
+	hipStream_t st = current_stream();
+	const size_t bytes = ilv32_floats(II, JJ, KK) * sizeof(float);
+	float *c = static_cast<float *>(pool_get(bytes));
+	int *flag = static_cast<int *>(pool_get(sizeof(int))), host = 0;
+	CEDAR_HIP_CHECK(hipMemsetAsync(flag, 0, sizeof(int), st));
+	ilv32_build(so, sor_msor, c, II, JJ, KK, flag, st);
+	CEDAR_HIP_CHECK(hipMemcpyAsync(&host, flag, sizeof(int), hipMemcpyDeviceToHost, st));
+	CEDAR_HIP_CHECK(hipStreamSynchronize(st));
+	pool_put(flag, sizeof(int));
+	if (host) {
+		snprintf(buf, sizeof(buf), "%s: an entry of the operator or of 1/diag overflows single precision; nothing done", who);
+		report(buf);
+	} else {
+		f(op3f_ilv(c, II, JJ, KK), st);
+		CEDAR_HIP_CHECK(hipStreamSynchronize(st));
+	}
+	pool_put(c, bytes);
+	return !host;
+}
+
 } // namespace cedar_amd
 
 extern "C" {
@@ -541,18 +573,14 @@ int cedar_amd_relax3_planes_masked(real_t *so, real_t *qf, real_t *q, real_t *so
 int cedar_amd_relax3_prepare(const real_t *so, const real_t *sor, len_t ii, len_t jj, len_t kk)
 {
 	if (!is_device_ptr(so) || !is_device_ptr(sor)) return 0; // staged host arrays change address from call to call
-	const char *e = getenv("CEDAR_AMD_ILV");
-	const int mode = e ? atoi(e) : 320;
-	// mode <= 0: no solve copy (the partial-sum scratch is still registered where the sweep wants it)
-	return relax3_prepare(so, sor, (int)ii, (int)jj, (int)kk, mode <= 0 ? -1 : mode == 1 ? 0 : mode, current_stream());
+	// CEDAR_AMD_ILV=0: no solve copy (the partial-sum scratch is still registered where the sweep wants it)
+	return relax3_prepare(so, sor, (int)ii, (int)jj, (int)kk, ilv_min_rows_env(), current_stream());
 }
 
 int cedar_amd_relax3_prepare_rows(const real_t *so, const real_t *sor, len_t ii, len_t jj, len_t kk, int psum_min_rows)
 {
 	if (!is_device_ptr(so) || !is_device_ptr(sor)) return 0;
-	const char *e = getenv("CEDAR_AMD_ILV");
-	const int mode = e ? atoi(e) : 320;
-	return relax3_prepare_rows(so, sor, (int)ii, (int)jj, (int)kk, mode <= 0 ? -1 : mode == 1 ? 0 : mode, psum_min_rows, current_stream());
+	return relax3_prepare_rows(so, sor, (int)ii, (int)jj, (int)kk, ilv_min_rows_env(), psum_min_rows, current_stream());
 }
 
 void cedar_amd_relax3_release(const real_t *so) { relax3_release(so); }
@@ -576,75 +604,30 @@ int cedar_amd_relax3_gs_psum(real_t *so, real_t *qf, real_t *q, real_t *sor, rea
 		relax3_gs(sso.get(), sqf.get(), sq.get(), ssor.get(), (int)ii, (int)jj, (int)kk, 14, updown, current_stream());
 		return 0;
 	}
-	real_t *T = scratch && is_device_ptr(scratch) ? scratch : static_cast<real_t *>(pool_get(P * sizeof(real_t)));
-	relax3_gs27_psum(op3_cedar(sso.get(), ssor.get(), (int)ii, (int)jj, (int)kk), sqf.get(), sq.get(), T, (int)ii, (int)jj,
+	const ScratchLoan T(scratch, P);
+	relax3_gs27_psum(op3_cedar(sso.get(), ssor.get(), (int)ii, (int)jj, (int)kk), sqf.get(), sq.get(), T.p, (int)ii, (int)jj,
 	                 (int)kk, updown, frun, current_stream());
-	if (T != scratch) {
-		CEDAR_HIP_CHECK(hipStreamSynchronize(current_stream()));
-		pool_put(T, P * sizeof(real_t));
-	}
 	return 1;
 }
 
 // ---- the 27-point sweep and residual on a single-precision copy of the operator (include/cedar_amd.h): the copy is
-// built for the call and dropped after it
-namespace {
-
-// temporary float copy (common.h Op3f) of so and sor's reciprocal plane; nullptr = refused (reported)
-float *op32_copy_get(const real_t *so, const real_t *sor_msor, int II, int JJ, int KK, const char *who)
-{
-	char buf[200];
-	if (II < 3 || JJ < 3 || KK < 3 || (II - 2 + 1) / 2 > 512) {
-		snprintf(buf, sizeof(buf), "%s: extents %d x %d x %d (ghosts included) are not served (rows of 1 .. 1024 points); nothing done",
-		         who, II, JJ, KK);
-		report(buf);
-		return nullptr;
-	}
-	hipStream_t st = current_stream();
-	const size_t bytes = ilv32_floats(II, JJ, KK) * sizeof(float);
-	float *c = static_cast<float *>(pool_get(bytes));
-	int *flag = static_cast<int *>(pool_get(sizeof(int))), host = 0;
-	CEDAR_HIP_CHECK(hipMemsetAsync(flag, 0, sizeof(int), st));
-	ilv32_build(so, sor_msor, c, II, JJ, KK, flag, st);
-	CEDAR_HIP_CHECK(hipMemcpyAsync(&host, flag, sizeof(int), hipMemcpyDeviceToHost, st));
-	CEDAR_HIP_CHECK(hipStreamSynchronize(st));
-	pool_put(flag, sizeof(int));
-	if (host) {
-		pool_put(c, bytes);
-		snprintf(buf, sizeof(buf), "%s: an entry of the operator or of 1/diag overflows single precision; nothing done", who);
-		report(buf);
-		return nullptr;
-	}
-	return c;
-}
-
-} // namespace
-
+// built for the call and dropped after it (with_op32_copy)
 int cedar_amd_relax3_gs_op32(real_t *so, real_t *qf, real_t *q, real_t *sor, real_t *scratch, len_t ii, len_t jj, len_t kk,
                              int updown, int frun)
 {
 	const int II = (int)ii, JJ = (int)jj, KK = (int)kk;
 	const size_t P = (size_t)ii * jj * kk;
 	Staged sso(so, P * 14, true, false), sqf(qf, P, true, false), sq(q, P, true, true), ssor(sor, P * 2, true, false);
-	float *c = op32_copy_get(sso.get(), ssor.get() + P, II, JJ, KK, "cedar_amd_relax3_gs_op32");
-	if (!c) return -1;
-	const Op3f A = op3f_ilv(c, II, JJ, KK);
-	hipStream_t st = current_stream();
 	// the run length as relax3_psum_frun applies CEDAR_AMD_FRUN: a plane needs at least four runs
 	const int run = (frun > 0 && JJ - 2 >= 4 * frun) ? frun : 0;
-	int took = 0;
-	if (relax3_psum_ok(II, JJ, KK, run)) {
-		real_t *T = scratch && is_device_ptr(scratch) ? scratch : static_cast<real_t *>(pool_get(P * sizeof(real_t)));
-		relax3_gs27_psum(A, sqf.get(), sq.get(), T, II, JJ, KK, updown, run, st);
-		CEDAR_HIP_CHECK(hipStreamSynchronize(st));
-		if (T != scratch) pool_put(T, P * sizeof(real_t));
-		took = 1;
-	} else {
-		relax3_gs27_op(A, sqf.get(), sq.get(), II, JJ, KK, updown, st); // reference order: plane-fused or row kernels
-		CEDAR_HIP_CHECK(hipStreamSynchronize(st));
-	}
-	pool_put(c, ilv32_floats(II, JJ, KK) * sizeof(float));
-	return took;
+	const bool psum = relax3_psum_ok(II, JJ, KK, run);
+	const bool ran = with_op32_copy(sso.get(), ssor.get() + P, II, JJ, KK, "cedar_amd_relax3_gs_op32", [&](const Op3f &A, hipStream_t st) {
+		if (psum) {
+			const ScratchLoan T(scratch, P);
+			relax3_gs27_psum(A, sqf.get(), sq.get(), T.p, II, JJ, KK, updown, run, st);
+		} else relax3_gs27_op(A, sqf.get(), sq.get(), II, JJ, KK, updown, st); // reference order: plane-fused or row kernels
+	});
+	return ran ? (psum ? 1 : 0) : -1;
 }
 
 int cedar_amd_residual3_op32(real_t *so, real_t *qf, real_t *q, real_t *res, len_t ii, len_t jj, len_t kk)
@@ -653,13 +636,10 @@ int cedar_amd_residual3_op32(real_t *so, real_t *qf, real_t *q, real_t *res, len
 	const size_t P = (size_t)ii * jj * kk;
 	Staged sso(so, P * 14, true, false), sqf(qf, P, true, false), sq(q, P, true, false), sres(res, P, true, true);
 	// 1/diag is not read by the residual: the copy's reciprocal row is filled from the operator's centre plane
-	float *c = op32_copy_get(sso.get(), sso.get(), II, JJ, KK, "cedar_amd_residual3_op32");
-	if (!c) return -1;
-	hipStream_t st = current_stream();
-	residual27_op(op3f_ilv(c, II, JJ, KK), sqf.get(), sq.get(), sres.get(), II, JJ, KK, st);
-	CEDAR_HIP_CHECK(hipStreamSynchronize(st));
-	pool_put(c, ilv32_floats(II, JJ, KK) * sizeof(float));
-	return 0;
+	const bool ran = with_op32_copy(sso.get(), sso.get(), II, JJ, KK, "cedar_amd_residual3_op32", [&](const Op3f &A, hipStream_t st) {
+		residual27_op(A, sqf.get(), sq.get(), sres.get(), II, JJ, KK, st);
+	});
+	return ran ? 0 : -1;
 }
 
 void cedar_amd_relax3_colour7(real_t *so, real_t *qf, real_t *q, real_t *sor, len_t ii, len_t jj, len_t kk, int pts)
@@ -888,7 +868,7 @@ int cedar_amd_residual3_many(int nrhs, real_t *so, real_t *qf, real_t *q, real_t
 	return 0;
 }
 
-// the two 27-point ones on a single-precision copy of the operator built for the call (op32_copy_get), reference order
+// the two 27-point ones on a single-precision copy of the operator built for the call (with_op32_copy), reference order
 int cedar_amd_relax3_gs_many_op32(int nrhs, real_t *so, real_t *qf, real_t *q, real_t *sor, len_t ii, len_t jj, len_t kk, int updown)
 {
 	const char *who = "cedar_amd_relax3_gs_many_op32";
@@ -896,13 +876,10 @@ int cedar_amd_relax3_gs_many_op32(int nrhs, real_t *so, real_t *qf, real_t *q, r
 	const int II = (int)ii, JJ = (int)jj, KK = (int)kk;
 	const size_t P = (size_t)ii * jj * kk;
 	Staged sso(so, P * 14, true, false), sqf(qf, P * nrhs, true, false), sq(q, P * nrhs, true, true), ssor(sor, P * 2, true, false);
-	float *c = op32_copy_get(sso.get(), ssor.get() + P, II, JJ, KK, who);
-	if (!c) return -1;
-	hipStream_t st = current_stream();
-	relax3_gs27_many(op3f_ilv(c, II, JJ, KK), sqf.get(), sq.get(), II, JJ, KK, updown, st, Batch{nrhs, P});
-	CEDAR_HIP_CHECK(hipStreamSynchronize(st));
-	pool_put(c, ilv32_floats(II, JJ, KK) * sizeof(float));
-	return 0;
+	const bool ran = with_op32_copy(sso.get(), ssor.get() + P, II, JJ, KK, who, [&](const Op3f &A, hipStream_t st) {
+		relax3_gs27_many(A, sqf.get(), sq.get(), II, JJ, KK, updown, st, Batch{nrhs, P});
+	});
+	return ran ? 0 : -1;
 }
 
 int cedar_amd_residual3_many_op32(int nrhs, real_t *so, real_t *qf, real_t *q, real_t *res, len_t ii, len_t jj, len_t kk)
@@ -913,13 +890,10 @@ int cedar_amd_residual3_many_op32(int nrhs, real_t *so, real_t *qf, real_t *q, r
 	const size_t P = (size_t)ii * jj * kk;
 	Staged sso(so, P * 14, true, false), sqf(qf, P * nrhs, true, false), sq(q, P * nrhs, true, false), sr(res, P * nrhs, true, true);
 	// 1/diag is not read by the residual: the copy's reciprocal row is filled from the operator's centre plane
-	float *c = op32_copy_get(sso.get(), sso.get(), II, JJ, KK, who);
-	if (!c) return -1;
-	hipStream_t st = current_stream();
-	residual27_many(op3f_ilv(c, II, JJ, KK), sqf.get(), sq.get(), sr.get(), II, JJ, KK, st, Batch{nrhs, P});
-	CEDAR_HIP_CHECK(hipStreamSynchronize(st));
-	pool_put(c, ilv32_floats(II, JJ, KK) * sizeof(float));
-	return 0;
+	const bool ran = with_op32_copy(sso.get(), sso.get(), II, JJ, KK, who, [&](const Op3f &A, hipStream_t st) {
+		residual27_many(A, sqf.get(), sq.get(), sr.get(), II, JJ, KK, st, Batch{nrhs, P});
+	});
+	return ran ? 0 : -1;
 }
 
 int cedar_amd_restrict3_many(int nrhs, real_t *q, real_t *qc, real_t *ci, len_t ii, len_t jj, len_t kk, len_t iic, len_t jjc,

@@ -102,6 +102,12 @@ void ilv32_build(const real_t *so, const real_t *sor_msor, float *ilv, int II, i
 // returns 1 when a copy was built (levels with at least min_rows rows that fit the card's free memory)
 int relax3_prepare(const real_t *so, const real_t *sor, int II, int JJ, int KK, int min_rows, hipStream_t st);
 void relax3_release(const real_t *so);
+// CEDAR_AMD_ILV as relax3_prepare's min_rows: -1 never (0), 0 every 27-point level (1), n levels of at least n rows
+// (n >= 2); default 320.  Read on every call
+int ilv_min_rows_env();
+// does a 27-point level of these extents (ghosts included) take the row-interleaved copy: min_rows >= 0, at least
+// min_rows rows, at most 512 row pairs, and the copy fits beside a 10 % reserve of the card
+bool ilv_level_wanted(int II, int JJ, int KK, int min_rows);
 // the operator view the sweeps of a registered operator read: its row-interleaved copy where there is one, else the planes
 Op3 relax3_op_view(const real_t *so, int II, int JJ, int KK);
 // build the row-interleaved copy from the Cedar-layout operator (14 slots) and 1/diag plane (relax3d.hip)

@@ -119,15 +119,34 @@ void ilv32_build(const real_t *so, const real_t *sor_msor, float *ilv, int II, i
 struct IlvReg { real_t *ilv, *T; int II, JJ, KK, frun; };
 static std::map<const real_t *, IlvReg> g_ilv;
 
+// Which 27-point levels take the row-interleaved copy, for a resident solver's levels (solver.cpp) and for registered
+// operators alike.  Measured (profiles/r02_experiment_ilv_layout_ab.log, r02_experiment_ilv_levels.log): 512^3 relax
+// sweep -7 %, V-cycle -3.8 % with the copy on level 0; slower on levels of 256^3 and below => same threshold as the
+// plane-fused pass.  CEDAR_AMD_ILV: 0 never, 1 every 27-point level, n >= 2 levels with at least n rows; default 320.
+int ilv_min_rows_env()
+{
+	const char *e = getenv("CEDAR_AMD_ILV");
+	const int mode = e ? atoi(e) : 320;
+	return mode <= 0 ? -1 : mode == 1 ? 0 : mode;
+}
+
+// The copy costs 16/14 of the operator again (17.9 GB at 512^3): levels whose copy does not fit beside a 10 % reserve
+// of the card stay on the Cedar layout (1024^3 on one GPU).
+bool ilv_level_wanted(int II, int JJ, int KK, int min_rows)
+{
+	if (min_rows < 0 || JJ - 2 < min_rows || (II - 2 + 1) / 2 > 512) return false;
+	size_t fr = 0, tot = 0;
+	if (hipMemGetInfo(&fr, &tot) != hipSuccess) return false;
+	return ilv_doubles(II, JJ, KK) * sizeof(real_t) + tot / 10 < fr;
+}
+
 // psum_min_rows > 0: the partial-sum sweep from that many rows on (relax3_prepare_rows: the distributed driver on rank grids
 // with an x / y split, where the alternative is not four row-class launches but four passes with an exchange after each)
 static int prepare_impl(const real_t *so, const real_t *sor, int II, int JJ, int KK, int min_rows, int psum_min_rows, hipStream_t st)
 {
 	relax3_release(so);
-	size_t fr = 0, tot = 0;
 	const size_t bytes = ilv_doubles(II, JJ, KK) * sizeof(real_t);
-	const bool want_ilv = min_rows >= 0 && JJ - 2 >= min_rows && (II - 2 + 1) / 2 <= 512 && hipMemGetInfo(&fr, &tot) == hipSuccess
-	                      && bytes + tot / 10 < fr;
+	const bool want_ilv = ilv_level_wanted(II, JJ, KK, min_rows);
 	int frun = relax3_psum_frun(JJ);
 	const char *ep = getenv("CEDAR_AMD_PSUM"), *ef = getenv("CEDAR_AMD_FRUN");
 	if (!frun && psum_min_rows > 0 && JJ - 2 >= psum_min_rows && !ef) frun = 8;

@@ -56,6 +56,23 @@ struct Level {
 	struct PlaneSet *pl[3] = {nullptr, nullptr, nullptr};
 };
 
+// Which stored form of a 27-point level's operator a kernel reads is decided by these two selectors and nowhere else.
+// The exact view: the operator the caller gave, as the reported residual and the Krylov passes read it -- the
+// row-interleaved copy (the same doubles) where the level keeps one, else the Cedar planes; never the float copy.
+Op3 exact_view27(const Level &L)
+{
+	return L.Ailv ? op3_ilv(L.Ailv, L.II, L.JJ, L.KK) : op3_cedar(L.A, L.SOR0, L.II, L.JJ, L.KK);
+}
+
+// The cycle's view, as the sweeps and the cycle's residual read it: the float copy where the level keeps it (it has
+// released Ailv, so the exact view there is the unrounded planes, which the cycle must not mix in), else the exact view.
+// f takes const auto &: Op3f or Op3, served by the overloads of relax3_gs27_op, residual27_op and the *_many pair.
+template <class F> void with_cycle_view27(const Level &L, F &&f)
+{
+	if (L.A32) f(op3f_ilv(L.A32, L.II, L.JJ, L.KK));
+	else f(exact_view27(L));
+}
+
 // include/cedar/3d/relax_planes.h:164-246.  The reference keeps one 2D solver per plane; copy_coeff gives all of
 // them the same operator (planes.hip), so one hierarchy is set up and the others share its set-up products.  Planes
 // of one colour are independent: instance q serves the planes 2q+1 and 2q+2 (one of each colour) on fixed 2D vectors
@@ -178,50 +195,25 @@ void clear(real_t *p, size_t n, hipStream_t st)
 	else zero_fill(p, n, st);
 }
 
-// Row-interleaved solve copy of a 27-point level (common.h Op3): read by relax and residual instead of the fourteen
-// Cedar-layout planes.  Measured (profiles/r02_experiment_ilv_layout_ab.log, r02_experiment_ilv_levels.log): 512^3 relax
-// sweep -7 %, V-cycle -3.8 % with the copy on level 0; slower on levels of 256^3 and below => same threshold as the
-// plane-fused pass.  CEDAR_AMD_ILV: 0 never, 1 every 27-point level, n >= 2 levels with at least n rows; default 320.
-// The copy costs 16/14 of the operator again (17.9 GB at 512^3): levels whose copy does not fit beside a 10 % reserve
-// of the card stay on the Cedar layout (1024^3 on one GPU).
-bool ilv_wanted(const Level &L)
-{
-	const char *e = getenv("CEDAR_AMD_ILV");
-	const int mode = e ? atoi(e) : 320;
-	if (mode <= 0 || (L.II - 2 + 1) / 2 > 512) return false;
-	if (!(mode == 1 || L.ny >= mode)) return false;
-	size_t fr = 0, tot = 0;
-	if (hipMemGetInfo(&fr, &tot) != hipSuccess) return false;
-	return ilv_doubles(L.II, L.JJ, L.KK) * sizeof(real_t) + tot / 10 < fr;
-}
-
-// the view of a 27-point level that its kernels read: the row-interleaved copy where the level keeps one, else the planes
-Op3 op3_of(const Level &L)
-{
-	return L.Ailv ? op3_ilv(L.Ailv, L.II, L.JJ, L.KK) : op3_cedar(L.A, L.SOR0, L.II, L.JJ, L.KK);
-}
-
-// the cycle's residual on a level: with the level's solve copy where it keeps one (A32: the operator rounded to float)
+// the cycle's residual on a level.  3D 27-point: through the cycle's view; a single vector on a level without a copy of
+// its own, and 7-point levels, go through residual3, which finds a copy that the operator's owner registered (relax3d.hip)
 void residual(const cedar_amd_solver *s, const Level &L, const real_t *x, const real_t *b, real_t *r, hipStream_t st)
 {
-	if (s->nd == 2) residual2(L.A, b, x, r, L.II, L.JJ, L.nst, st, Batch{s->nb, L.npts});
-	// (A32 before op3_of: a level that keeps the float copy has released Ailv, and op3_of would hand out the unrounded planes)
-	else if (s->nb > 1 && L.A32) residual27_many(op3f_ilv(L.A32, L.II, L.JJ, L.KK), b, x, r, L.II, L.JJ, L.KK, st, Batch{s->nb, L.npts});
-	else if (s->nb > 1 && L.nst == 14) residual27_many(op3_of(L), b, x, r, L.II, L.JJ, L.KK, st, Batch{s->nb, L.npts});
-	else if (s->nb > 1) residual7_many(L.A, b, x, r, L.II, L.JJ, L.KK, st, Batch{s->nb, L.npts});
-	else if (L.A32) residual27_op(op3f_ilv(L.A32, L.II, L.JJ, L.KK), b, x, r, L.II, L.JJ, L.KK, st);
-	else if (L.Ailv) residual27_op(op3_of(L), b, x, r, L.II, L.JJ, L.KK, st);
+	const Batch bt{s->nb, L.npts};
+	if (s->nd == 2) residual2(L.A, b, x, r, L.II, L.JJ, L.nst, st, bt);
+	else if (s->nb > 1 && L.nst != 14) residual7_many(L.A, b, x, r, L.II, L.JJ, L.KK, st, bt);
+	else if (s->nb > 1) with_cycle_view27(L, [&](const auto &A) { residual27_many(A, b, x, r, L.II, L.JJ, L.KK, st, bt); });
+	else if (L.A32 || L.Ailv) with_cycle_view27(L, [&](const auto &A) { residual27_op(A, b, x, r, L.II, L.JJ, L.KK, st); });
 	else residual3(L.A, b, x, r, L.II, L.JJ, L.KK, L.nst, st);
 }
 
-// r = b - A x with the operator the caller gave: what a solve reports and what the Krylov recurrence starts from.  On a
-// level that keeps the single-precision copy this reads the FP64 planes, not the copy (a batch: every item)
+// r = b - A x with the operator the caller gave: what a solve reports and what the Krylov recurrence starts from.  The
+// cycle's residual, except on a level that keeps the float copy: there the same launches on the exact view
 void residual_true(const cedar_amd_solver *s, const Level &L, const real_t *x, const real_t *b, real_t *r, hipStream_t st)
 {
-	if (L.A32 && s->nb > 1)
-		residual27_many(op3_cedar(L.A, L.SOR0, L.II, L.JJ, L.KK), b, x, r, L.II, L.JJ, L.KK, st, Batch{s->nb, L.npts});
-	else if (L.A32) residual3(L.A, b, x, r, L.II, L.JJ, L.KK, L.nst, st);
-	else residual(s, L, x, b, r, st);
+	if (!L.A32) residual(s, L, x, b, r, st);
+	else if (s->nb > 1) residual27_many(exact_view27(L), b, x, r, L.II, L.JJ, L.KK, st, Batch{s->nb, L.npts});
+	else residual3(L.A, b, x, r, L.II, L.JJ, L.KK, L.nst, st);
 }
 
 // one y-line sweep: on the transposed arrays when the level keeps them
@@ -409,15 +401,13 @@ void smooth(const cedar_amd_solver *s, const Level &L, real_t *x, const real_t *
 		}
 		if (s->nd == 3 && s->nb > 1) { // a batch of right-hand sides: reference order, operator fetched once (many3d.hip)
 			const Batch bt{s->nb, L.npts};
-			if (L.A32) relax3_gs27_many(op3f_ilv(L.A32, L.II, L.JJ, L.KK), b, x, L.II, L.JJ, L.KK, updown, st, bt); // before op3_of
-			else if (L.nst == 14) relax3_gs27_many(op3_of(L), b, x, L.II, L.JJ, L.KK, updown, st, bt);
-			else relax3_gs7_many(L.A, b, x, L.SOR0, L.II, L.JJ, L.KK, updown, st, bt);
+			if (L.nst != 14) relax3_gs7_many(L.A, b, x, L.SOR0, L.II, L.JJ, L.KK, updown, st, bt);
+			else with_cycle_view27(L, [&](const auto &A) { relax3_gs27_many(A, b, x, L.II, L.JJ, L.KK, updown, st, bt); });
 			continue;
 		}
-		if (s->nd == 3) {
-			if (L.A32) relax3_gs27_op(op3f_ilv(L.A32, L.II, L.JJ, L.KK), b, x, L.II, L.JJ, L.KK, updown, st, L.T);
-			else if (L.Ailv || L.T) relax3_gs27_op(op3_of(L), b, x, L.II, L.JJ, L.KK, updown, st, L.T);
-			else relax3_gs(L.A, b, x, L.SOR0, L.II, L.JJ, L.KK, L.nst, updown, st);
+		if (s->nd == 3) { // without a copy or scratch of its own: relax3_gs, which finds what the operator's owner registered
+			if (!L.A32 && !L.Ailv && !L.T) relax3_gs(L.A, b, x, L.SOR0, L.II, L.JJ, L.KK, L.nst, updown, st);
+			else with_cycle_view27(L, [&](const auto &A) { relax3_gs27_op(A, b, x, L.II, L.JJ, L.KK, updown, st, L.T); });
 			continue;
 		}
 		const int ipn = s->st.ibc;
@@ -806,7 +796,7 @@ static cedar_amd_solver *solver_create(int nd, len_t nx, len_t ny, len_t nz, int
 				continue;
 			}
 			setup_recip(F.A, F.SOR0 + F.npts, F.II, F.JJ, F.KK, st);
-			if (F.nst == 14 && !s->st.ibc && ilv_wanted(F)) {
+			if (F.nst == 14 && !s->st.ibc && ilv_level_wanted(F.II, F.JJ, F.KK, ilv_min_rows_env())) {
 				F.Ailv = dalloc_raw(ilv_doubles(F.II, F.JJ, F.KK));
 				ilv_build(F.A, F.SOR0 + F.npts, F.Ailv, F.II, F.JJ, F.KK, st);
 			}
@@ -1295,7 +1285,8 @@ static int pcg_run(cedar_amd_solver *s, int nrhs, const real_t *b, real_t *x, co
 	const PcgRule rule = pcg_rule(p);
 	const int zm = rule.zm;
 	real_t *Z = zm == 0 ? s->kr : s->kz;
-	const Op3 view = op3_of(L);
+	const Op3 view = exact_view27(L);
+	const Op3 *op27 = L.Ailv ? &view : nullptr; // (nullptr: the passes read the planes L.A themselves)
 	const size_t ld = (size_t)p.max_iter + 1; // row length of hist
 	double sc[CEDAR_AMD_MAX_RHS * PCG_NSC], r0[CEDAR_AMD_MAX_RHS], m0[CEDAR_AMD_MAX_RHS];
 	int itm[CEDAR_AMD_MAX_RHS];
@@ -1303,10 +1294,9 @@ static int pcg_run(cedar_amd_solver *s, int nrhs, const real_t *b, real_t *x, co
 	// the two passes on the active items; update: pn = nullptr leaves x and r where they are (dot products only)
 	auto direction = [&](const real_t *pold, real_t *pn, bool first) {
 		if (nrhs == 1)
-			pcg_direction(L.A, L.Ailv ? &view : nullptr, Z, pold, pn, s->kw, s->nd, L.nst, L.II, L.JJ, L.KK, first, s->kslab, s->ksc, st);
+			pcg_direction(L.A, op27, Z, pold, pn, s->kw, s->nd, L.nst, L.II, L.JJ, L.KK, first, s->kslab, s->ksc, st);
 		else
-			pcg_direction_many(L.A, L.Ailv ? &view : nullptr, Z, pold, pn, s->kw, s->nd, L.nst, L.II, L.JJ, L.KK, first, s->kslab,
-			                   s->ksc, st, bt, active);
+			pcg_direction_many(L.A, op27, Z, pold, pn, s->kw, s->nd, L.nst, L.II, L.JJ, L.KK, first, s->kslab, s->ksc, st, bt, active);
 	};
 	auto update = [&](int zmode, const real_t *pn, bool first) {
 		const real_t *w = pn ? s->kw : nullptr;

@@ -60,4 +60,22 @@ private:
 	real_t *dev_;
 };
 
+// A scratch vector for one call (T of the 27-point partial-sum sweep): the caller's device array where they passed one,
+// else a pool block, which goes back to the pool when the scope ends, after the stream has drained.
+struct ScratchLoan {
+	real_t *p;
+	const size_t bytes; // of the pool block; 0: p is the caller's
+	ScratchLoan(real_t *scratch, size_t doubles) : p(scratch), bytes(scratch && is_device_ptr(scratch) ? 0 : doubles * sizeof(real_t))
+	{
+		if (bytes) p = static_cast<real_t *>(pool_get(bytes));
+	}
+	~ScratchLoan()
+	{
+		if (!bytes) return;
+		CEDAR_HIP_CHECK(hipStreamSynchronize(current_stream()));
+		pool_put(p, bytes);
+	}
+	ScratchLoan(const ScratchLoan &) = delete;
+};
+
 } // namespace cedar_amd

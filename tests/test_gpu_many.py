@@ -230,6 +230,66 @@ def test_cycle_and_solve_many_on_a_partial_sum_sized_level(capi, monkeypatch):
     _check_cycle_and_solve(capi, so, st, b, single)
 
 
+def test_levels_with_the_row_interleaved_copy_give_the_same_bits(capi, monkeypatch):
+    """a single-vector and a batch handle whose two smoothed 27-point levels keep the row-interleaved solve copy
+    (CEDAR_AMD_ILV=1; by default only levels of 320 rows do) against the same pair on the Cedar planes (CEDAR_AMD_ILV=0):
+    the copy holds the same doubles, so the cycle, the solve and conjugate gradients (on these V(2,1) handles with the
+    diagonal preconditioner, on a V(2,2) pair with the cycle as preconditioner) give the same bits"""
+    mk_op, mk_rhs, st = cases.SOLVES["fe27_40x33x50_v21"]
+    so, b = mk_op(), _rhs_items(mk_rhs)
+    monkeypatch.setenv("CEDAR_AMD_PSUM", "0")
+    monkeypatch.delenv("CEDAR_AMD_FRUN", raising=False)
+
+    def handles(ilv, st):
+        monkeypatch.setenv("CEDAR_AMD_ILV", ilv)
+        s1 = capi.Solver(so, **st)
+        monkeypatch.setenv("CEDAR_AMD_ILV", ilv)
+        return s1, capi.Solver(so, max_rhs=3, **st)
+
+    def pcg(out, s1, sm, tag, **kw):
+        for m in range(3):
+            x = np.zeros_like(b[m])
+            out[tag, "pcg hist", m], out[tag, "pcg x", m] = s1.pcg(b[m], x, **kw), x
+        x = np.zeros_like(b)
+        hist, iters = sm.pcg_many(b, x, **kw)
+        out[tag, "pcg_many x"], out[tag, "pcg_many iters"] = x, iters
+        for m in range(3):
+            out[tag, "pcg_many hist", m] = hist[m]
+
+    def run(ilv):
+        out = {}
+        s1, sm = handles(ilv, st)  # the case's V(2,1) cycle
+        for m in range(3):
+            x = np.zeros_like(b[m])
+            s1.vcycle(x, b[m])
+            out["vcycle", m] = x
+            x = np.zeros_like(b[m])
+            out["solve hist", m], out["solve x", m] = s1.solve(b[m], x), x
+        x = np.zeros_like(b)
+        sm.vcycle_many(x, b)
+        out["vcycle_many"] = x
+        x = np.zeros_like(b)
+        rel, iters = sm.solve_many(b, x)
+        out["solve_many x"], out["solve_many iters"] = x, iters
+        for m in range(3):
+            out["solve_many hist", m] = rel[m]
+        pcg(out, s1, sm, "diag", precon="diag", max_iter=25)  # (the multigrid preconditioner wants a symmetric cycle)
+        s1.close()
+        sm.close()
+        s1, sm = handles(ilv, dict(st, nrelax_post=st["nrelax_pre"]))
+        pcg(out, s1, sm, "mg")
+        s1.close()
+        sm.close()
+        return out
+
+    planes, copy = run("0"), run("1")
+    assert planes.keys() == copy.keys()
+    for k in planes:
+        assert np.array_equal(planes[k], copy[k]), k
+    for m in range(3):
+        assert np.array_equal(copy["vcycle_many"][m], copy["vcycle", m]), m
+
+
 # ------------------------------------------------------------------ 4. against the reference itself
 @pytest.mark.parametrize("name", ["fe27_65_v21", "fe27_40x33x50_v21", "poisson7_65_v21"], ids=str)
 def test_solve_many_history_vs_reference_golden(capi, golden, name):
