@@ -404,6 +404,21 @@ class Kernels:
                                          u(grid[-1]), u(grid[-2]), u(grid[0] if len(grid) == 3 else 1), int(first), _p(sc)) != 0:
             raise RuntimeError("cedar_amd_pcg_update_many refused")
 
+    def pcg_dots_wz(self, r, z, w, first, sc):
+        """flexible CG's dots after the preconditioner: r.r, r.z, w.z, beta = -((alpha w.z) / rho), rho = r.z -> sc"""
+        assert all(a is None or a.shape == r.shape for a in (z, w)) and sc.size == 8
+        if lib.cedar_amd_pcg_dots_wz(_p(r), _p(z), _p(w), *self._dims(r), int(first), _p(sc)) != 0:
+            raise RuntimeError("cedar_amd_pcg_dots_wz refused")
+
+    def pcg_dots_wz_many(self, r, z, w, first, sc, nrhs=None, active=None):
+        """per item m: pcg_dots_wz -> sc[m]"""
+        assert all(a is None or a.shape == r.shape for a in (z, w))
+        n, act = self._batch(r, sc, nrhs, active)
+        grid = r.shape[1:]
+        if lib.cedar_amd_pcg_dots_wz_many(n, act, _p(r), _p(z), _p(w), u(grid[-1]), u(grid[-2]),
+                                          u(grid[0] if len(grid) == 3 else 1), int(first), _p(sc)) != 0:
+            raise RuntimeError("cedar_amd_pcg_dots_wz_many refused")
+
     def pcg_rank_scalars(self, which, zmode, gathered, world, stride, first, sc):
         """which 0: alpha from the ranks' sigma; 1: rho / beta from their r.r (and r.z); summed in rank order"""
         assert sc.size == 8 and gathered.size >= world * stride
@@ -497,6 +512,10 @@ lib.cedar_amd_solver_precondition.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p
 lib.cedar_amd_solver_pcg_many.restype = C.c_int
 lib.cedar_amd_solver_pcg_many.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(PcgSettings), C.c_void_p,
                                           C.POINTER(C.c_int)]
+lib.cedar_amd_solver_fcg.restype = C.c_int
+lib.cedar_amd_solver_fcg.argtypes = lib.cedar_amd_solver_pcg.argtypes
+lib.cedar_amd_solver_fcg_many.restype = C.c_int
+lib.cedar_amd_solver_fcg_many.argtypes = lib.cedar_amd_solver_pcg_many.argtypes
 lib.cedar_amd_solver_use_fp32_operator.restype = C.c_int
 lib.cedar_amd_solver_use_fp32_operator.argtypes = [C.c_void_p, C.c_int]
 lib.cedar_amd_solver_use_fp32_operator_many.restype = C.c_int
@@ -599,21 +618,15 @@ class Solver:
         n = lib.cedar_amd_solver_solve(self.h, _vp(b), _vp(x), rel.ctypes.data)
         return rel[: n + 1]
 
-    def pcg(self, b, x, max_iter=50, tol=1e-8, stop="rel_l2", precon="mg", nmg_cycles=1):
-        """conjugate gradients preconditioned by the cycle (cedar_amd_solver_pcg): x updated in place; returns the
-        history [||r0||, ||r1||/||r0||, ...]; RuntimeError when the library refuses the settings (x untouched)"""
+    def _cg(self, call, b, x, max_iter, tol, stop, precon, nmg_cycles):
         ps = PcgSettings(int(max_iter), float(tol), PCG_STOP[stop], PCG_PRECON[precon], int(nmg_cycles))
         hist = np.zeros(max(int(max_iter), 0) + 1)
-        n = lib.cedar_amd_solver_pcg(self.h, _vp(b), _vp(x), C.byref(ps), hist.ctypes.data)
+        n = getattr(lib, call)(self.h, _vp(b), _vp(x), C.byref(ps), hist.ctypes.data)
         if n < 0:
-            raise RuntimeError("cedar_amd_solver_pcg refused the settings (see the printed reason)")
+            raise RuntimeError(call + " refused the settings (see the printed reason)")
         return hist[: n + 1]
 
-    def pcg_many(self, b, x, max_iter=50, tol=1e-8, stop="rel_l2", precon="mg", nmg_cycles=1, hist=None):
-        """pcg for the items of b, x of shape (nrhs,) + grid in lockstep (cedar_amd_solver_pcg_many): an item that has
-        stopped is left alone, so x[m] and its history are those of pcg on item m.  Returns (hist_rows, iters): row m cut
-        to iters[m] + 1 entries.  hist: optional (nrhs, max_iter + 1) array the library writes into.  RuntimeError when
-        the library refuses (x and hist untouched)."""
+    def _cg_many(self, call, b, x, max_iter, tol, stop, precon, nmg_cycles, hist):
         nrhs = self._nrhs(x, b)
         ps = PcgSettings(int(max_iter), float(tol), PCG_STOP[stop], PCG_PRECON[precon], int(nmg_cycles))
         ld = max(int(max_iter), 0) + 1
@@ -621,11 +634,32 @@ class Solver:
             hist = np.zeros((nrhs, ld))
         assert hist.shape == (nrhs, ld) and hist.dtype == np.float64 and hist.flags["C_CONTIGUOUS"]
         iters = np.zeros(nrhs, dtype=np.int32)
-        n = lib.cedar_amd_solver_pcg_many(self.h, nrhs, _vp(b), _vp(x), C.byref(ps), hist.ctypes.data,
-                                          iters.ctypes.data_as(C.POINTER(C.c_int)))
+        n = getattr(lib, call)(self.h, nrhs, _vp(b), _vp(x), C.byref(ps), hist.ctypes.data,
+                               iters.ctypes.data_as(C.POINTER(C.c_int)))
         if n < 0:
-            raise RuntimeError("cedar_amd_solver_pcg_many refused (see the printed reason)")
+            raise RuntimeError(call + " refused (see the printed reason)")
         return [hist[m, : int(iters[m]) + 1] for m in range(nrhs)], [int(v) for v in iters]
+
+    def pcg(self, b, x, max_iter=50, tol=1e-8, stop="rel_l2", precon="mg", nmg_cycles=1):
+        """conjugate gradients preconditioned by the cycle (cedar_amd_solver_pcg): x updated in place; returns the
+        history [||r0||, ||r1||/||r0||, ...]; RuntimeError when the library refuses the settings (x untouched)"""
+        return self._cg("cedar_amd_solver_pcg", b, x, max_iter, tol, stop, precon, nmg_cycles)
+
+    def pcg_many(self, b, x, max_iter=50, tol=1e-8, stop="rel_l2", precon="mg", nmg_cycles=1, hist=None):
+        """pcg for the items of b, x of shape (nrhs,) + grid in lockstep (cedar_amd_solver_pcg_many): an item that has
+        stopped is left alone, so x[m] and its history are those of pcg on item m.  Returns (hist_rows, iters): row m cut
+        to iters[m] + 1 entries.  hist: optional (nrhs, max_iter + 1) array the library writes into.  RuntimeError when
+        the library refuses (x and hist untouched)."""
+        return self._cg_many("cedar_amd_solver_pcg_many", b, x, max_iter, tol, stop, precon, nmg_cycles, hist)
+
+    def fcg(self, b, x, max_iter=50, tol=1e-8, stop="rel_l2", precon="mg", nmg_cycles=1):
+        """flexible conjugate gradients (cedar_amd_solver_fcg): pcg with the Polak-Ribiere beta, so any cycle of the
+        handle may be the preconditioner -- V(m,n), F-cycles, plane relaxation.  Same arguments and return as pcg"""
+        return self._cg("cedar_amd_solver_fcg", b, x, max_iter, tol, stop, precon, nmg_cycles)
+
+    def fcg_many(self, b, x, max_iter=50, tol=1e-8, stop="rel_l2", precon="mg", nmg_cycles=1, hist=None):
+        """fcg for the items of b, x in lockstep (cedar_amd_solver_fcg_many); same arguments and return as pcg_many"""
+        return self._cg_many("cedar_amd_solver_fcg_many", b, x, max_iter, tol, stop, precon, nmg_cycles, hist)
 
     def precondition(self, z, r):
         """z = M^-1 r: one cycle from z = 0 (cedar_amd_solver_precondition)"""

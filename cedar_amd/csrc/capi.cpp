@@ -674,7 +674,7 @@ void cedar_amd_box_copy_strided(real_t *arr, len_t ii, len_t jj, len_t kk, int n
 // ------------------------------------------------------------------ the passes of a CG iteration (krylov.hip)
 static_assert(CEDAR_AMD_PCG_RHO == PCG_RHO && CEDAR_AMD_PCG_SIGMA == PCG_SIGMA && CEDAR_AMD_PCG_ALPHA == PCG_ALPHA
                   && CEDAR_AMD_PCG_BETA == PCG_BETA && CEDAR_AMD_PCG_RR == PCG_RR && CEDAR_AMD_PCG_RZ == PCG_RZ
-                  && CEDAR_AMD_PCG_FLAG == PCG_FLAG && CEDAR_AMD_PCG_NSC == PCG_NSC,
+                  && CEDAR_AMD_PCG_FLAG == PCG_FLAG && CEDAR_AMD_PCG_WZ == PCG_WZ && CEDAR_AMD_PCG_NSC == PCG_NSC,
               "the scalar slots of include/cedar_amd.h are those of common.h");
 
 namespace {
@@ -791,6 +791,34 @@ int cedar_amd_pcg_update_many(int nrhs, unsigned active, int zmode, int move, re
 	    sd(zmode == 1 ? diag : nullptr, P, true, false), ssc(sc, (size_t)PCG_NSC * nrhs, true, true);
 	pcg_update_many(zmode, mv, sx.get(), sr.get(), sp.get(), sw.get(), sz.get(), sd.get(), (int)ii, (int)jj, (int)kk,
 	                first != 0, slab.dev, ssc.get(), current_stream(), Batch{nrhs, P}, active);
+	return 0;
+}
+
+// the dots of flexible CG after the preconditioner (krylov.hip pcg_dwz / pcg_dwz_many); no vector is written
+int cedar_amd_pcg_dots_wz(const real_t *r, const real_t *z, const real_t *w, len_t ii, len_t jj, len_t kk, int first, real_t *sc)
+{
+	const char *who = "cedar_amd_pcg_dots_wz";
+	if (pcg_shape_refused(ii, jj, kk, who)) return -1;
+	if (!r || !z || !w || !sc) return pcg_refuse(who, "a required array is NULL"), -1;
+	const size_t P = (size_t)ii * jj * kk;
+	NanSlab slab(pcg_slab_doubles(kk == 1 ? 2 : 3, kk == 1 ? 3 : 4, (int)ii, (int)jj, (int)kk));
+	Staged sr(r, P, true, false), sz(z, P, true, false), sw(w, P, true, false), ssc(sc, PCG_NSC, true, true);
+	pcg_dots_wz(sr.get(), sz.get(), sw.get(), (int)ii, (int)jj, (int)kk, first != 0, slab.dev, ssc.get(), current_stream());
+	return 0;
+}
+
+int cedar_amd_pcg_dots_wz_many(int nrhs, unsigned active, const real_t *r, const real_t *z, const real_t *w, len_t ii, len_t jj,
+                               len_t kk, int first, real_t *sc)
+{
+	const char *who = "cedar_amd_pcg_dots_wz_many";
+	if (nrhs < 1 || nrhs > CEDAR_AMD_MAX_RHS) return pcg_refuse(who, "nrhs must be 1 .. 32"), -1;
+	if (pcg_shape_refused(ii, jj, kk, who)) return -1;
+	if (!r || !z || !w || !sc) return pcg_refuse(who, "a required array is NULL"), -1;
+	const size_t P = (size_t)ii * jj * kk, N = P * nrhs;
+	NanSlab slab(pcg_slab_doubles(kk == 1 ? 2 : 3, kk == 1 ? 3 : 4, (int)ii, (int)jj, (int)kk) * nrhs);
+	Staged sr(r, N, true, false), sz(z, N, true, false), sw(w, N, true, false), ssc(sc, (size_t)PCG_NSC * nrhs, true, true);
+	pcg_dots_wz_many(sr.get(), sz.get(), sw.get(), (int)ii, (int)jj, (int)kk, first != 0, slab.dev, ssc.get(), current_stream(),
+	                 Batch{nrhs, P}, active);
 	return 0;
 }
 

@@ -282,7 +282,7 @@ void solve_cg3(real_t *q, const real_t *qf, int II, int JJ, int KK, const real_t
                Batch bt = Batch()); // bbd: nabd2 doubles per batch item
 // krylov.hip: the vector work of the preconditioned conjugate gradient (solver.cpp cedar_amd_solver_pcg).  The scalars
 // of a run live on the device in sc[PCG_NSC]; the kernels read alpha / beta from there and write them back.
-enum { PCG_RHO = 0, PCG_SIGMA = 1, PCG_ALPHA = 2, PCG_BETA = 3, PCG_RR = 4, PCG_RZ = 5, PCG_FLAG = 6, PCG_NSC = 8 };
+enum { PCG_RHO = 0, PCG_SIGMA = 1, PCG_ALPHA = 2, PCG_BETA = 3, PCG_RR = 4, PCG_RZ = 5, PCG_FLAG = 6, PCG_WZ = 7, PCG_NSC = 8 };
 // What a run's settings decide on the host, for the resident solver and the rank grid alike (solver.cpp pcg_run,
 // dist_common.h dist_pcg).  zm: where z = M^-1 r comes from, 0 z = r, 1 z = r / diag, 2 the multigrid cycle; the stop test
 // is on ||r||_2, or with mnorm on sqrt(r.z), relative (rel) to its initial value or absolute.
@@ -330,7 +330,14 @@ void pcg_direction_many(const real_t *so, const Op3 *op27, const real_t *z, cons
 void pcg_update_many(int zmode, bool move, real_t *x, real_t *r, const real_t *p, const real_t *w, real_t *z,
                      const real_t *diag, int II, int JJ, int KK, bool first, real_t *slab, real_t *sc, hipStream_t st,
                      Batch bt, unsigned active);
-// On a rank grid (dist_common.h dist_pcg) the two single-vector launchers above get `partial`: instead of the one-rank second stage they
+// The dots of flexible CG (cedar_amd_solver_fcg) after the preconditioner, no vector written: r.r, r.z and w.z with w = A p
+// still in its buffer, then sc[PCG_WZ] = w.z, beta = -((alpha w.z) / rho) (first or rho = 0: 0) and rho = r.z.  r.r and r.z
+// have the bits of pcg_update(2, false, ..); alpha, sigma and the flag are left alone.  _many: per active item.
+void pcg_dots_wz(const real_t *r, const real_t *z, const real_t *w, int II, int JJ, int KK, bool first, real_t *slab,
+                 real_t *sc, hipStream_t st);
+void pcg_dots_wz_many(const real_t *r, const real_t *z, const real_t *w, int II, int JJ, int KK, bool first, real_t *slab,
+                      real_t *sc, hipStream_t st, Batch bt, unsigned active);
+// On a rank grid (dist_common.h dist_pcg) pcg_direction and pcg_update get `partial`: instead of the one-rank second stage they
 // leave this rank's slab sums there (direction: sigma; update: r.r, and r.z unless zmode 0; zmode 3: nothing -- r.r is
 // gathered with r.z after the preconditioner).  After the all-gather of `stride` doubles per rank, the _ranks kernels
 // sum the partials in rank order and set the scalars as the one-rank stages do (world = 1: the same values bit for bit).

@@ -19,6 +19,7 @@
 //   pcg_update      x, r read and written 32 + p', w read 16                                    = 48 B
 //                   precon = diag: + a_ii read 8 + z written 8                                  = 64 B
 //   pcg_dots        (pcg_update without the update) r, z read                                   = 16 B
+//   pcg_dots_wz     (flexible CG, cedar_amd_solver_fcg: the same dots and w.z) r, z, w read     = 24 B
 #include "common.h"
 #include "relax27_dev.h"
 #include <algorithm>
@@ -285,6 +286,45 @@ __global__ __launch_bounds__(256) void pcg_upd(real_t *__restrict__ x, real_t *_
 	}
 }
 
+// The dots of flexible CG after the preconditioner: pcg_upd<2, false> (same row dealing, pair loop and sums, so r.r and
+// r.z have its bits) that also reads w = A p, still in its buffer, for w.z -- a third slab section.  Nothing is written
+// but the slab.
+__global__ __launch_bounds__(256) void pcg_dwz(const real_t *__restrict__ r, const real_t *__restrict__ z,
+                                               const real_t *__restrict__ w, int II, int JJ, int KK,
+                                               real_t *__restrict__ part)
+{
+	__shared__ real_t lds[4];
+	const int nj = JJ - 2, nk = KK == 1 ? 1 : KK - 2;
+	const size_t nrows = (size_t)nj * nk;
+	real_t rr = 0.0, rz = 0.0, wz = 0.0;
+	for (size_t t = blockIdx.x; t < nrows; t += gridDim.x) {
+		const size_t j = t % nj + 1, k = KK == 1 ? 0 : t / nj + 1;
+		const size_t row = (size_t)II * (j + (size_t)JJ * k);
+		for (int q = threadIdx.x; 2 * q + 1 <= II - 2; q += blockDim.x) {
+			const size_t ie = row + 2 * q + 1;
+			const bool two = 2 * q + 2 <= II - 2;
+			real_t r0, r1, z0, z1, w0, w1;
+			ldpair(r + ie, two, r0, r1);
+			ldpair(z + ie, two, z0, z1);
+			ldpair(w + ie, two, w0, w1);
+			rr += r0 * r0;
+			if (two) rr += r1 * r1;
+			rz += r0 * z0;
+			if (two) rz += r1 * z1;
+			wz += w0 * z0;
+			if (two) wz += w1 * z1;
+		}
+	}
+	const real_t s0 = block_sum_k<256>(rr, lds);
+	const real_t s1 = block_sum_k<256>(rz, lds);
+	const real_t s2 = block_sum_k<256>(wz, lds);
+	if (threadIdx.x == 0) {
+		part[blockIdx.x] = s0;
+		part[gridDim.x + blockIdx.x] = s1;
+		part[2 * gridDim.x + blockIdx.x] = s2;
+	}
+}
+
 // ---------------------------------------------------------------- second stages (one workgroup)
 __device__ __forceinline__ real_t slab_sum(const real_t *__restrict__ part, unsigned n, real_t *lds)
 {
@@ -331,6 +371,29 @@ __global__ __launch_bounds__(RED_BS) void pcg_rho(const real_t *__restrict__ par
 	const real_t rr = slab_sum(part, n, lds);
 	const real_t rz = has_rz == 1 ? slab_sum(part + n, n, lds) : rr;
 	if (threadIdx.x == 0) set_rho(rr, rz, has_rz, first, sc);
+}
+
+// flexible CG (Polak-Ribiere beta): with r_k - r_k+1 = alpha w, beta = z_k+1.(r_k+1 - r_k) / rho_k = -(alpha w.z) / rho_k;
+// two roundings, then an exact negation.  alpha, sigma and the flag stay as the direction pass left them.
+__device__ __forceinline__ void set_rho_flex(real_t rr, real_t rz, real_t wz, int first, real_t *__restrict__ sc)
+{
+	const real_t rho = sc[PCG_RHO], alpha = sc[PCG_ALPHA];
+	sc[PCG_RR] = rr;
+	sc[PCG_RZ] = rz;
+	sc[PCG_WZ] = wz;
+	sc[PCG_BETA] = first || rho == 0.0 ? 0.0 : -((alpha * wz) / rho);
+	sc[PCG_RHO] = rz;
+}
+
+// r.r (slab 0), r.z (slab 1), w.z (slab 2) of pcg_dwz: the new rho and the flexible beta
+__global__ __launch_bounds__(RED_BS) void pcg_rho_flex(const real_t *__restrict__ part, unsigned n, int first,
+                                                       real_t *__restrict__ sc)
+{
+	__shared__ real_t lds[RED_BS / 64];
+	const real_t rr = slab_sum(part, n, lds);
+	const real_t rz = slab_sum(part + n, n, lds);
+	const real_t wz = slab_sum(part + 2 * (size_t)n, n, lds);
+	if (threadIdx.x == 0) set_rho_flex(rr, rz, wz, first, sc);
 }
 
 // ---------------------------------------------------------------- the same second stages on a rank grid
@@ -659,11 +722,84 @@ __global__ __launch_bounds__(RED_BS) void pcg_rho_many(const real_t *__restrict_
 	if (threadIdx.x == 0) set_rho(rr, rz, has_rz, first, sc + (size_t)m * PCG_NSC);
 }
 
+// pcg_dwz on the items m0 .. m0 + nitems-1, laid out as pcg_upd_many<2, false> (same workgroups, row dealing, item loop
+// inside the pair loop, LDS columns per lane) with a third column for w.z.  Item m's slab: three sections of gridDim.x
+// from part[3 m gridDim.x]: r.r, r.z, w.z.
+__global__ __launch_bounds__(256) void pcg_dwz_many(const real_t *__restrict__ r, const real_t *__restrict__ z,
+                                                    const real_t *__restrict__ w, int II, int JJ, int KK,
+                                                    real_t *__restrict__ part, int nrhs, size_t stride, unsigned active)
+{
+	__shared__ real_t lds[4];
+	__shared__ real_t rrl[ITEM_CHUNK][256], rzl[ITEM_CHUNK][256], wzl[ITEM_CHUNK][256];
+	const int m0 = ITEM_CHUNK * (int)blockIdx.y, nitems = min(ITEM_CHUNK, nrhs - m0);
+	const int nj = JJ - 2, nk = KK == 1 ? 1 : KK - 2;
+	const size_t nrows = (size_t)nj * nk;
+	for (int t = 0; t < nitems; t++) {
+		rrl[t][threadIdx.x] = 0.0;
+		rzl[t][threadIdx.x] = 0.0;
+		wzl[t][threadIdx.x] = 0.0;
+	}
+	for (size_t tr = blockIdx.x; tr < nrows; tr += gridDim.x) {
+		const size_t j = tr % nj + 1, k = KK == 1 ? 0 : tr / nj + 1;
+		const size_t row = (size_t)II * (j + (size_t)JJ * k);
+		for (int q = threadIdx.x; 2 * q + 1 <= II - 2; q += blockDim.x) {
+			const size_t ip = row + 2 * q + 1;
+			const bool two = 2 * q + 2 <= II - 2;
+#pragma unroll 1
+			for (int t = 0; t < nitems; t++) {
+				const int m = m0 + t;
+				if (!item_on(active, m)) continue;
+				const size_t ie = (size_t)m * stride + ip;
+				real_t rr = rrl[t][threadIdx.x], rz = rzl[t][threadIdx.x], wz = wzl[t][threadIdx.x];
+				real_t r0, r1, z0, z1, w0, w1;
+				ldpair(r + ie, two, r0, r1);
+				ldpair(z + ie, two, z0, z1);
+				ldpair(w + ie, two, w0, w1);
+				rr += r0 * r0;
+				if (two) rr += r1 * r1;
+				rz += r0 * z0;
+				if (two) rz += r1 * z1;
+				wz += w0 * z0;
+				if (two) wz += w1 * z1;
+				rrl[t][threadIdx.x] = rr;
+				rzl[t][threadIdx.x] = rz;
+				wzl[t][threadIdx.x] = wz;
+			}
+		}
+	}
+	for (int t = 0; t < nitems; t++) {
+		const int m = m0 + t;
+		if (!item_on(active, m)) continue; // uniform over the workgroup
+		const real_t s0 = block_sum_k<256>(rrl[t][threadIdx.x], lds);
+		const real_t s1 = block_sum_k<256>(rzl[t][threadIdx.x], lds);
+		const real_t s2 = block_sum_k<256>(wzl[t][threadIdx.x], lds);
+		if (threadIdx.x == 0) {
+			part[(size_t)(3 * m) * gridDim.x + blockIdx.x] = s0;
+			part[(size_t)(3 * m + 1) * gridDim.x + blockIdx.x] = s1;
+			part[(size_t)(3 * m + 2) * gridDim.x + blockIdx.x] = s2;
+		}
+	}
+}
+
+// workgroup m is pcg_rho_flex on item m's slab and scalar block
+__global__ __launch_bounds__(RED_BS) void pcg_rho_flex_many(const real_t *__restrict__ part, unsigned n, size_t ld, int first,
+                                                            real_t *__restrict__ sc, unsigned active)
+{
+	__shared__ real_t lds[RED_BS / 64];
+	const int m = blockIdx.x;
+	if (!item_on(active, m)) return;
+	const real_t *__restrict__ pm = part + (size_t)m * ld;
+	const real_t rr = slab_sum(pm, n, lds);
+	const real_t rz = slab_sum(pm + n, n, lds);
+	const real_t wz = slab_sum(pm + 2 * (size_t)n, n, lds);
+	if (threadIdx.x == 0) set_rho_flex(rr, rz, wz, first, sc + (size_t)m * PCG_NSC);
+}
+
 } // namespace
 
 size_t pcg_slab_doubles(int nd, int nst, int II, int JJ, int KK)
 {
-	size_t n = 2 * (size_t)UPD_NB;
+	size_t n = 3 * (size_t)UPD_NB; // pcg_dots_wz: three sections
 	if (nd == 2) n = std::max(n, (size_t)((II - 2 + 255) / 256) * (size_t)(JJ - 2));
 	else if (nst == 14) n = std::max(n, (size_t)tile_blocks((unsigned)(JJ - 2), (unsigned)(KK - 2), tile_shape_resid()));
 	else n = std::max(n, (size_t)(JJ - 2) * (size_t)(KK - 2));
@@ -787,6 +923,25 @@ void pcg_update_many(int zmode, bool move, real_t *x, real_t *r, const real_t *p
 #undef LU_
 	const int has_rz = zmode == 3 ? 0 : zmode == 0 ? 2 : 1; // 2: r.z = r.r
 	hipLaunchKernelGGL(pcg_rho_many, dim3(bt.n), dim3(RED_BS), 0, st, slab, nb, (size_t)2 * nb, has_rz, first ? 1 : 0, sc, active);
+}
+
+void pcg_dots_wz(const real_t *r, const real_t *z, const real_t *w, int II, int JJ, int KK, bool first, real_t *slab,
+                 real_t *sc, hipStream_t st)
+{
+	const size_t nrows = (size_t)(JJ - 2) * (KK == 1 ? 1 : KK - 2);
+	const unsigned nb = (unsigned)std::min<size_t>(UPD_NB, nrows);
+	hipLaunchKernelGGL(pcg_dwz, dim3(nb), dim3(256), 0, st, r, z, w, II, JJ, KK, slab);
+	hipLaunchKernelGGL(pcg_rho_flex, dim3(1), dim3(RED_BS), 0, st, slab, nb, first ? 1 : 0, sc);
+}
+
+void pcg_dots_wz_many(const real_t *r, const real_t *z, const real_t *w, int II, int JJ, int KK, bool first, real_t *slab,
+                      real_t *sc, hipStream_t st, Batch bt, unsigned active)
+{
+	const size_t nrows = (size_t)(JJ - 2) * (KK == 1 ? 1 : KK - 2);
+	const unsigned nb = (unsigned)std::min<size_t>(UPD_NB, nrows);
+	const dim3 grid(nb, (unsigned)((bt.n + ITEM_CHUNK - 1) / ITEM_CHUNK));
+	hipLaunchKernelGGL(pcg_dwz_many, grid, dim3(256), 0, st, r, z, w, II, JJ, KK, slab, bt.n, bt.stride, active);
+	hipLaunchKernelGGL(pcg_rho_flex_many, dim3(bt.n), dim3(RED_BS), 0, st, slab, nb, (size_t)3 * nb, first ? 1 : 0, sc, active);
 }
 
 void pcg_ranks_alpha(const real_t *gathered, int world, int stride, real_t *sc, hipStream_t st)

@@ -1272,8 +1272,11 @@ static void pcg_precondition(cedar_amd_solver *s, int nmg, hipStream_t st)
 // `active` mask: its x, r, scalars stay as they are from then on (it still rides through the batched cycle, which has no
 // mask; its z is unused).  hist: rows of max_iter + 1 entries, those after an item's last iteration unwritten; iters
 // (may be null): the items' counts.  Returns the largest.
+// flexible (cedar_amd_solver_fcg / _fcg_many, multigrid preconditioner only): the dots after the preconditioner also form
+// w.z -- s->kw is still w_k = A p_k there, the next direction pass has not run -- and beta is the Polak-Ribiere one
+// (krylov.hip pcg_rho_flex), which needs no symmetry of M.  Nothing else of the loop changes.
 static int pcg_run(cedar_amd_solver *s, int nrhs, const real_t *b, real_t *x, const cedar_amd_pcg_settings &p, real_t *hist,
-                   int *iters, const char *who)
+                   int *iters, const char *who, bool flexible = false)
 {
 	pcg_alloc(s, nrhs == 1 ? 1 : s->nb_alloc);
 	Level &L = s->lv[0];
@@ -1303,6 +1306,13 @@ static int pcg_run(cedar_amd_solver *s, int nrhs, const real_t *b, real_t *x, co
 		if (nrhs == 1) pcg_update(zmode, pn != nullptr, X, s->kr, pn, w, Z, L.A, L.II, L.JJ, L.KK, first, s->kslab, s->ksc, st);
 		else pcg_update_many(zmode, pn != nullptr, X, s->kr, pn, w, Z, L.A, L.II, L.JJ, L.KK, first, s->kslab, s->ksc, st, bt, active);
 	};
+	// z = M^-1 r of the new residuals, then their dots (flexible: w.z with them)
+	auto precondition_dots = [&]() {
+		pcg_precondition(s, p.nmg_cycles, st);
+		if (!flexible) update(2, nullptr, false);
+		else if (nrhs == 1) pcg_dots_wz(s->kr, Z, s->kw, L.II, L.JJ, L.KK, false, s->kslab, s->ksc, st);
+		else pcg_dots_wz_many(s->kr, Z, s->kw, L.II, L.JJ, L.KK, false, s->kslab, s->ksc, st, bt, active);
+	};
 	auto scalars = [&]() {
 		CEDAR_HIP_CHECK(hipMemcpyAsync(sc, s->ksc, (size_t)nrhs * PCG_NSC * sizeof(double), hipMemcpyDeviceToHost, st));
 		CEDAR_HIP_CHECK(hipStreamSynchronize(st));
@@ -1327,10 +1337,7 @@ static int pcg_run(cedar_amd_solver *s, int nrhs, const real_t *b, real_t *x, co
 		real_t *pold = s->kp[(k + 1) & 1], *pn = s->kp[k & 1];
 		direction(pold, pn, k == 0);
 		update(zm == 2 ? 3 : zm, pn, false);
-		if (zm == 2 && rule.mnorm) { // the M-norm of the new residuals needs their preconditioned form first
-			pcg_precondition(s, p.nmg_cycles, st);
-			update(2, nullptr, false);
-		}
+		if (zm == 2 && rule.mnorm) precondition_dots(); // the M-norm of the new residuals needs their preconditioned form first
 		scalars();
 		for (int m = 0; m < nrhs; m++) {
 			if (!((active >> m) & 1u)) continue;
@@ -1340,10 +1347,7 @@ static int pcg_run(cedar_amd_solver *s, int nrhs, const real_t *b, real_t *x, co
 			if (hist) hist[m * ld + itm[m]] = std::sqrt(q[PCG_RR]) / r0[m];
 			if (rule.stop(q[PCG_RR], q[PCG_RZ], r0[m], m0[m])) active &= ~(1u << m);
 		}
-		if (zm == 2 && !rule.mnorm && k + 1 < p.max_iter && active) { // z of the new residuals, for the next direction
-			pcg_precondition(s, p.nmg_cycles, st);
-			update(2, nullptr, false);
-		}
+		if (zm == 2 && !rule.mnorm && k + 1 < p.max_iter && active) precondition_dots(); // z of the new residuals, for the next direction
 	}
 	launch_check(who);
 	int most = 0;
@@ -1372,6 +1376,45 @@ int cedar_amd_solver_pcg_many(cedar_amd_solver *s, int nrhs, const real_t *b, re
 	const cedar_amd_pcg_settings p = pcg_settings_or_default(settings);
 	if (pcg_refused(s, p, who)) return -1;
 	return pcg_run(s, nrhs, b, x, p, hist, iters, who);
+}
+
+// Flexible CG: what cedar_amd_solver_pcg refuses of the multigrid preconditioner for its lack of symmetry is served here
+static bool fcg_refused(const cedar_amd_solver *s, const cedar_amd_pcg_settings &p, const char *who)
+{
+	const char *why = nullptr;
+	if (s->st.ibc != 0) why = "periodic boundary conditions (ibc != 0) are not supported";
+	else if (p.stop_test < CEDAR_AMD_PCG_STOP_ABS_RES_L2 || p.stop_test > CEDAR_AMD_PCG_STOP_REL_RES_M2) why = "stop_test must be 0..3";
+	else if (p.precon < CEDAR_AMD_PCG_PRECON_NONE || p.precon > CEDAR_AMD_PCG_PRECON_BMG) why = "precon must be 1..3";
+	else if (p.max_iter < 0) why = "max_iter must not be negative";
+	else if (p.precon == CEDAR_AMD_PCG_PRECON_BMG) {
+		if (p.nmg_cycles < 1) why = "nmg_cycles must be at least 1";
+		else if (s->st.nrelax_pre + s->st.nrelax_post < 1) why = "the multigrid preconditioner needs at least one relaxation sweep";
+	}
+	if (!why) return false;
+	char msg[256];
+	snprintf(msg, sizeof(msg), "%s: %s; nothing done", who, why);
+	print_error(msg);
+	return true;
+}
+
+// precon none / diag: M is exactly symmetric, the recurrence is cedar_amd_solver_pcg's own (bit for bit)
+int cedar_amd_solver_fcg(cedar_amd_solver *s, const real_t *b, real_t *x, const cedar_amd_pcg_settings *settings, real_t *hist)
+{
+	const char *who = "cedar_amd_solver_fcg";
+	if (null_handle(s, who)) return -1;
+	const cedar_amd_pcg_settings p = pcg_settings_or_default(settings);
+	if (fcg_refused(s, p, who)) return -1;
+	return pcg_run(s, 1, b, x, p, hist, nullptr, who, p.precon == CEDAR_AMD_PCG_PRECON_BMG);
+}
+
+int cedar_amd_solver_fcg_many(cedar_amd_solver *s, int nrhs, const real_t *b, real_t *x, const cedar_amd_pcg_settings *settings,
+                              real_t *hist, int *iters)
+{
+	const char *who = "cedar_amd_solver_fcg_many";
+	if (null_handle(s, who) || many_refused(s, nrhs, who)) return -1;
+	const cedar_amd_pcg_settings p = pcg_settings_or_default(settings);
+	if (fcg_refused(s, p, who)) return -1;
+	return pcg_run(s, nrhs, b, x, p, hist, iters, who, p.precon == CEDAR_AMD_PCG_PRECON_BMG);
 }
 
 void cedar_amd_solver_precondition(cedar_amd_solver *s, real_t *z, const real_t *r)

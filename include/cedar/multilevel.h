@@ -133,21 +133,10 @@ public:
 	// conjugate gradients preconditioned by the cycle (cedar_amd_solver_pcg), configured by the keys pcg.max-iter,
 	// pcg.tol, pcg.stop-test (BoxMG's 0..3 or abs-l2 / rel-l2 / abs-m / rel-m), pcg.precon (1..3 or none / diag / mg) and
 	// pcg.nmg-cycles; `history` as after solve().  Resident path only.
-	void pcg(const grid_func & b, grid_func & x)
-	{
-		history.clear();
-		if (!resident()) {
-			log::error << "pcg: needs the device-resident solver (every kernel \"hip\")" << std::endl;
-			return;
-		}
-		const cedar_amd_pcg_settings ps = pcg_settings();
-		std::vector<real_t> rel(ps.max_iter > 0 ? ps.max_iter + 1 : 1);
-		int n = cedar_amd_solver_pcg(h, b.data(), x.data(), &ps, rel.data());
-		if (n < 0) return;
-		log::info << "Initial residual l2 norm: " << rel[0] << std::endl;
-		for (int i = 0; i < n; i++) log::status << "PCG iteration " << i << " relative l2 norm: " << rel[i + 1] << std::endl;
-		history.assign(rel.begin(), rel.begin() + n + 1);
-	}
+	void pcg(const grid_func & b, grid_func & x) { krylov(cedar_amd_solver_pcg, "pcg", b, x); }
+	// flexible conjugate gradients (cedar_amd_solver_fcg): pcg with the Polak-Ribiere beta, so any cycle of the solver --
+	// V(m,n), an F-cycle, plane relaxation -- may be the preconditioner.  The same pcg.* keys, `history` as after pcg().
+	void fcg(const grid_func & b, grid_func & x) { krylov(cedar_amd_solver_fcg, "fcg", b, x); }
 
 	// several right-hand sides in lockstep on the one hierarchy (cedar_amd_solver_solve_many; room for them is made with
 	// the key solver.max-rhs).  histories[m] / iterations[m]: item m's residual history cut to the cycles run and the
@@ -193,16 +182,45 @@ public:
 	// that has converged is left alone from then on, so x[m] is what pcg(b[m], x[m]) gives.  Resident path only.
 	void pcg_many(const std::vector<grid_func> & b, std::vector<grid_func> & x)
 	{
+		krylov_many(cedar_amd_solver_pcg_many, "pcg_many", b, x);
+	}
+	// fcg on several right-hand sides in lockstep (cedar_amd_solver_fcg_many); results as after pcg_many()
+	void fcg_many(const std::vector<grid_func> & b, std::vector<grid_func> & x)
+	{
+		krylov_many(cedar_amd_solver_fcg_many, "fcg_many", b, x);
+	}
+
+	// pcg / fcg and their batched forms: one C entry point each, the same marshalling
+	void krylov(int (*call)(cedar_amd_solver *, const real_t *, real_t *, const cedar_amd_pcg_settings *, real_t *),
+	            const char * who, const grid_func & b, grid_func & x)
+	{
+		history.clear();
+		if (!resident()) {
+			log::error << who << ": needs the device-resident solver (every kernel \"hip\")" << std::endl;
+			return;
+		}
+		const cedar_amd_pcg_settings ps = pcg_settings();
+		std::vector<real_t> rel(ps.max_iter > 0 ? ps.max_iter + 1 : 1);
+		int n = call(h, b.data(), x.data(), &ps, rel.data());
+		if (n < 0) return;
+		log::info << "Initial residual l2 norm: " << rel[0] << std::endl;
+		for (int i = 0; i < n; i++) log::status << "PCG iteration " << i << " relative l2 norm: " << rel[i + 1] << std::endl;
+		history.assign(rel.begin(), rel.begin() + n + 1);
+	}
+
+	void krylov_many(int (*call)(cedar_amd_solver *, int, const real_t *, real_t *, const cedar_amd_pcg_settings *, real_t *, int *),
+	                 const char * who, const std::vector<grid_func> & b, std::vector<grid_func> & x)
+	{
 		history.clear();
 		histories.clear();
 		iterations.clear();
 		if (!resident()) {
-			log::error << "pcg_many: needs the device-resident solver (every kernel \"hip\")" << std::endl;
+			log::error << who << ": needs the device-resident solver (every kernel \"hip\")" << std::endl;
 			return;
 		}
 		const std::size_t nrhs = b.size();
 		if (nrhs == 0 || x.size() != nrhs) {
-			log::error << "pcg_many: b and x must hold the same number (at least one) of grid functions" << std::endl;
+			log::error << who << ": b and x must hold the same number (at least one) of grid functions" << std::endl;
 			return;
 		}
 		const cedar_amd_pcg_settings ps = pcg_settings();
@@ -213,7 +231,7 @@ public:
 			std::copy(x[m].data(), x[m].data() + npts, xx.begin() + m * npts);
 		}
 		iterations.assign(nrhs, 0);
-		const int n = cedar_amd_solver_pcg_many(h, (int)nrhs, bb.data(), xx.data(), &ps, rel.data(), iterations.data());
+		const int n = call(h, (int)nrhs, bb.data(), xx.data(), &ps, rel.data(), iterations.data());
 		if (n < 0) {
 			iterations.clear();
 			return;

@@ -285,7 +285,7 @@ void cedar_amd_box_copy_strided(real_t *arr, len_t ii, len_t jj, len_t kk, int n
  * wrote shows in the scalars.  All return 0, or -1 (nothing done, reported through print_error) on arguments they do
  * not serve. */
 enum { CEDAR_AMD_PCG_RHO = 0, CEDAR_AMD_PCG_SIGMA = 1, CEDAR_AMD_PCG_ALPHA = 2, CEDAR_AMD_PCG_BETA = 3, CEDAR_AMD_PCG_RR = 4,
-       CEDAR_AMD_PCG_RZ = 5, CEDAR_AMD_PCG_FLAG = 6, CEDAR_AMD_PCG_NSC = 8 };
+       CEDAR_AMD_PCG_RZ = 5, CEDAR_AMD_PCG_FLAG = 6, CEDAR_AMD_PCG_WZ = 7, CEDAR_AMD_PCG_NSC = 8 };
 /* pn = z + beta p (first != 0: pn = z, p is not read and may be NULL), w = A pn with the terms of cedar_amd_matvec2 / 3
  * in their order, sigma = pn.w; nstncl = 3|5 (2D), 4|14 (3D).  beta = sc[BETA]; the neighbours of a point are
  * z + beta p of the input arrays, ghost cells included.  partial == NULL: the one-rank second stage -- sc[SIGMA] = sigma,
@@ -301,6 +301,12 @@ int cedar_amd_pcg_direction(const real_t *so, const real_t *z, const real_t *p, 
  * zmode 1 | 2 also partial[1] = r.z, zmode 3 nothing; sc is only read.  Arrays a mode does not use may be NULL. */
 int cedar_amd_pcg_update(int zmode, int move, real_t *x, real_t *r, const real_t *p, const real_t *w, real_t *z,
                          const real_t *diag, len_t ii, len_t jj, len_t kk, int first, real_t *sc, real_t *partial);
+/* The dots of flexible CG (cedar_amd_solver_fcg) after the preconditioner, one pass over r, z = M^-1 r and w = A p of the
+ * iteration just made: sc[RR] = r.r, sc[RZ] = r.z (both with the bits of cedar_amd_pcg_update(2, 0, ..)), sc[WZ] = w.z,
+ * sc[BETA] = -((sc[ALPHA] * w.z) / sc[RHO]) -- two roundings and an exact negation; 0 when first != 0 or sc[RHO] = 0 --
+ * then sc[RHO] = r.z.  sc[ALPHA], sc[SIGMA], sc[FLAG] and the three arrays are only read. */
+int cedar_amd_pcg_dots_wz(const real_t *r, const real_t *z, const real_t *w, len_t ii, len_t jj, len_t kk, int first,
+                          real_t *sc);
 /* the second stages of a rank grid: the ranks' partials (gathered[rank * stride + t], t = 0: sigma or r.r, t = 1: r.z)
  * summed in rank order, then the scalars as above; which = 0: alpha from sigma, 1: rho / beta by zmode.  world = 1 gives
  * the one-rank values bit for bit. */
@@ -402,6 +408,17 @@ int cedar_amd_solver_pcg(cedar_amd_solver *s, const real_t *b, real_t *x, const 
 /* z = M^-1 r: one cycle of the solver from z = 0 (the preconditioner of cedar_amd_solver_pcg with nmg_cycles = 1);
  * z, r host or device.  Refused (z untouched) on the settings cedar_amd_solver_pcg refuses for precon = 3. */
 void cedar_amd_solver_precondition(cedar_amd_solver *s, real_t *z, const real_t *r);
+/* Flexible conjugate gradients (Golub-Ye 1999, Notay 2000, FCG(1)): cedar_amd_solver_pcg with the one change that
+ * beta = z_k+1.(r_k+1 - r_k) / (r_k.z_k) = -(alpha_k (A p_k).z_k+1) / rho_k instead of r_k+1.z_k+1 / rho_k -- one more dot
+ * product in the pass that reads r and z after the preconditioner, no extra vector or operator pass (DESIGN.md section
+ * 14).  The two agree when M is symmetric and the flexible one does not need it, so with precon = 3 ANY cycle of the
+ * handle is served: V(m,n) with m + n >= 1 (the default V(2,1) included), F-cycles, point, line and plane relaxation with
+ * any plane sweep counts, handles switched by cedar_amd_solver_use_fp32_operator (the recurrence keeps the FP64
+ * operator).  precon = 1 | 2 (M exactly symmetric) run cedar_amd_solver_pcg itself: its results bit for bit.
+ * Same settings, hist, return value, stop tests, breakdown rules and storage as cedar_amd_solver_pcg.  Refused
+ * (print_error, -1, nothing written): a NULL handle, ibc != 0, stop_test or precon out of range, max_iter < 0, and with
+ * precon = 3 nmg_cycles < 1 or a cycle without any relaxation sweep. */
+int cedar_amd_solver_fcg(cedar_amd_solver *s, const real_t *b, real_t *x, const cedar_amd_pcg_settings *p, real_t *hist);
 
 /* Keep the 27-point operator of the cycle in single precision (3D, Dirichlet, point relaxation).  Every smoothed
  * 27-point level (all but the coarsest) with at least min_rows rows gets a row-interleaved copy of A and 1/diag rounded
@@ -523,6 +540,16 @@ int cedar_amd_pcg_direction_many(int nrhs, unsigned active, const real_t *so, co
 int cedar_amd_pcg_update_many(int nrhs, unsigned active, int zmode, int move, real_t *x, real_t *r, const real_t *p,
                               const real_t *w, real_t *z, const real_t *diag, len_t ii, len_t jj, len_t kk, int first,
                               real_t *sc);
+/* cedar_amd_solver_fcg on the first nrhs items in lockstep: the contract of cedar_amd_solver_pcg_many (hist rows, iters,
+ * freezing of items, storage, bits: item m equals cedar_amd_solver_fcg on item m alone in reference order; nrhs == 1 runs
+ * the single-vector path) with the flexible beta.  Refused: whatever the other _many calls refuse (F-cycles and 3D plane
+ * relaxation among it) and whatever cedar_amd_solver_fcg refuses. */
+int cedar_amd_solver_fcg_many(cedar_amd_solver *s, int nrhs, const real_t *b, real_t *x,
+                              const cedar_amd_pcg_settings *p, real_t *hist, int *iters);
+/* cedar_amd_pcg_dots_wz on nrhs items (r, z, w item-major, sc = nrhs blocks): item m's five scalars have the bits of the
+ * single call on item m; bit m of `active` clear = item m's block stays as given */
+int cedar_amd_pcg_dots_wz_many(int nrhs, unsigned active, const real_t *r, const real_t *z, const real_t *w, len_t ii,
+                               len_t jj, len_t kk, int first, real_t *sc);
 /* The batched 3D kernels one by one on caller arrays (host or device; vectors hold nrhs items back to back, operator
  * arrays are shared); argument order of the BMG3_SymStd_* drop-ins, nstncl = 4|14, Dirichlet.  interp_add3 keeps the
  * reference's side effect (res /= so(kp)) per item.  0, or -1 (print_error, nothing done) for nrhs outside 1 .. 32, an
