@@ -253,6 +253,19 @@ class Kernels:
         assert nst == 14
         return lib.cedar_amd_residual3_op32(_p(so), _p(qf), _p(q), _p(res), u(II), u(JJ), u(KK))
 
+    def relax7_op32(self, so, qf, q, sor, updown):
+        """7-point sweep on the operator and 1/diag rounded to single precision (cedar_amd_relax7_gs_op32); 0, or -1 if
+        refused (q untouched)"""
+        nst, KK, JJ, II = so.shape
+        assert nst == 4
+        return lib.cedar_amd_relax7_gs_op32(_p(so), _p(qf), _p(q), _p(sor), u(II), u(JJ), u(KK), updown)
+
+    def residual7_op32(self, so, qf, q, res):
+        """7-point residual on the operator rounded to single precision (cedar_amd_residual7_op32); -1 if refused"""
+        nst, KK, JJ, II = so.shape
+        assert nst == 4
+        return lib.cedar_amd_residual7_op32(_p(so), _p(qf), _p(q), _p(res), u(II), u(JJ), u(KK))
+
     def residual3(self, so, qf, q, res):
         nst, KK, JJ, II = so.shape
         lib.BMG3_SymStd_residual(1, 1, int(nst == 4), _p(q), _p(qf), _p(so), _p(res), u(II), u(JJ), u(KK), nst)
@@ -340,6 +353,18 @@ class Kernels:
         grid = q.shape[1:]
         KK, JJ, II = grid
         return lib.cedar_amd_residual3_many_op32(q.shape[0] if nrhs is None else nrhs, _p(so), _p(qf), _p(q), _p(res), u(II), u(JJ), u(KK))
+
+    def relax7_many_op32(self, so, qf, q, sor, updown, nrhs=None):
+        """the batched 7-point sweep on the operator and 1/diag rounded to single precision
+        (cedar_amd_relax7_gs_many_op32); 0, or -1 if refused (q untouched)"""
+        KK, JJ, II = q.shape[1:]
+        return lib.cedar_amd_relax7_gs_many_op32(q.shape[0] if nrhs is None else nrhs, _p(so), _p(qf), _p(q), _p(sor), u(II), u(JJ), u(KK), updown)
+
+    def residual7_many_op32(self, so, qf, q, res, nrhs=None):
+        """the batched 7-point residual on the operator rounded to single precision (cedar_amd_residual7_many_op32);
+        0, or -1 if refused (res untouched)"""
+        KK, JJ, II = q.shape[1:]
+        return lib.cedar_amd_residual7_many_op32(q.shape[0] if nrhs is None else nrhs, _p(so), _p(qf), _p(q), _p(res), u(II), u(JJ), u(KK))
 
     def restrict3_many(self, q, qc, ci, nrhs=None):
         n, KK, JJ, II = q.shape
@@ -520,6 +545,8 @@ lib.cedar_amd_solver_use_fp32_operator.restype = C.c_int
 lib.cedar_amd_solver_use_fp32_operator.argtypes = [C.c_void_p, C.c_int]
 lib.cedar_amd_solver_use_fp32_operator_many.restype = C.c_int
 lib.cedar_amd_solver_use_fp32_operator_many.argtypes = [C.c_void_p, C.c_int]
+lib.cedar_amd_solver_use_fp32_operator_all.restype = C.c_int
+lib.cedar_amd_solver_use_fp32_operator_all.argtypes = [C.c_void_p, C.c_int]
 lib.cedar_amd_solver_fp32_levels.restype = C.c_int
 lib.cedar_amd_solver_fp32_levels.argtypes = [C.c_void_p]
 
@@ -675,6 +702,12 @@ class Solver:
         """use_fp32_operator for a handle made with max_rhs > 1 (cedar_amd_solver_use_fp32_operator_many): the batched cycle
         of vcycle_many / solve_many / pcg_many then reads the float copies.  With max_rhs == 1 it is use_fp32_operator"""
         return lib.cedar_amd_solver_use_fp32_operator_many(self.h, int(min_rows))
+
+    def use_fp32_operator_all(self, min_rows=0):
+        """the switch for any 3D handle, a 7-point level 0 included (cedar_amd_solver_use_fp32_operator_all): min_rows > 0
+        switches every smoothed level with at least that many rows; 0 takes the measured defaults (128 rows for either
+        kind of level).  Returns the number of levels that read a float copy, -1 if refused"""
+        return lib.cedar_amd_solver_use_fp32_operator_all(self.h, int(min_rows))
 
     def fp32_levels(self):
         return lib.cedar_amd_solver_fp32_levels(self.h)

@@ -157,6 +157,36 @@ static bool with_op32_copy(const real_t *so, const real_t *sor_msor, int II, int
 	return !host;
 }
 
+// the same for a 7-point operator (common.h Op7f, op7f.hip): rows of any length
+template <class F>
+static bool with_op7f_copy(const real_t *so, const real_t *sor_msor, int II, int JJ, int KK, const char *who, F &&f)
+{
+	char buf[200];
+	if (II < 3 || JJ < 3 || KK < 3) {
+		snprintf(buf, sizeof(buf), "%s: extents %d x %d x %d (ghosts included) are not served; nothing done", who, II, JJ, KK);
+		report(buf);
+		return false;
+	}
+	hipStream_t st = current_stream();
+	const size_t bytes = op7f_floats(II, JJ, KK) * sizeof(float);
+	float *c = static_cast<float *>(pool_get(bytes));
+	int *flag = static_cast<int *>(pool_get(sizeof(int))), host = 0;
+	CEDAR_HIP_CHECK(hipMemsetAsync(flag, 0, sizeof(int), st));
+	op7f_build(so, sor_msor, c, II, JJ, KK, flag, st);
+	CEDAR_HIP_CHECK(hipMemcpyAsync(&host, flag, sizeof(int), hipMemcpyDeviceToHost, st));
+	CEDAR_HIP_CHECK(hipStreamSynchronize(st));
+	pool_put(flag, sizeof(int));
+	if (host) {
+		snprintf(buf, sizeof(buf), "%s: an entry of the operator or of 1/diag overflows single precision; nothing done", who);
+		report(buf);
+	} else {
+		f(op7f_view(c, II, JJ, KK), st);
+		CEDAR_HIP_CHECK(hipStreamSynchronize(st));
+	}
+	pool_put(c, bytes);
+	return !host;
+}
+
 } // namespace cedar_amd
 
 extern "C" {
@@ -922,6 +952,55 @@ int cedar_amd_residual3_many_op32(int nrhs, real_t *so, real_t *qf, real_t *q, r
 		residual27_many(A, sqf.get(), sq.get(), sr.get(), II, JJ, KK, st, Batch{nrhs, P});
 	});
 	return ran ? 0 : -1;
+}
+
+// ---- the 7-point sweep and residual on a single-precision copy of the operator built for the call (with_op7f_copy;
+// include/cedar_amd.h); many: the batched kernel (the _many entry points, also with nrhs = 1), else the single-vector one
+static int relax7_op32(const char *who, bool many, int nrhs, real_t *so, real_t *qf, real_t *q, real_t *sor, len_t ii, len_t jj, len_t kk, int updown)
+{
+	if (many_args_refused(nrhs, so && qf && q && sor, true, who)) return -1;
+	const int II = (int)ii, JJ = (int)jj, KK = (int)kk;
+	const size_t P = (size_t)ii * jj * kk;
+	Staged sso(so, P * 4, true, false), sqf(qf, P * nrhs, true, false), sq(q, P * nrhs, true, true), ssor(sor, P * 2, true, false);
+	const bool ran = with_op7f_copy(sso.get(), ssor.get() + P, II, JJ, KK, who, [&](const Op7f &A, hipStream_t st) {
+		if (many) relax3_gs7_many(A, sqf.get(), sq.get(), II, JJ, KK, updown, st, Batch{nrhs, P});
+		else relax3_gs7_op(A, sqf.get(), sq.get(), II, JJ, KK, updown, st);
+	});
+	return ran ? 0 : -1;
+}
+
+static int residual7_op32(const char *who, bool many, int nrhs, real_t *so, real_t *qf, real_t *q, real_t *res, len_t ii, len_t jj, len_t kk)
+{
+	if (many_args_refused(nrhs, so && qf && q && res, true, who)) return -1;
+	const int II = (int)ii, JJ = (int)jj, KK = (int)kk;
+	const size_t P = (size_t)ii * jj * kk;
+	Staged sso(so, P * 4, true, false), sqf(qf, P * nrhs, true, false), sq(q, P * nrhs, true, false), sr(res, P * nrhs, true, true);
+	// 1/diag is not read by the residual: the copy's reciprocal row is filled from the operator's centre plane
+	const bool ran = with_op7f_copy(sso.get(), sso.get(), II, JJ, KK, who, [&](const Op7f &A, hipStream_t st) {
+		if (many) residual7_many(A, sqf.get(), sq.get(), sr.get(), II, JJ, KK, st, Batch{nrhs, P});
+		else residual7_op(A, sqf.get(), sq.get(), sr.get(), II, JJ, KK, st);
+	});
+	return ran ? 0 : -1;
+}
+
+int cedar_amd_relax7_gs_op32(real_t *so, real_t *qf, real_t *q, real_t *sor, len_t ii, len_t jj, len_t kk, int updown)
+{
+	return relax7_op32("cedar_amd_relax7_gs_op32", false, 1, so, qf, q, sor, ii, jj, kk, updown);
+}
+
+int cedar_amd_residual7_op32(real_t *so, real_t *qf, real_t *q, real_t *res, len_t ii, len_t jj, len_t kk)
+{
+	return residual7_op32("cedar_amd_residual7_op32", false, 1, so, qf, q, res, ii, jj, kk);
+}
+
+int cedar_amd_relax7_gs_many_op32(int nrhs, real_t *so, real_t *qf, real_t *q, real_t *sor, len_t ii, len_t jj, len_t kk, int updown)
+{
+	return relax7_op32("cedar_amd_relax7_gs_many_op32", true, nrhs, so, qf, q, sor, ii, jj, kk, updown);
+}
+
+int cedar_amd_residual7_many_op32(int nrhs, real_t *so, real_t *qf, real_t *q, real_t *res, len_t ii, len_t jj, len_t kk)
+{
+	return residual7_op32("cedar_amd_residual7_many_op32", true, nrhs, so, qf, q, res, ii, jj, kk);
 }
 
 int cedar_amd_restrict3_many(int nrhs, real_t *q, real_t *qc, real_t *ci, len_t ii, len_t jj, len_t kk, len_t iic, len_t jjc,

@@ -121,6 +121,32 @@ struct Batch {
 	size_t stride = 0;
 };
 
+// The single-precision copy of a 7-point level (cedar_amd_solver_use_fp32_operator_all; op7f.hip):
+// the NS7 = 5 slot-rows of grid row (j,k) -- KPW, KPS, KB, the diagonal KP, 1/diag -- are contiguous, rows padded to RS
+// floats (a multiple of 32 => every slot-row starts on a 128-byte line).  Entry (slot, i, j, k) = a[j*SJ + k*SK + slot*RS
+// + i]; SJ = 5*RS, SK = 5*RS*JJ.  Ghost rows and columns are kept (the sweep reads KPW at i+1, KPS at j+1, KB at k+1).
+struct Op7f {
+	const float *a;
+	size_t RS, SJ, SK;
+};
+enum { NS7 = 5, O7_PW = 0, O7_PS = 1, O7_B = 2, O7_P = 3, O7_RD = 4 };
+static inline size_t op7f_floats(int II, int JJ, int KK) { return ilv32_row_stride(II) * NS7 * (size_t)JJ * KK; }
+static inline Op7f op7f_view(const float *a, int II, int JJ, int KK)
+{
+	const size_t RS = ilv32_row_stride(II);
+	(void)KK;
+	return Op7f{a, RS, NS7 * RS, NS7 * RS * (size_t)JJ};
+}
+// build it from the Cedar planes (4 slots) and the 1/diag plane (round to nearest even); *overflow as for ilv32_build
+void op7f_build(const real_t *so, const real_t *sor_msor, float *out, int II, int JJ, int KK, int *overflow, hipStream_t st);
+// the 7-point sweep (two colour launches, UP = 0,1; DOWN = 1,0) and residual on that view, and their batched twins
+// (operator entries fetched once per point, the items inside): bit for bit relax3_gs / residual3 / relax3_gs7_many /
+// residual7_many on the rounded arrays; rows of any length
+void relax3_gs7_op(const Op7f &A, const real_t *qf, real_t *q, int II, int JJ, int KK, int updown, hipStream_t st);
+void residual7_op(const Op7f &A, const real_t *qf, const real_t *q, real_t *res, int II, int JJ, int KK, hipStream_t st);
+void relax3_gs7_many(const Op7f &A, const real_t *qf, real_t *q, int II, int JJ, int KK, int updown, hipStream_t st, Batch bt);
+void residual7_many(const Op7f &A, const real_t *qf, const real_t *q, real_t *res, int II, int JJ, int KK, hipStream_t st, Batch bt);
+
 // ---- kernel launchers (device pointers, asynchronous on `st`) ----
 // relax3d.hip
 void setup_recip(const real_t *so_diag, real_t *sor_msor, size_t II, size_t JJ, size_t KK, hipStream_t st);

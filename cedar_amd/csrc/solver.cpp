@@ -47,6 +47,9 @@ struct Level {
 	// the same copy in single precision (common.h Op3f) after cedar_amd_solver_use_fp32_operator: it replaces Ailv, and
 	// the level's sweeps and the cycle's residual read it; A itself stays FP64
 	float *A32 = nullptr;
+	// 3D 7-point (level 0): the single-precision copy of A and 1/diag (common.h Op7f) after
+	// cedar_amd_solver_use_fp32_operator_all; the level's sweeps and the cycle's residual read it, A itself stays FP64
+	float *A7f = nullptr;
 	// 3D 27-point: partial-sum scratch of the relax sweep (relax3d_psum.hip), one vector
 	real_t *T = nullptr;
 	// the set-up products (A, P, SOR, At, PF*) belong to another solver of the same operator (plane relaxation:
@@ -71,6 +74,15 @@ template <class F> void with_cycle_view27(const Level &L, F &&f)
 {
 	if (L.A32) f(op3f_ilv(L.A32, L.II, L.JJ, L.KK));
 	else f(exact_view27(L));
+}
+
+// The same choice for a 7-point level, made here and nowhere else: f(Op7f) on the float copy where the level keeps it, else
+// g() on the Cedar planes L.A / L.SOR0 -- the exact operator, which residual_true, the Krylov passes and interp_add3's
+// diagonal always read.
+template <class F, class G> void with_cycle_view7(const Level &L, F &&f, G &&g)
+{
+	if (L.A7f) f(op7f_view(L.A7f, L.II, L.JJ, L.KK));
+	else g();
 }
 
 // include/cedar/3d/relax_planes.h:164-246.  The reference keeps one 2D solver per plane; copy_coeff gives all of
@@ -201,7 +213,14 @@ void residual(const cedar_amd_solver *s, const Level &L, const real_t *x, const 
 {
 	const Batch bt{s->nb, L.npts};
 	if (s->nd == 2) residual2(L.A, b, x, r, L.II, L.JJ, L.nst, st, bt);
-	else if (s->nb > 1 && L.nst != 14) residual7_many(L.A, b, x, r, L.II, L.JJ, L.KK, st, bt);
+	else if (L.nst != 14 && (s->nb > 1 || L.A7f)) // (a single vector only for the float view: op7f.hip)
+		with_cycle_view7(
+		    L,
+		    [&](const Op7f &A) {
+			    if (s->nb > 1) residual7_many(A, b, x, r, L.II, L.JJ, L.KK, st, bt);
+			    else residual7_op(A, b, x, r, L.II, L.JJ, L.KK, st);
+		    },
+		    [&]() { residual7_many(L.A, b, x, r, L.II, L.JJ, L.KK, st, bt); });
 	else if (s->nb > 1) with_cycle_view27(L, [&](const auto &A) { residual27_many(A, b, x, r, L.II, L.JJ, L.KK, st, bt); });
 	else if (L.A32 || L.Ailv) with_cycle_view27(L, [&](const auto &A) { residual27_op(A, b, x, r, L.II, L.JJ, L.KK, st); });
 	else residual3(L.A, b, x, r, L.II, L.JJ, L.KK, L.nst, st);
@@ -211,7 +230,8 @@ void residual(const cedar_amd_solver *s, const Level &L, const real_t *x, const 
 // cycle's residual, except on a level that keeps the float copy: there the same launches on the exact view
 void residual_true(const cedar_amd_solver *s, const Level &L, const real_t *x, const real_t *b, real_t *r, hipStream_t st)
 {
-	if (!L.A32) residual(s, L, x, b, r, st);
+	if (!L.A32 && !L.A7f) residual(s, L, x, b, r, st);
+	else if (s->nb > 1 && L.nst != 14) residual7_many(L.A, b, x, r, L.II, L.JJ, L.KK, st, Batch{s->nb, L.npts});
 	else if (s->nb > 1) residual27_many(exact_view27(L), b, x, r, L.II, L.JJ, L.KK, st, Batch{s->nb, L.npts});
 	else residual3(L.A, b, x, r, L.II, L.JJ, L.KK, L.nst, st);
 }
@@ -401,12 +421,19 @@ void smooth(const cedar_amd_solver *s, const Level &L, real_t *x, const real_t *
 		}
 		if (s->nd == 3 && s->nb > 1) { // a batch of right-hand sides: reference order, operator fetched once (many3d.hip)
 			const Batch bt{s->nb, L.npts};
-			if (L.nst != 14) relax3_gs7_many(L.A, b, x, L.SOR0, L.II, L.JJ, L.KK, updown, st, bt);
+			if (L.nst != 14)
+				with_cycle_view7(
+				    L, [&](const Op7f &A) { relax3_gs7_many(A, b, x, L.II, L.JJ, L.KK, updown, st, bt); },
+				    [&]() { relax3_gs7_many(L.A, b, x, L.SOR0, L.II, L.JJ, L.KK, updown, st, bt); });
 			else with_cycle_view27(L, [&](const auto &A) { relax3_gs27_many(A, b, x, L.II, L.JJ, L.KK, updown, st, bt); });
 			continue;
 		}
 		if (s->nd == 3) { // without a copy or scratch of its own: relax3_gs, which finds what the operator's owner registered
-			if (!L.A32 && !L.Ailv && !L.T) relax3_gs(L.A, b, x, L.SOR0, L.II, L.JJ, L.KK, L.nst, updown, st);
+			if (L.nst != 14)
+				with_cycle_view7(
+				    L, [&](const Op7f &A) { relax3_gs7_op(A, b, x, L.II, L.JJ, L.KK, updown, st); },
+				    [&]() { relax3_gs(L.A, b, x, L.SOR0, L.II, L.JJ, L.KK, L.nst, updown, st); });
+			else if (!L.A32 && !L.Ailv && !L.T) relax3_gs(L.A, b, x, L.SOR0, L.II, L.JJ, L.KK, L.nst, updown, st);
 			else with_cycle_view27(L, [&](const auto &A) { relax3_gs27_op(A, b, x, L.II, L.JJ, L.KK, updown, st, L.T); });
 			continue;
 		}
@@ -834,6 +861,7 @@ void cedar_amd_solver_destroy(cedar_amd_solver *s)
 		if (!L.shared) {
 			(void)hipFree(L.P); (void)hipFree(L.SOR0); (void)hipFree(L.SOR1); (void)hipFree(L.At); (void)hipFree(L.Ailv);
 			(void)hipFree(L.A32);
+			(void)hipFree(L.A7f);
 			(void)hipFree(L.PFx); (void)hipFree(L.PFy);
 		}
 		(void)hipFree(L.res); (void)hipFree(L.yscr); (void)hipFree(L.bt); (void)hipFree(L.xt); (void)hipFree(L.T);
@@ -894,7 +922,7 @@ static void pcg_precondition(cedar_amd_solver *s, int nmg, hipStream_t st);
 static int fp32_count(const cedar_amd_solver *s)
 {
 	int n = 0;
-	for (const Level &L : s->lv) n += L.A32 ? 1 : 0;
+	for (const Level &L : s->lv) n += (L.A32 || L.A7f) ? 1 : 0;
 	return n;
 }
 
@@ -912,7 +940,8 @@ static bool op32_build(cedar_amd_solver *s, const Level &L, float *out, hipStrea
 {
 	int *flag = s->dinfo + 1, host = 0; // (dinfo[0]: the coarse factorisation's info)
 	CEDAR_HIP_CHECK(hipMemsetAsync(flag, 0, sizeof(int), st));
-	ilv32_build(L.A, L.SOR0 + L.npts, out, L.II, L.JJ, L.KK, flag, st);
+	if (L.nst == 14) ilv32_build(L.A, L.SOR0 + L.npts, out, L.II, L.JJ, L.KK, flag, st);
+	else op7f_build(L.A, L.SOR0 + L.npts, out, L.II, L.JJ, L.KK, flag, st);
 	CEDAR_HIP_CHECK(hipMemcpyAsync(&host, flag, sizeof(int), hipMemcpyDeviceToHost, st));
 	CEDAR_HIP_CHECK(hipStreamSynchronize(st));
 	return host != 0;
@@ -924,6 +953,11 @@ static bool op32_build(cedar_amd_solver *s, const Level &L, float *out, hipStrea
 // A batch handle (cedar_amd_solver_use_fp32_operator_many) has the same break-even level at 1, 2, 4 and 8 right-hand sides
 // (tools/op32_many_time.py, profiles/op32_many_time.json) and takes the same default
 enum { OP32_DEFAULT_MIN_ROWS = 128 };
+// The same for the 7-point level under cedar_amd_solver_use_fp32_operator_all(s, 0) (0 here would leave it in FP64 unless
+// min_rows > 0 is given).  Measured (tools/op32_7pt_time.py, profiles/op32_7pt_time.json): the
+// switched V(1,1) / V(2,1) cycle runs in 0.72 / 0.69 of the FP64 one at 512^3, 0.87 / 0.88 at 256^3 and 0.95 / 0.94 at
+// 128^3, each gain many times the spread of the repetitions; nothing smaller was measured, so nothing smaller is taken
+enum { OP32_7PT_DEFAULT_MIN_ROWS = 128 };
 
 int cedar_amd_solver_fp32_levels(const cedar_amd_solver *s)
 {
@@ -931,8 +965,9 @@ int cedar_amd_solver_fp32_levels(const cedar_amd_solver *s)
 }
 
 // the body of cedar_amd_solver_use_fp32_operator (batch false: a handle of cedar_amd_solver_create_many is refused) and
-// of cedar_amd_solver_use_fp32_operator_many on a batch handle
-static int op32_switch(cedar_amd_solver *s, int min_rows, bool batch, const char *who)
+// of cedar_amd_solver_use_fp32_operator_many on a batch handle; seven: the 7-point level takes its copy as well
+// (cedar_amd_solver_use_fp32_operator_all)
+static int op32_switch(cedar_amd_solver *s, int min_rows, bool batch, const char *who, bool seven = false)
 {
 	if (null_handle(s, who)) return -1;
 	const char *why = nullptr;
@@ -948,6 +983,8 @@ static int op32_switch(cedar_amd_solver *s, int min_rows, bool batch, const char
 		return -1;
 	};
 	if (why) return refuse(why);
+	// the 7-point level (level 0; rows of any length): an explicit min_rows counts as given, 0 = its own measured default
+	const int min_rows7 = !seven ? 0 : min_rows > 0 ? min_rows : (int)OP32_7PT_DEFAULT_MIN_ROWS;
 	if (min_rows == 0) {
 		const char *e = getenv("CEDAR_AMD_OP32_MIN_ROWS"); // read per call, like CEDAR_AMD_PSUM
 		min_rows = e && atoi(e) > 0 ? atoi(e) : (int)OP32_DEFAULT_MIN_ROWS;
@@ -961,9 +998,11 @@ static int op32_switch(cedar_amd_solver *s, int min_rows, bool batch, const char
 	};
 	for (int l = 0; l + 1 < (int)s->lv.size(); l++) {
 		const Level &L = s->lv[l];
-		if (L.A32 || L.nst != 14 || L.ny < min_rows || (L.II - 2 + 1) / 2 > 512) continue;
+		const bool take7 = s->nd == 3 && L.nst != 14 && !L.A7f && min_rows7 > 0 && L.ny >= min_rows7;
+		if (!take7 && (L.A32 || L.nst != 14 || L.ny < min_rows || (L.II - 2 + 1) / 2 > 512)) continue;
 		float *c = nullptr;
-		if (hipMalloc((void **)&c, ilv32_floats(L.II, L.JJ, L.KK) * sizeof(float)) != hipSuccess) {
+		const size_t nfl = take7 ? op7f_floats(L.II, L.JJ, L.KK) : ilv32_floats(L.II, L.JJ, L.KK);
+		if (hipMalloc((void **)&c, nfl * sizeof(float)) != hipSuccess) {
 			(void)hipGetLastError();
 			undo();
 			return refuse("out of device memory for the single-precision copy");
@@ -978,6 +1017,10 @@ static int op32_switch(cedar_amd_solver *s, int min_rows, bool batch, const char
 		graphs_drop(s);
 		for (auto &f : fresh) {
 			Level &L = s->lv[f.first];
+			if (L.nst != 14) {
+				L.A7f = f.second;
+				continue;
+			}
 			L.A32 = f.second;
 			(void)hipFree(L.Ailv);
 			L.Ailv = nullptr;
@@ -1003,6 +1046,15 @@ int cedar_amd_solver_use_fp32_operator_many(cedar_amd_solver *s, int min_rows)
 	return op32_switch(s, min_rows, true, who);
 }
 
+// Either kind of handle, and the 7-point level as well: what the two calls above do, plus the float copy of a 7-point
+// level 0 (op7f.hip).  The two calls above keep leaving a 7-point level in FP64.
+int cedar_amd_solver_use_fp32_operator_all(cedar_amd_solver *s, int min_rows)
+{
+	const char *who = "cedar_amd_solver_use_fp32_operator_all";
+	if (null_handle(s, who)) return -1;
+	return op32_switch(s, min_rows, s->nb_alloc > 1, who, true);
+}
+
 // levels[lvl].A / .P / .SOR / ABD are public members of the reference's solver (include/cedar/level.h:14-41,
 // include/cedar/2d/solver.h:56): a caller may replace a set-up product.  Solver-internal copies that derive from the
 // array (row-interleaved solve copy, transposed y-line planes, scan-ordered line factors) are rebuilt.
@@ -1024,14 +1076,15 @@ size_t cedar_amd_solver_set(cedar_amd_solver *s, int lvl, const char *what, cons
 	else cedar_amd_memcpy_h2d(dst, in, n * sizeof(real_t));
 	if (L.Ailv && (!strcmp(what, "A") || !strcmp(what, "SOR0")))
 		ilv_build(L.A, L.SOR0 + L.npts, L.Ailv, L.II, L.JJ, L.KK, st);
-	if (L.A32 && (!strcmp(what, "A") || !strcmp(what, "SOR0")) && op32_build(s, L, L.A32, st)) {
+	float *&c32 = L.nst == 14 ? L.A32 : L.A7f; // the level's float copy, of either kind
+	if (c32 && (!strcmp(what, "A") || !strcmp(what, "SOR0")) && op32_build(s, L, c32, st)) {
 		// the new entries do not fit float: the level goes back to the FP64 planes (the captured cycle names the copy)
 		char msg[] = "cedar_amd_solver_set: an entry of the new array overflows single precision; the level reads the FP64 "
 		             "operator again";
 		print_error(msg);
 		graphs_drop(s);
-		(void)hipFree(L.A32);
-		L.A32 = nullptr;
+		(void)hipFree(c32);
+		c32 = nullptr;
 	}
 	if (L.At && !strcmp(what, "A")) setup_lines_yt(L.A, L.At, L.II, L.JJ, L.nst, st);
 	if (L.PFx && !strcmp(what, "SOR0")) lines_permute(L.SOR0, L.PFx, L.nx, L.II, L.ny, L.npts, st);

@@ -264,6 +264,16 @@ public:
 		}
 		return cedar_amd_solver_use_fp32_operator_many(h, min_rows);
 	}
+	// the same on either kind of solver, and a 7-point level 0 takes its float copy as well
+	// (cedar_amd_solver_use_fp32_operator_all); min_rows = 0: the measured defaults (levels with at least 128 rows)
+	int use_fp32_operator_all(int min_rows = 0)
+	{
+		if (!h) {
+			log::error << "use_fp32_operator_all: needs the device-resident solver (every kernel \"hip\")" << std::endl;
+			return -1;
+		}
+		return cedar_amd_solver_use_fp32_operator_all(h, min_rows);
+	}
 	int fp32_levels() const { return h ? cedar_amd_solver_fp32_levels(h) : 0; }
 
 	void vcycle(grid_func & x, const grid_func & b)

@@ -196,6 +196,15 @@ int cedar_amd_relax3_gs_psum(real_t *so, real_t *qf, real_t *q, real_t *sor, rea
 int cedar_amd_relax3_gs_op32(real_t *so, real_t *qf, real_t *q, real_t *sor, real_t *scratch, len_t ii, len_t jj, len_t kk,
                              int updown, int frun);
 int cedar_amd_residual3_op32(real_t *so, real_t *qf, real_t *q, real_t *res, len_t ii, len_t jj, len_t kk);
+/* The same for a 7-point operator (so: 4 planes; what the 7-point level of a solver runs after
+ * cedar_amd_solver_use_fp32_operator_all): a row-interleaved float copy of KPW, KPS, KB, the diagonal and 1/diag is built
+ * for the call and dropped after it.  The sweep is two colour launches in the reference's order (updown 1 = UP: colours
+ * 0, 1; 0 = DOWN: 1, 0; BMG3_SymStd_relax_GS.f90:144-184), the residual keeps BMG3_SymStd_residual's term order; entries
+ * are promoted to double on load, vectors and arithmetic stay FP64 -- bit for bit BMG3_SymStd_relax_GS /
+ * BMG3_SymStd_residual on so and sor rounded to float.  Rows of any length.  Returns 0; a NULL array or an entry that
+ * overflows float: print_error, -1, q / res untouched. */
+int cedar_amd_relax7_gs_op32(real_t *so, real_t *qf, real_t *q, real_t *sor, len_t ii, len_t jj, len_t kk, int updown);
+int cedar_amd_residual7_op32(real_t *so, real_t *qf, real_t *q, real_t *res, len_t ii, len_t jj, len_t kk);
 /* The 2D analogue for nine-point operators (BMG2_SymStd_relax_GS.f90:89-114): the band-fused sweep whose S rows take the
  * six couplings to the two neighbouring F rows as ONE partial-sum row kept in LDS by the workgroup that has just relaxed
  * those F rows.  Same contract as cedar_amd_relax3_gs_psum; the resident solver runs it on levels with at least 4096 rows
@@ -469,6 +478,24 @@ int cedar_amd_solver_fp32_levels(const cedar_amd_solver *s);
  *   cedar_amd_solver_set           "A" / "SOR0" on a switched level rebuild its float copy, as above.
  * cedar_amd_solver_use_fp32_operator itself keeps refusing batch handles. */
 int cedar_amd_solver_use_fp32_operator_many(cedar_amd_solver *s, int min_rows);
+/* The switch for any 3D handle, 7-point level included.  On a batch handle it does what
+ * cedar_amd_solver_use_fp32_operator_many does, on a handle with one right-hand side what
+ * cedar_amd_solver_use_fp32_operator does; in both cases a 7-point level 0 (coarse levels are always 27-point) also takes
+ * a float copy -- KPW, KPS, KB, the diagonal and 1/diag, row-interleaved -- which its sweeps and
+ * the cycle's residual read: single vector, batch, and nrhs == 1 on a batch handle.  The reported residual, the Krylov
+ * passes and interpolation's diagonal keep reading the FP64 operator, and cedar_amd_solver_solve / _solve_many go to
+ * defect-correction form as described above.  Rows of any length.
+ *   min_rows > 0: every smoothed level with at least min_rows rows, the 7-point level among them.
+ *   min_rows 0  : the 27-point levels by their default (128 rows, CEDAR_AMD_OP32_MIN_ROWS); the 7-point level by its own
+ *                 measured default, 128 rows as well (the V-cycle of gallery::poisson runs in
+ *                 0.72 / 0.87 / 0.95 of its FP64 time at 512^3 / 256^3 / 128^3; smaller levels were not measured and stay
+ *                 FP64 unless min_rows > 0 asks for them).
+ * Copies are built and checked before the handle changes, captured graphs are dropped, the call may be repeated; returns
+ * cedar_amd_solver_fp32_levels, which counts the 7-point level.  Refused -- print_error, -1, handle unchanged -- for a
+ * NULL or 2D handle, ibc != 0, plane relaxation, a negative min_rows, and when an entry overflows float.
+ * cedar_amd_solver_set "A" / "SOR0" on level 0 rebuild the copy (overflow: reported, the level reads FP64 again).
+ * The two calls above are unchanged: on a 7-point handle they switch the 27-point levels only. */
+int cedar_amd_solver_use_fp32_operator_all(cedar_amd_solver *s, int min_rows);
 
 /* Several right-hand sides at once on one resident hierarchy.  The operator, 1/diag and the interpolation weights are
  * the same for every right-hand side, so the batched 3D kernels (many3d.hip) fetch them once per workgroup task and apply
@@ -567,6 +594,14 @@ int cedar_amd_residual3_many(int nrhs, real_t *so, real_t *qf, real_t *q, real_t
 int cedar_amd_relax3_gs_many_op32(int nrhs, real_t *so, real_t *qf, real_t *q, real_t *sor, len_t ii, len_t jj, len_t kk,
                                   int updown);
 int cedar_amd_residual3_many_op32(int nrhs, real_t *so, real_t *qf, real_t *q, real_t *res, len_t ii, len_t jj, len_t kk);
+/* The 7-point pair on a batch (what the 7-point level of a batch handle runs after
+ * cedar_amd_solver_use_fp32_operator_all): cedar_amd_relax7_gs_op32 / cedar_amd_residual7_op32 on nrhs items stored back
+ * to back; a point's coefficients are fetched from the float copy once and applied to every item, so item m has the bits
+ * of the single call on item m alone, and of cedar_amd_relax3_gs_many / cedar_amd_residual3_many on the rounded arrays.
+ * Returns 0; nrhs outside 1 .. 32, a NULL array or an entry that overflows float: print_error, -1, q / res untouched. */
+int cedar_amd_relax7_gs_many_op32(int nrhs, real_t *so, real_t *qf, real_t *q, real_t *sor, len_t ii, len_t jj, len_t kk,
+                                  int updown);
+int cedar_amd_residual7_many_op32(int nrhs, real_t *so, real_t *qf, real_t *q, real_t *res, len_t ii, len_t jj, len_t kk);
 int cedar_amd_restrict3_many(int nrhs, real_t *q, real_t *qc, real_t *ci, len_t ii, len_t jj, len_t kk, len_t iic, len_t jjc,
                              len_t kkc);
 int cedar_amd_interp_add3_many(int nrhs, real_t *q, real_t *qc, real_t *so, real_t *res, real_t *ci, len_t iic, len_t jjc,
