@@ -332,9 +332,41 @@ def hierarchies(R):
         print(name, ml.nlev, h[0], h[-1], flush=True)
 
 
+def regimes(R):
+    """operators on every side of the interpolation set-up's lumping switch (cases.REGIME_*): the kernel suites,
+    non-periodic and periodic, and for the positive definite solve cases the residual history of 10 cycles with the
+    reference's set-up products, spread over files of at most 1 MB (tests/golden_io.py)"""
+    from golden_io import save_split
+    k = {}
+    with np.errstate(all="ignore"):
+        for lst, fn in ((cases.REGIME_2D, cases.regime_suite_2d), (cases.REGIME_3D, cases.regime_suite_3d),
+                        (cases.REGIME_PER, cases.regime_suite_per),
+                        (cases.REGIME_PER3, lambda impl, c: cases.regime_suite_per3(impl, c, reference=True))):
+            for c in lst:
+                for key, v in fn(R, c).items():
+                    k[f"{c[0]}/{key}"] = v
+    print("regimes_kernels:", save_split("regimes_kernels", k), "files", flush=True)
+    for name, (mk_op, mk_rhs, st) in cases.REGIME_SOLVES.items():
+        so, b = mk_op(), mk_rhs()
+        ml = RefML(R, so, **st)
+        x = np.zeros_like(b)
+        h = ml.solve(b, x, maxiter=10, tol=1e-8)
+        out = {"hist": np.array(h), "nlev": np.array(ml.nlev), "level_dims": np.array([a.shape[1:][::-1] for a in ml.A]),
+               "x_l2": np.array(seq_l2(x))}
+        for l in range(ml.nlev):
+            if l > 0:
+                out["A%d" % l] = ml.A[l]
+                out["P%d" % l] = ml.P[l]
+            if l < ml.nlev - 1:
+                out["SOR0_%d" % l] = ml.SOR[l][0]
+        print(name, ml.nlev, h[0], h[-1], save_split("regimes_hier_" + name.split(".")[0], out), "files", flush=True)
+
+
 if __name__ == "__main__":
     if len(sys.argv) > 1 and sys.argv[1] == "hierarchy":
         hierarchies(Ref())
+    elif len(sys.argv) > 1 and sys.argv[1] == "regimes":
+        regimes(Ref())
     elif len(sys.argv) > 1 and sys.argv[1] == "periodic":  # regenerate only the periodic fixtures
         os.makedirs(GOLD, exist_ok=True)
         main_periodic(Ref())

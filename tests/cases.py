@@ -28,15 +28,18 @@ CASES_3D = [
 
 
 def _seed(name):
-    return sum((i + 1) * ord(c) for i, c in enumerate(name)) % 100000
+    """from the name up to a '.': the variants of one regime case ('g33x21_9.mixed', '.scaled') share their inputs"""
+    return sum((i + 1) * ord(c) for i, c in enumerate(name.split(".")[0])) % 100000
 
 
-def kernel_suite_2d(impl, case):
+def kernel_suite_2d(impl, case, op=pb.random_op, cg=True):
+    """op(shape_g, nst, seed) builds the operator; cg=False leaves out the band coarse solve (operators that are
+    not positive definite)"""
     name, nx, ny, nst = case
     sd = _seed(name)
     g = (ny + 2, nx + 2)
     gc = pb.coarse_shape(g)
-    so = pb.random_op(g, nst, sd)
+    so = op(g, nst, sd)
     qf = pb.uniform(g, sd + 1, -1, 1)
     q0 = pb.uniform(g, sd + 2, -1, 1)
     out = {}
@@ -72,7 +75,7 @@ def kernel_suite_2d(impl, case):
     q, res = q0.copy(), qf.copy()
     impl.interp_add2(q, qcx, res, so, ci)
     out["interp_add_q"], out["interp_add_res"] = q, res
-    if nx * ny <= 200:
+    if cg and nx * ny <= 200:
         abd = np.zeros((nx * ny, nx + 2))
         impl.setup_cg2(so, abd)
         out["abd"] = abd.copy()
@@ -82,12 +85,12 @@ def kernel_suite_2d(impl, case):
     return out
 
 
-def kernel_suite_3d(impl, case):
+def kernel_suite_3d(impl, case, op=pb.random_op, cg=True):
     name, nx, ny, nz, nst = case
     sd = _seed(name)
     g = (nz + 2, ny + 2, nx + 2)
     gc = pb.coarse_shape(g)
-    so = pb.random_op(g, nst, sd)
+    so = op(g, nst, sd)
     qf = pb.uniform(g, sd + 1, -1, 1)
     q0 = pb.uniform(g, sd + 2, -1, 1)
     out = {}
@@ -115,7 +118,7 @@ def kernel_suite_3d(impl, case):
     q, res = q0.copy(), qf.copy()
     impl.interp_add3(q, qcx, so, res, ci)
     out["interp_add_q"], out["interp_add_res"] = q, res
-    if nx * ny * nz <= 500:
+    if cg and nx * ny * nz <= 500:
         abd = np.zeros((nx * ny * nz, nx * (ny + 1) + 2))
         impl.setup_cg3(so, abd)
         out["abd"] = abd.copy()
@@ -213,12 +216,12 @@ CASES_PER = [
 ]
 
 
-def kernel_suite_per(impl, case):
+def kernel_suite_per(impl, case, op=lambda g, nst, sd: pb.random_op(g, nst, sd, zero_ghost=False)):
     name, nx, ny, nst, ibc = case
     sd = _seed(name)
     g = (ny + 2, nx + 2)
     gc = pb.coarse_shape(g)
-    so = pb.random_op(g, nst, sd, zero_ghost=False)
+    so = op(g, nst, sd)
     out = {}
     sor = np.zeros((2,) + g)
     impl.setup_recip2(so, sor)
@@ -323,14 +326,14 @@ CASES_PER3 = [
 ]
 
 
-def kernel_suite_per3(impl, case, reference=False):
+def kernel_suite_per3(impl, case, reference=False, op=None):
     """reference=True (golden generation): interp_add only for per_z, the one code for which the routine's ghost
     refresh is well defined by the source.  Restriction and Galerkin product use the implementation's own
     interpolation weights: they pin every weight that is ever read."""
     name, nx, ny, nz, nst, ibc = case
     sd = _seed(name)
     per = pb.per3_of(ibc)
-    so = pb.periodic_random_op3(nx, ny, nz, nst, per, sd)
+    so = pb.periodic_random_op3(nx, ny, nz, nst, per, sd) if op is None else op((nz + 2, ny + 2, nx + 2), nst, sd)
     g = so.shape[1:]
     gc = pb.coarse_shape(g)
     out = {}
@@ -398,3 +401,61 @@ SOLVES_PER3 = {
     "perrand27_z_20x24x32_f21": _per3((20, 24, 32), (0, 0, 1), "random", 11) + (dict(relax="point", nrelax_pre=2, nrelax_post=1, ibc=5, cycle="f"),),
     "perpoisson7_xy_32x32x24_f21": _per3((32, 32, 24), (1, 1, 0), "poisson") + (dict(relax="point", nrelax_pre=2, nrelax_post=1, ibc=3, cycle="f"),),
 }
+
+
+# --------------------------------------------------------------------------
+# Operators on every side of the interpolation set-up's lumping switch (problems.regime_op).  A case is named
+# '<shape>.<variant>'; the variants of one shape share their random draws (_seed), so 'scaled' is 'mixed' times 2**-10
+# bit for bit.  The band coarse solve runs for the positive definite variant only.
+# --------------------------------------------------------------------------
+def _variants(shapes, spd_shape):
+    out = [(f"{c[0]}.{v}",) + c[1:] for c in shapes for v in ("mixed", "signed", "scaled")]
+    return out + [(f"{c[0]}.spd",) + c[1:] for c in shapes if c[0] in spd_shape]
+
+
+REGIME_2D = _variants([("g33x21_9", 33, 21, 5), ("g16x12_9", 16, 12, 5), ("g20x17_5", 20, 17, 3), ("g9x9_5", 9, 9, 3)],
+                      ("g16x12_9", "g9x9_5"))
+# With 26 couplings per row and a tenth of them negative, a negative diagonal is rare and sits next to a Dirichlet
+# side: the letter in a 27-point name picks draws whose signed variant has one (a fully periodic 27-point operator has
+# none, so that boundary code runs on the seven-point stencil).
+REGIME_3D = _variants([("g17x13x11d_27", 17, 13, 11, 14), ("g16x12x10c_27", 16, 12, 10, 14), ("g12x9x10_7", 12, 9, 10, 4),
+                       ("g9x9x9_7", 9, 9, 9, 4)], ("g16x12x10c_27", "g9x9x9_7"))
+# periodic: even extents in the wrapped directions, ny <= nz in 3D (CASES_PER3)
+REGIME_PER = [(f"{c[0]}.{v}",) + c[1:] for c in [("h16x11_9_x", 16, 11, 5, 2), ("h11x16_5_y", 11, 16, 3, 1),
+                                                  ("h12x10_9_xy", 12, 10, 5, 3)] for v in ("mixed", "signed")]
+REGIME_PER3 = [(f"{c[0]}.{v}",) + c[1:] for c in [("h8x7x9d_27_x", 8, 7, 9, 14, 2), ("h7x6x8_7_z", 7, 6, 8, 4, 5),
+                                                   ("h7x8x10_27_yz", 7, 8, 10, 14, 7), ("h6x6x8_7_xyz", 6, 6, 8, 4, 8)]
+               for v in ("mixed", "signed")]
+
+
+def regime_builder(name, per=None):
+    kw = pb.REGIMES[name.split(".")[1]]
+    return lambda g, nst, sd: pb.regime_op(g, nst, sd, per=per, **kw)
+
+
+def regime_suite_2d(impl, case):
+    return kernel_suite_2d(impl, case, op=regime_builder(case[0]), cg=case[0].endswith(".spd"))
+
+
+def regime_suite_3d(impl, case):
+    return kernel_suite_3d(impl, case, op=regime_builder(case[0]), cg=case[0].endswith(".spd"))
+
+
+def regime_suite_per(impl, case):
+    per = {1: (False, True), 2: (True, False), 3: (True, True)}[case[4]]
+    return kernel_suite_per(impl, case, op=regime_builder(case[0], per))
+
+
+def regime_suite_per3(impl, case, reference=False):
+    return kernel_suite_per3(impl, case, reference=reference, op=regime_builder(case[0], pb.per3_of(case[5])))
+
+
+def _regime_solve(n, nst):
+    g = tuple(m + 2 for m in n[::-1])
+    return ((lambda: pb.regime_op(g, nst, 7, **pb.REGIMES["spd"])), (lambda: (pb.rhs2 if len(n) == 2 else pb.rhs3)(*n)),
+            dict(relax="point", nrelax_pre=2, nrelax_post=1))
+
+
+# full solves on the positive definite variant; 'g33x30x29_7' has 27-point coarse levels
+REGIME_SOLVES = {"g65x40_9.spd": _regime_solve((65, 40), 5), "g33x30x29_27.spd": _regime_solve((33, 30, 29), 14),
+                 "g33x30x29_7.spd": _regime_solve((33, 30, 29), 4)}

@@ -199,6 +199,78 @@ def random_op(shape_g, nst, seed, zero_ghost=True):
     return so
 
 
+def slot_offsets(nd, nst):
+    """slot s stored at P couples the points P+a and P+b; offsets in array (slowest-first) order"""
+    if nd == 2:
+        return {0: ((0, 0), (0, 0)), 1: ((0, 0), (0, -1)), 2: ((0, 0), (-1, 0)), 3: ((0, 0), (-1, -1)),
+                4: ((-1, 0), (0, -1))}
+    # (di,dj,dk) tables of DESIGN.md section 2, reversed to (dk,dj,di)
+    A3 = [(0, 0, 0)] * 5 + [(0, -1, 0)] + [(0, 0, 0)] + [(0, -1, 0), (0, -1, 0), (-1, -1, 0), (-1, 0, 0), (-1, 0, 0)] + [(0, 0, 0)] * 2
+    B3 = [(0, 0, 0), (-1, 0, 0), (0, -1, 0), (0, 0, -1), (-1, -1, 0), (-1, 0, 0), (-1, 0, -1), (-1, 0, -1), (0, 0, -1),
+          (0, 0, -1), (0, 0, -1), (0, -1, -1), (0, -1, -1), (-1, -1, -1)]
+    return {s: (A3[s][::-1], B3[s][::-1]) for s in range(nst)}
+
+
+def _pow10(u):
+    """10**u rounded to single precision: the library power function may differ in the last bit of a double
+    from one machine to the next, and the golden vectors of these operators are compared bit for bit"""
+    return np.power(10.0, u).astype(np.float32).astype(np.float64)
+
+
+def regime_op(shape_g, nst, seed, p_def=0.0, p_zero=0.0, p_neg=0.0, scale=1.0, per=None):
+    """operator whose rows fall on every side of the interpolation set-up's lumping switch (random_op stays on
+    one).  Off-diagonals 10**U(-3,0), with probability p_neg times -0.25; entries that would couple to a ghost of a
+    non-periodic direction are zero.  R(p) = sum of the stored signed couplings that touch p (wrapped in the periodic
+    directions), diagonal = R (1 + d) with |d| = 10**U(-4,0): d = -|d|/2 with probability p_def (deficient row),
+    d = 0 exactly with probability p_zero (zero row sum), else d = +|d|.  Everything times `scale`.
+    per = (periodic_x, periodic_y[, periodic_z]): ghost layers carry the periodic image there."""
+    g = tuple(shape_g)
+    nd = len(g)
+    per = tuple(bool(p) for p in (per or (False,) * nd))[::-1]  # array (slowest-first) order
+    inner = (slice(None),) + tuple(slice(1, -1) for _ in g)
+    axes = tuple(range(nd))
+    v = _pow10(uniform((nst,) + g, seed, -3.0, 0.0))
+    v = np.where(uniform((nst,) + g, seed + 2000, 0.0, 1.0) < p_neg, -0.25 * v, v)[inner]
+    v[0] = 0.0
+    R = np.zeros(v.shape[1:])
+    offs = slot_offsets(nd, nst)
+    for s in range(1, nst):
+        ends = offs[s]
+        for o in ends:
+            for d in range(nd):
+                if o[d] and not per[d]:  # the entry reaches across a Dirichlet side
+                    v[(s,) + tuple(slice(0, 1) if e == d else slice(None) for e in range(nd))] = 0.0
+        for o in ends:
+            R += np.roll(v[s], o, axis=axes)
+    mag = _pow10(uniform(g, seed + 1000, -4.0, 0.0))[inner[1:]]
+    r = uniform(g, seed + 3000, 0.0, 1.0)[inner[1:]]
+    delta = np.where(r < p_def, -0.5 * mag, np.where(r < p_def + p_zero, 0.0, mag))
+    v[0] = R * (1.0 + delta)
+    so = np.zeros((nst,) + g)
+    so[inner] = v * scale
+    for d in range(nd):
+        if per[d]:
+            ax = d + 1
+            lo, hi = [slice(None)] * (nd + 1), [slice(None)] * (nd + 1)
+            src_lo, src_hi = list(lo), list(hi)
+            lo[ax], src_lo[ax], hi[ax], src_hi[ax] = 0, -2, -1, 1
+            so[tuple(lo)] = so[tuple(src_lo)]
+            so[tuple(hi)] = so[tuple(src_hi)]
+    return so
+
+
+# the four named members of the family (cases.py): mixed = a third of the rows deficient; signed = mixed with a
+# tenth of the couplings negative (negative diagonals: kernel-level tests only); scaled = mixed times 2**-10 (the
+# scale decides which argument of the 27-point centre minimum wins); spd = no deficient row, a third with zero row
+# sum (anything that factors or solves)
+REGIMES = {
+    "mixed": dict(p_def=1.0 / 3.0),
+    "signed": dict(p_def=1.0 / 3.0, p_neg=0.1),
+    "scaled": dict(p_def=1.0 / 3.0, scale=2.0 ** -10),
+    "spd": dict(p_zero=1.0 / 3.0),
+}
+
+
 def coarse_shape(shape_g):
     return tuple(int((n - 2 - 1) / 2.0 + 1) + 2 for n in shape_g)
 

@@ -6,20 +6,10 @@ import numpy as np
 import pytest
 
 import problems as pb
+from problems import slot_offsets
 
 SHAPES_2D = [(3, 3), (4, 3), (5, 5), (6, 9), (37, 6), (16, 33)]
 SHAPES_3D = [(3, 3, 3), (4, 5, 3), (5, 5, 5), (6, 9, 7), (12, 5, 21)]
-
-
-def slot_offsets(nd, nst):
-    """slot s stored at P couples the points P+a and P+b; offsets in array (slowest-first) order"""
-    if nd == 2:
-        return {0: ((0, 0), (0, 0)), 1: ((0, 0), (0, -1)), 2: ((0, 0), (-1, 0)), 3: ((0, 0), (-1, -1)), 4: ((-1, 0), (0, -1))}
-    # (di,dj,dk) tables of DESIGN.md section 2, reversed to (dk,dj,di)
-    A3 = [(0, 0, 0)] * 5 + [(0, -1, 0)] + [(0, 0, 0)] + [(0, -1, 0), (0, -1, 0), (-1, -1, 0), (-1, 0, 0), (-1, 0, 0)] + [(0, 0, 0)] * 2
-    B3 = [(0, 0, 0), (-1, 0, 0), (0, -1, 0), (0, 0, -1), (-1, -1, 0), (-1, 0, 0), (-1, 0, -1), (-1, 0, -1), (0, 0, -1),
-          (0, 0, -1), (0, 0, -1), (0, -1, -1), (0, -1, -1), (-1, -1, -1)]
-    return {s: (A3[s][::-1], B3[s][::-1]) for s in range(nst)}
 
 
 def dense_from_stencil(so):
