@@ -452,6 +452,10 @@ void BMG2_SymStd_SETUP_cg_LU(real_t *so, len_t *ii, len_t *jj, int *nstncl, real
 	const int bc = bc2(*ibc, "BMG2_SymStd_SETUP_cg_LU");
 	if (bc < 0) return;
 	size_t P = (size_t)(*ii) * (*jj), NA = (size_t)(*nabd1) * (*nabd2);
+	if (bc && ((size_t)*nabd1 < (size_t)(*ii - 2) * (*jj - 2) || (size_t)*nabd2 < (size_t)(*ii - 2) * (*jj - 2))) {
+		report("BMG2_SymStd_SETUP_cg_LU: the periodic coarsest operator is dense, ABD(n,n)");
+		return;
+	}
 	Staged sso(so, P * (*nstncl), true, false), sabd(abd, NA, true, true);
 	int *dinfo = static_cast<int *>(pool_get(64));
 	if (bc == 0) setup_cg2(sso.get(), (int)*ii, (int)*jj, *nstncl, sabd.get(), (int)*nabd1, (int)*nabd2, dinfo, current_stream());

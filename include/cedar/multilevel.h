@@ -312,6 +312,7 @@ protected:
 		}
 		setup_cg_solve();
 		host_setup_done = true;
+		orchestrated_built = true;
 	}
 	// host arrays of every level exist and hold the hierarchy (downloaded, or set up through the kernel manager)
 	void host_levels()
@@ -332,8 +333,10 @@ protected:
 	{
 		// a kernel selection made after construction invalidates the downloaded hierarchy only in so far as set-up
 		// kernels changed; redo the set-up through the manager so that user set-up kernels are honoured too
+		// Downloaded arrays alone do not make the path ready: the smoothers and the coarse solver (with its factorised
+		// ABD) exist only after a set-up through the manager.
 		const bool all_hip = kman->all_selected("hip");
-		if (!host_setup_done || (!all_hip && !setup_through_manager)) {
+		if (!host_setup_done || !orchestrated_built || (!all_hip && !setup_through_manager)) {
 			in_touch = true;
 			host_setup_done = false;
 			setup(levels.fine.A);
@@ -441,7 +444,9 @@ protected:
 	real_t * bbd = nullptr;
 	cedar_amd_solver * h = nullptr;
 	std::size_t nlev = 0;
-	bool space_ready = false, host_setup_done = false, setup_through_manager = false, in_touch = false;
+	// host_setup_done: the host arrays of every level hold the hierarchy (downloaded or set up through the manager);
+	// orchestrated_built: setup_impl has run, so level.presmoother / postsmoother and coarse_solver can be called
+	bool space_ready = false, host_setup_done = false, orchestrated_built = false, setup_through_manager = false, in_touch = false;
 };
 }
 #endif

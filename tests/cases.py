@@ -459,3 +459,38 @@ def _regime_solve(n, nst):
 # full solves on the positive definite variant; 'g33x30x29_7' has 27-point coarse levels
 REGIME_SOLVES = {"g65x40_9.spd": _regime_solve((65, 40), 5), "g33x30x29_27.spd": _regime_solve((33, 30, 29), 14),
                  "g33x30x29_7.spd": _regime_solve((33, 30, 29), 4)}
+
+
+# --------------------------------------------------------------------------
+# The C++ mirror's orchestrated driver (include/cedar/multilevel.h), tests/test_cxx_registry.py: the operator, the
+# right-hand side and the settings in the oracle's words (ml_create); every case runs six cycles.  "per" is
+# grid.periodic; a "plane" dictionary becomes the plane-config block.
+# --------------------------------------------------------------------------
+def _orc(mk_op, mk_rhs, per=None, **st):
+    return mk_op, mk_rhs, st, per
+
+
+ORCHESTRATED = {
+    "2d_fe9_linex": _orc(lambda: pb.fe2(45, 38), lambda: pb.rhs2(45, 38), relax="line-x"),
+    "2d_aniso9_liney": _orc(lambda: pb.aniso9(38, 45), lambda: pb.rhs2(38, 45), relax="line-y"),
+    "2d_aniso9_linexy": _orc(lambda: pb.aniso9(70, 33), lambda: pb.rhs2(70, 33), relax="line-xy"),
+    "2d_stretch5_linexy_f": _orc(lambda: pb.diag_diffusion2(40, 33, 1e-2, 1.0), lambda: pb.rhs2(40, 33), relax="line-xy", cycle="f"),
+    "2d_varcoef9_f32": _orc(lambda: pb.varcoef9(45, 38), lambda: pb.rhs2(45, 38), cycle="f", nrelax_pre=3, nrelax_post=2),
+    "2d_poisson5_two_levels": _orc(lambda: pb.poisson2(20, 17), lambda: pb.rhs2(20, 17), num_levels=2),
+    "2d_poisson5_one_level": _orc(lambda: pb.poisson2(9, 7), lambda: pb.rhs2(9, 7), num_levels=1),
+    "2d_per5_x": _orc(lambda: pb.periodic_poisson2(32, 24, (True, False)), lambda: pb.periodic_rhs2(32, 24, (True, False)),
+                      per=(True, False), nrelax_pre=1, nrelax_post=1, ibc=2),
+    "2d_per9_xy_linexy": _orc(lambda: pb.periodic_random_op(32, 24, 5, (True, True), 5), lambda: pb.periodic_rhs2(32, 24, (True, True)),
+                              per=(True, True), relax="line-xy", ibc=3),
+    "3d_poisson7": _orc(lambda: pb.poisson3(14, 12, 10), lambda: pb.rhs3(14, 12, 10)),
+    "3d_fe27_f11": _orc(lambda: pb.fe3(17, 12, 9), lambda: pb.rhs3(17, 12, 9), cycle="f", nrelax_pre=1, nrelax_post=1),
+    "3d_fe27_two_levels": _orc(lambda: pb.fe3(9, 8, 7), lambda: pb.rhs3(9, 8, 7), num_levels=2),
+    "3d_per7_z": _orc(lambda: pb.periodic_poisson3(8, 8, 16, (0, 0, 1)), lambda: pb.periodic_rhs3(8, 8, 16, (0, 0, 1)),
+                      per=(False, False, True), ibc=5),
+    "3d_per27_xyz": _orc(lambda: pb.periodic_random_op3(8, 8, 8, 14, (1, 1, 1), 15), lambda: pb.periodic_rhs3(8, 8, 8, (1, 1, 1)),
+                         per=(True, True, True), ibc=8),
+    "3d_aniso7_planexy_cfg": _orc(lambda: pb.diag_diffusion3(20, 18, 17, 1.0, 1.0, 1e-3), lambda: pb.rhs3(20, 18, 17), relax="plane-xy",
+                                  plane=dict(relax="line-xy", nrelax_pre=1, nrelax_post=1)),
+    "3d_fe27_planexz_f": _orc(lambda: pb.fe3(13, 12, 11), lambda: pb.rhs3(13, 12, 11), relax="plane-xz", cycle="f"),
+}
+ORCHESTRATED_MAXITER = 6
