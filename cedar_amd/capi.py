@@ -169,6 +169,36 @@ class Kernels:
         assert nst == 5
         return lib.cedar_amd_relax2_gs_psum(_p(so), _p(qf), _p(q), _p(sor), u(II), u(JJ), updown)
 
+    def relax2_op32(self, so, qf, q, sor, updown):
+        """2D point sweep (nine- or five-point) on the operator and 1/diag rounded to single precision
+        (cedar_amd_relax2_gs_op32), reference order; 0, or -1 if refused (q untouched)"""
+        nst, JJ, II = so.shape
+        return lib.cedar_amd_relax2_gs_op32(_p(so), _p(qf), _p(q), _p(sor), u(II), u(JJ), nst, updown)
+
+    def relax2_psum_op32(self, so, qf, q, sor, updown):
+        """nine-point partial-sum sweep on the rounded operator (cedar_amd_relax2_gs_psum_op32); 1 if that path ran, 0 if
+        the reference-order sweep ran, -1 if refused"""
+        nst, JJ, II = so.shape
+        assert nst == 5
+        return lib.cedar_amd_relax2_gs_psum_op32(_p(so), _p(qf), _p(q), _p(sor), u(II), u(JJ), updown)
+
+    def residual2_op32(self, so, qf, q, res):
+        """2D residual on the operator rounded to single precision (cedar_amd_residual2_op32); 0, or -1 if refused"""
+        nst, JJ, II = so.shape
+        return lib.cedar_amd_residual2_op32(_p(so), _p(qf), _p(q), _p(res), u(II), u(JJ), nst)
+
+    def relax2_many_op32(self, so, qf, q, sor, updown, nrhs=None):
+        """relax2_op32 on the items of qf, q of shape (nrhs,) + grid (cedar_amd_relax2_gs_many_op32); 0, or -1 if refused"""
+        nst, JJ, II = so.shape
+        return lib.cedar_amd_relax2_gs_many_op32(q.shape[0] if nrhs is None else nrhs, _p(so), _p(qf), _p(q), _p(sor),
+                                                 u(II), u(JJ), nst, updown)
+
+    def residual2_many_op32(self, so, qf, q, res, nrhs=None):
+        """residual2_op32 on the items of qf, q, res (cedar_amd_residual2_many_op32); 0, or -1 if refused"""
+        nst, JJ, II = so.shape
+        return lib.cedar_amd_residual2_many_op32(q.shape[0] if nrhs is None else nrhs, _p(so), _p(qf), _p(q), _p(res),
+                                                 u(II), u(JJ), nst)
+
     def setup_lines2(self, so, sor, d, ibc=0):
         nst, JJ, II = so.shape
         f = lib.BMG2_SymStd_SETUP_lines_x if d == "x" else lib.BMG2_SymStd_SETUP_lines_y
@@ -547,6 +577,8 @@ lib.cedar_amd_solver_use_fp32_operator_many.restype = C.c_int
 lib.cedar_amd_solver_use_fp32_operator_many.argtypes = [C.c_void_p, C.c_int]
 lib.cedar_amd_solver_use_fp32_operator_all.restype = C.c_int
 lib.cedar_amd_solver_use_fp32_operator_all.argtypes = [C.c_void_p, C.c_int]
+lib.cedar_amd_solver_use_fp32_operator_2d.restype = C.c_int
+lib.cedar_amd_solver_use_fp32_operator_2d.argtypes = [C.c_void_p, C.c_int]
 lib.cedar_amd_solver_fp32_levels.restype = C.c_int
 lib.cedar_amd_solver_fp32_levels.argtypes = [C.c_void_p]
 
@@ -708,6 +740,12 @@ class Solver:
         switches every smoothed level with at least that many rows; 0 takes the measured defaults (128 rows for either
         kind of level).  Returns the number of levels that read a float copy, -1 if refused"""
         return lib.cedar_amd_solver_use_fp32_operator_all(self.h, int(min_rows))
+
+    def use_fp32_operator_2d(self, min_rows=0):
+        """the switch for a 2D handle, single or batch, Dirichlet point relaxation (cedar_amd_solver_use_fp32_operator_2d):
+        min_rows > 0 switches every smoothed level with at least that many rows, five- and nine-point alike; 0 takes the
+        measured default (levels of at least 1024 rows).  Returns the number of levels that read a float copy, -1 if refused"""
+        return lib.cedar_amd_solver_use_fp32_operator_2d(self.h, int(min_rows))
 
     def fp32_levels(self):
         return lib.cedar_amd_solver_fp32_levels(self.h)

@@ -1007,6 +1007,80 @@ int cedar_amd_residual7_many_op32(int nrhs, real_t *so, real_t *qf, real_t *q, r
 	return residual7_op32("cedar_amd_residual7_many_op32", true, nrhs, so, qf, q, res, ii, jj, kk);
 }
 
+// ---- the 2D point sweep and residual on a single-precision copy of the operator built for the call (common.h Op2f,
+// op2f.hip; include/cedar_amd.h).  kind 0: reference-order sweep, 1: partial-sum sweep (returns 1 where it ran), 2: residual
+static int op32_2d(const char *who, int kind, int nrhs, real_t *so, real_t *qf, real_t *q, real_t *out, len_t ii, len_t jj,
+                   int nstncl, int updown)
+{
+	const char *why = nrhs < 1 || nrhs > CEDAR_AMD_MAX_RHS ? "nrhs must be 1 .. 32"
+	                  : nstncl != 3 && nstncl != 5 ? "nstncl must be 3 or 5"
+	                  : !(so && qf && q && out) ? "a required array is NULL" : nullptr;
+	char buf[200];
+	if (why) {
+		snprintf(buf, sizeof(buf), "%s: %s; nothing done", who, why);
+		report(buf);
+		return -1;
+	}
+	const int II = (int)ii, JJ = (int)jj;
+	const size_t P = (size_t)ii * jj;
+	const bool resid = kind == 2;
+	// `out`: 1/diag's array for the sweeps (read), the residual's result (written)
+	Staged sso(so, P * nstncl, true, false), sqf(qf, P * nrhs, true, false), sq(q, P * nrhs, true, !resid),
+	    sout(out, resid ? P * nrhs : P * 2, true, resid);
+	hipStream_t st = current_stream();
+	const size_t bytes = op2f_floats(II, JJ, nstncl) * sizeof(float);
+	float *c = static_cast<float *>(pool_get(bytes));
+	int *flag = static_cast<int *>(pool_get(sizeof(int))), host = 0;
+	CEDAR_HIP_CHECK(hipMemsetAsync(flag, 0, sizeof(int), st));
+	// 1/diag is not read by the residual: the copy's reciprocal row is filled from the operator's centre plane
+	op2f_build(sso.get(), resid ? sso.get() : sout.get() + P, c, II, JJ, nstncl, flag, st);
+	CEDAR_HIP_CHECK(hipMemcpyAsync(&host, flag, sizeof(int), hipMemcpyDeviceToHost, st));
+	CEDAR_HIP_CHECK(hipStreamSynchronize(st));
+	pool_put(flag, sizeof(int));
+	int ret = 0;
+	if (host) {
+		snprintf(buf, sizeof(buf), "%s: an entry of the operator or of 1/diag overflows single precision; nothing done", who);
+		report(buf);
+		ret = -1; // (staged host arrays go back as they came)
+	} else {
+		const Op2f A = op2f_view(c, II, nstncl);
+		const Batch bt{nrhs, P};
+		if (kind == 0) relax2_gs_op(A, sqf.get(), sq.get(), II, JJ, nstncl, updown, st, bt);
+		else if (kind == 1) {
+			ret = relax2_psum_wanted(II, JJ) ? 1 : 0;
+			relax2_gs9_psum_op(A, sqf.get(), sq.get(), II, JJ, updown, st, bt);
+		} else residual2_op(A, sqf.get(), sq.get(), sout.get(), II, JJ, nstncl, st, bt);
+		CEDAR_HIP_CHECK(hipStreamSynchronize(st));
+	}
+	pool_put(c, bytes);
+	return ret;
+}
+
+int cedar_amd_relax2_gs_op32(real_t *so, real_t *qf, real_t *q, real_t *sor, len_t ii, len_t jj, int nstncl, int updown)
+{
+	return op32_2d("cedar_amd_relax2_gs_op32", 0, 1, so, qf, q, sor, ii, jj, nstncl, updown);
+}
+
+int cedar_amd_relax2_gs_psum_op32(real_t *so, real_t *qf, real_t *q, real_t *sor, len_t ii, len_t jj, int updown)
+{
+	return op32_2d("cedar_amd_relax2_gs_psum_op32", 1, 1, so, qf, q, sor, ii, jj, 5, updown);
+}
+
+int cedar_amd_residual2_op32(real_t *so, real_t *qf, real_t *q, real_t *res, len_t ii, len_t jj, int nstncl)
+{
+	return op32_2d("cedar_amd_residual2_op32", 2, 1, so, qf, q, res, ii, jj, nstncl, 0);
+}
+
+int cedar_amd_relax2_gs_many_op32(int nrhs, real_t *so, real_t *qf, real_t *q, real_t *sor, len_t ii, len_t jj, int nstncl, int updown)
+{
+	return op32_2d("cedar_amd_relax2_gs_many_op32", 0, nrhs, so, qf, q, sor, ii, jj, nstncl, updown);
+}
+
+int cedar_amd_residual2_many_op32(int nrhs, real_t *so, real_t *qf, real_t *q, real_t *res, len_t ii, len_t jj, int nstncl)
+{
+	return op32_2d("cedar_amd_residual2_many_op32", 2, nrhs, so, qf, q, res, ii, jj, nstncl, 0);
+}
+
 int cedar_amd_restrict3_many(int nrhs, real_t *q, real_t *qc, real_t *ci, len_t ii, len_t jj, len_t kk, len_t iic, len_t jjc,
                              len_t kkc)
 {

@@ -147,6 +147,43 @@ void residual7_op(const Op7f &A, const real_t *qf, const real_t *q, real_t *res,
 void relax3_gs7_many(const Op7f &A, const real_t *qf, real_t *q, int II, int JJ, int KK, int updown, hipStream_t st, Batch bt);
 void residual7_many(const Op7f &A, const real_t *qf, const real_t *q, real_t *res, int II, int JJ, int KK, hipStream_t st, Batch bt);
 
+// The single-precision copy of a 2D level (cedar_amd_solver_use_fp32_operator_2d; op2f.hip): the
+// slot-rows of grid row j lie back to back -- nine-point (ns = 6): KW, KS, KSW, KNW, KO, 1/diag; five-point (ns = 4): KW,
+// KS, KO, 1/diag -- each padded to RS floats (a multiple of 32 => every slot-row starts on a 128-byte line).  Element i of
+// a slot-row sits at offset i + 1: the sweep's pairs start at odd i, so the one float of lead puts them on 8-byte
+// boundaries and no pair straddles a line.  Ghost rows and columns are kept (the sweep reads KW at i+1 and KS / KSW / KNW
+// of row j+1).  row(slot, j) takes the Cedar slot number (KO .. KNW) and points at element i = 0.
+struct Op2f {
+	const float *a;
+	size_t RS, SJ;
+	int ns;
+	__host__ __device__ __forceinline__ const float *row(int slot, size_t j) const
+	{
+		return a + j * SJ + (size_t)(slot == KO ? ns - 2 : slot - 1) * RS + 1;
+	}
+	__host__ __device__ __forceinline__ const float *rd(size_t j) const { return a + j * SJ + (size_t)(ns - 1) * RS + 1; }
+};
+static inline int op2f_slots(int nstncl) { return nstncl == 5 ? 6 : 4; }
+static inline size_t op2f_row_stride(int II) { return ilv32_row_stride(II + 1); }
+static inline size_t op2f_floats(int II, int JJ, int nstncl) { return op2f_row_stride(II) * op2f_slots(nstncl) * (size_t)JJ; }
+static inline Op2f op2f_view(const float *a, int II, int nstncl)
+{
+	const size_t RS = op2f_row_stride(II);
+	return Op2f{a, RS, RS * op2f_slots(nstncl), op2f_slots(nstncl)};
+}
+// build it from the Cedar planes (nstncl 5 | 3 of them) and the 1/diag plane (round to nearest even); *overflow as for
+// ilv32_build
+void op2f_build(const real_t *so, const real_t *sor_msor, float *out, int II, int JJ, int nstncl, int *overflow, hipStream_t st);
+// The 2D point sweep and residual on that view, batches as for the FP64 kernels (the item from the launch grid):
+// relax2_gs_op -- reference order (CEDAR_AMD_FRUN2 picks band-fused or two launches, as relax2_gs does); relax2_gs9_psum_op --
+// the partial-sum sweep where relax2_gs9_psum would run it (same run length), else relax2_gs_op.  Bit for bit the FP64
+// kernels of relax2d.hip / residual.hip on the rounded arrays (the device bodies are the same code: relax2_dev.h)
+void relax2_gs_op(const Op2f &A, const real_t *qf, real_t *q, int II, int JJ, int nstncl, int updown, hipStream_t st,
+                  Batch bt = Batch());
+void relax2_gs9_psum_op(const Op2f &A, const real_t *qf, real_t *q, int II, int JJ, int updown, hipStream_t st, Batch bt = Batch());
+void residual2_op(const Op2f &A, const real_t *qf, const real_t *q, real_t *res, int II, int JJ, int nstncl, hipStream_t st,
+                  Batch bt = Batch());
+
 // ---- kernel launchers (device pointers, asynchronous on `st`) ----
 // relax3d.hip
 void setup_recip(const real_t *so_diag, real_t *sor_msor, size_t II, size_t JJ, size_t KK, hipStream_t st);

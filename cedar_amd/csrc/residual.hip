@@ -9,6 +9,7 @@
 // 136 algorithmic B/DOF (27-pt), 64 B/DOF (9-pt).  Term order = reference,
 // -ffp-contract=off => bit-identical to the reference CPU build.
 #include "common.h"
+#include "relax2_dev.h"
 
 namespace cedar_amd {
 
@@ -42,11 +43,7 @@ __global__ __launch_bounds__(256) void residual2_kernel(const real_t *__restrict
 		res[x] = s;
 		return;
 	}
-	real_t s = qf[x];
-	s = s + so[KW * PS + x] * q[x - 1];
-	s = s + so[KW * PS + x + 1] * q[x + 1];
-	s = s + so[KS * PS + x] * q[x - sj];
-	s = s + so[KS * PS + x + sj] * q[x + sj];
+	real_t s = offdiag5(op2_cedar(so, nullptr, II, JJ), qf, q, i, (size_t)j, x, sj); // relax2_dev.h: shared with op2f.hip
 	if (NINE) {
 		s = s + so[KSW * PS + x] * q[x - 1 - sj];
 		s = s + so[KNW * PS + x + 1] * q[x + 1 - sj];

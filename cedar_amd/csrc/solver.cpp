@@ -50,6 +50,10 @@ struct Level {
 	// 3D 7-point (level 0): the single-precision copy of A and 1/diag (common.h Op7f) after
 	// cedar_amd_solver_use_fp32_operator_all; the level's sweeps and the cycle's residual read it, A itself stays FP64
 	float *A7f = nullptr;
+	// 2D, Dirichlet point relaxation: the single-precision copy of A and 1/diag (common.h Op2f) after
+	// cedar_amd_solver_use_fp32_operator_2d; the level's sweeps and the cycle's residual read it, A itself stays FP64.  Its
+	// presence alone decides that: a level that keeps it runs the row kernels, never the LDS-resident small-level ones
+	float *A2f = nullptr;
 	// 3D 27-point: partial-sum scratch of the relax sweep (relax3d_psum.hip), one vector
 	real_t *T = nullptr;
 	// the set-up products (A, P, SOR, At, PF*) belong to another solver of the same operator (plane relaxation:
@@ -82,6 +86,15 @@ template <class F> void with_cycle_view27(const Level &L, F &&f)
 template <class F, class G> void with_cycle_view7(const Level &L, F &&f, G &&g)
 {
 	if (L.A7f) f(op7f_view(L.A7f, L.II, L.JJ, L.KK));
+	else g();
+}
+
+// The same choice for a 2D level, made here and nowhere else: f(Op2f) on the float copy where the level keeps it, else g()
+// on the Cedar planes L.A / L.SOR0 -- the exact operator, which residual_true, the Krylov passes, interp_add2's diagonal,
+// restriction and the coarsest solve always read.
+template <class F, class G> void with_cycle_view2(const Level &L, F &&f, G &&g)
+{
+	if (L.A2f) f(op2f_view(L.A2f, L.II, L.nst));
 	else g();
 }
 
@@ -212,7 +225,10 @@ void clear(real_t *p, size_t n, hipStream_t st)
 void residual(const cedar_amd_solver *s, const Level &L, const real_t *x, const real_t *b, real_t *r, hipStream_t st)
 {
 	const Batch bt{s->nb, L.npts};
-	if (s->nd == 2) residual2(L.A, b, x, r, L.II, L.JJ, L.nst, st, bt);
+	if (s->nd == 2)
+		with_cycle_view2(
+		    L, [&](const Op2f &A) { residual2_op(A, b, x, r, L.II, L.JJ, L.nst, st, bt); },
+		    [&]() { residual2(L.A, b, x, r, L.II, L.JJ, L.nst, st, bt); });
 	else if (L.nst != 14 && (s->nb > 1 || L.A7f)) // (a single vector only for the float view: op7f.hip)
 		with_cycle_view7(
 		    L,
@@ -230,7 +246,8 @@ void residual(const cedar_amd_solver *s, const Level &L, const real_t *x, const 
 // cycle's residual, except on a level that keeps the float copy: there the same launches on the exact view
 void residual_true(const cedar_amd_solver *s, const Level &L, const real_t *x, const real_t *b, real_t *r, hipStream_t st)
 {
-	if (!L.A32 && !L.A7f) residual(s, L, x, b, r, st);
+	if (!L.A32 && !L.A7f && !L.A2f) residual(s, L, x, b, r, st);
+	else if (s->nd == 2) residual2(L.A, b, x, r, L.II, L.JJ, L.nst, st, Batch{s->nb, L.npts});
 	else if (s->nb > 1 && L.nst != 14) residual7_many(L.A, b, x, r, L.II, L.JJ, L.KK, st, Batch{s->nb, L.npts});
 	else if (s->nb > 1) residual27_many(exact_view27(L), b, x, r, L.II, L.JJ, L.KK, st, Batch{s->nb, L.npts});
 	else residual3(L.A, b, x, r, L.II, L.JJ, L.KK, L.nst, st);
@@ -399,7 +416,7 @@ void smooth(const cedar_amd_solver *s, const Level &L, real_t *x, const real_t *
 		relax_lines_small(L.A, b, x, L.SOR0, kind == 2 ? L.SOR0 : L.SOR1, L.II, L.JJ, L.nst, kind, updown, n, st, Batch{s->nb, L.npts});
 		return;
 	}
-	if (s->nd == 2 && s->st.ibc == 0 && s->st.relaxation == CEDAR_AMD_RELAX_POINT && lines_small_ok(L.II, L.JJ)) {
+	if (s->nd == 2 && s->st.ibc == 0 && s->st.relaxation == CEDAR_AMD_RELAX_POINT && !L.A2f && lines_small_ok(L.II, L.JJ)) {
 		relax_points_small(L.A, b, x, L.SOR0, L.II, L.JJ, L.nst, updown, n, st, Batch{s->nb, L.npts});
 		return;
 	}
@@ -446,8 +463,16 @@ void smooth(const cedar_amd_solver *s, const Level &L, real_t *x, const real_t *
 		switch (s->st.relaxation) {
 		case CEDAR_AMD_RELAX_POINT:
 			// nine-point levels of at least 4096 rows: the band-fused sweep with inter-row partial sums (relax2d.hip)
-			if (L.nst == 5 && relax2_psum_wanted(L.II, L.JJ)) relax2_gs9_psum(L.A, b, x, L.SOR0, L.II, L.JJ, updown, st, bt);
-			else relax2_gs(L.A, b, x, L.SOR0, L.II, L.JJ, L.nst, updown, st, bt);
+			with_cycle_view2(
+			    L,
+			    [&](const Op2f &A) {
+				    if (L.nst == 5 && relax2_psum_wanted(L.II, L.JJ)) relax2_gs9_psum_op(A, b, x, L.II, L.JJ, updown, st, bt);
+				    else relax2_gs_op(A, b, x, L.II, L.JJ, L.nst, updown, st, bt);
+			    },
+			    [&]() {
+				    if (L.nst == 5 && relax2_psum_wanted(L.II, L.JJ)) relax2_gs9_psum(L.A, b, x, L.SOR0, L.II, L.JJ, updown, st, bt);
+				    else relax2_gs(L.A, b, x, L.SOR0, L.II, L.JJ, L.nst, updown, st, bt);
+			    });
 			break;
 		case CEDAR_AMD_RELAX_LINE_X: relax_lines_x(L.A, b, x, L.SOR0, L.II, L.JJ, L.nst, updown, st, ipn, L.PFx, bt); break;
 		case CEDAR_AMD_RELAX_LINE_Y: lines_y(L, x, b, L.SOR0, updown, ipn, st, bt); break;
@@ -517,7 +542,8 @@ void ncycle(cedar_amd_solver *s, int lvl, real_t *x, const real_t *b, hipStream_
 	Level &L = s->lv[lvl], &K = s->lv[lvl + 1];
 	L.bt_fresh = false; // b of this visit has not been transposed yet
 	// a small 2D level: each half of the visit is one launch with the level resident in LDS (lines_small.hip)
-	const bool small = s->nd == 2 && s->st.ibc == 0 && s->st.relaxation <= CEDAR_AMD_RELAX_LINE_XY && lines_small_ok(L.II, L.JJ);
+	// (a level that keeps a float copy runs the row kernels on it: the copy's presence decides, before the small-level path)
+	const bool small = s->nd == 2 && s->st.ibc == 0 && s->st.relaxation <= CEDAR_AMD_RELAX_LINE_XY && !L.A2f && lines_small_ok(L.II, L.JJ);
 	const int kind = s->st.relaxation == CEDAR_AMD_RELAX_POINT ? 0 : s->st.relaxation == CEDAR_AMD_RELAX_LINE_X ? 1
 	               : s->st.relaxation == CEDAR_AMD_RELAX_LINE_Y ? 2 : 3;
 	const real_t *sory = kind == 2 ? L.SOR0 : L.SOR1;
@@ -862,6 +888,7 @@ void cedar_amd_solver_destroy(cedar_amd_solver *s)
 			(void)hipFree(L.P); (void)hipFree(L.SOR0); (void)hipFree(L.SOR1); (void)hipFree(L.At); (void)hipFree(L.Ailv);
 			(void)hipFree(L.A32);
 			(void)hipFree(L.A7f);
+			(void)hipFree(L.A2f);
 			(void)hipFree(L.PFx); (void)hipFree(L.PFy);
 		}
 		(void)hipFree(L.res); (void)hipFree(L.yscr); (void)hipFree(L.bt); (void)hipFree(L.xt); (void)hipFree(L.T);
@@ -922,7 +949,7 @@ static void pcg_precondition(cedar_amd_solver *s, int nmg, hipStream_t st);
 static int fp32_count(const cedar_amd_solver *s)
 {
 	int n = 0;
-	for (const Level &L : s->lv) n += (L.A32 || L.A7f) ? 1 : 0;
+	for (const Level &L : s->lv) n += (L.A32 || L.A7f || L.A2f) ? 1 : 0;
 	return n;
 }
 
@@ -940,7 +967,8 @@ static bool op32_build(cedar_amd_solver *s, const Level &L, float *out, hipStrea
 {
 	int *flag = s->dinfo + 1, host = 0; // (dinfo[0]: the coarse factorisation's info)
 	CEDAR_HIP_CHECK(hipMemsetAsync(flag, 0, sizeof(int), st));
-	if (L.nst == 14) ilv32_build(L.A, L.SOR0 + L.npts, out, L.II, L.JJ, L.KK, flag, st);
+	if (s->nd == 2) op2f_build(L.A, L.SOR0 + L.npts, out, L.II, L.JJ, L.nst, flag, st);
+	else if (L.nst == 14) ilv32_build(L.A, L.SOR0 + L.npts, out, L.II, L.JJ, L.KK, flag, st);
 	else op7f_build(L.A, L.SOR0 + L.npts, out, L.II, L.JJ, L.KK, flag, st);
 	CEDAR_HIP_CHECK(hipMemcpyAsync(&host, flag, sizeof(int), hipMemcpyDeviceToHost, st));
 	CEDAR_HIP_CHECK(hipStreamSynchronize(st));
@@ -1055,6 +1083,64 @@ int cedar_amd_solver_use_fp32_operator_all(cedar_amd_solver *s, int min_rows)
 	return op32_switch(s, min_rows, s->nb_alloc > 1, who, true);
 }
 
+// The switch for 2D handles, single or batch (Dirichlet, point relaxation, V- or F-cycle): every smoothed level with at
+// least min_rows rows, five-point level 0 and nine-point levels alike, takes a float copy (common.h Op2f, op2f.hip).
+// Written after op32_switch; the two share fp32_count, graphs_drop and op32_build.
+// min_rows = 0, the default: levels of at least 1024 rows.  Measured (tools/op32_2d_time.py, profiles/op32_2d_time.json;
+// DESIGN.md section 16) on the nine-point varcoef9 and the five-point gallery::poisson: with level 0 alone switched the
+// V(1,1) / V(2,1) cycle runs in 0.93 / 0.93 and 0.89 / 0.87 of its FP64 time at 4096^2, 0.88 / 0.87 and 0.91 / 0.91 at
+// 2048^2, 0.95 / 0.94 and 0.96 / 0.94 at 1024^2, each gain several times the spread of the repetitions; at 512^2 it is
+// 1.00 / 1.00 and 0.99 / 0.99, inside the spread, and adding a level of 512 rows to a larger handle's set gains nothing
+// (4096^2) or loses (1024^2: 0.951 -> 0.963).  So levels of 512 rows and fewer stay FP64 unless min_rows > 0 asks.
+enum { OP32_2D_DEFAULT_MIN_ROWS = 1024 };
+
+int cedar_amd_solver_use_fp32_operator_2d(cedar_amd_solver *s, int min_rows)
+{
+	const char *who = "cedar_amd_solver_use_fp32_operator_2d";
+	if (null_handle(s, who)) return -1;
+	auto refuse = [&](const char *reason) {
+		char msg[256];
+		snprintf(msg, sizeof(msg), "%s: %s; the handle is unchanged", who, reason);
+		print_error(msg);
+		return -1;
+	};
+	if (s->nd != 2) return refuse("3D handles are not supported (use cedar_amd_solver_use_fp32_operator_all)");
+	if (s->st.ibc != 0) return refuse("periodic boundary conditions (ibc != 0) are not supported");
+	if (s->st.relaxation != CEDAR_AMD_RELAX_POINT) return refuse("line relaxation is not supported");
+	if (min_rows < 0) return refuse("min_rows must not be negative");
+	if (min_rows == 0) {
+		const char *e = getenv("CEDAR_AMD_OP32_MIN_ROWS"); // read per call, like CEDAR_AMD_PSUM
+		min_rows = e && atoi(e) > 0 ? atoi(e) : (int)OP32_2D_DEFAULT_MIN_ROWS;
+	}
+	// all copies are built and checked before the handle changes
+	hipStream_t st = current_stream();
+	std::vector<std::pair<int, float *>> fresh;
+	auto undo = [&]() {
+		for (auto &f : fresh) (void)hipFree(f.second);
+	};
+	for (int l = 0; min_rows > 0 && l + 1 < (int)s->lv.size(); l++) {
+		const Level &L = s->lv[l];
+		if (L.A2f || L.ny < min_rows) continue;
+		float *c = nullptr;
+		if (hipMalloc((void **)&c, op2f_floats(L.II, L.JJ, L.nst) * sizeof(float)) != hipSuccess) {
+			(void)hipGetLastError();
+			undo();
+			return refuse("out of device memory for the single-precision copy");
+		}
+		fresh.emplace_back(l, c);
+		if (op32_build(s, L, c, st)) {
+			undo();
+			return refuse("an entry of the operator or of 1/diag overflows single precision");
+		}
+	}
+	if (!fresh.empty()) {
+		graphs_drop(s);
+		for (auto &f : fresh) s->lv[f.first].A2f = f.second;
+	}
+	launch_check(who);
+	return fp32_count(s);
+}
+
 // levels[lvl].A / .P / .SOR / ABD are public members of the reference's solver (include/cedar/level.h:14-41,
 // include/cedar/2d/solver.h:56): a caller may replace a set-up product.  Solver-internal copies that derive from the
 // array (row-interleaved solve copy, transposed y-line planes, scan-ordered line factors) are rebuilt.
@@ -1076,7 +1162,7 @@ size_t cedar_amd_solver_set(cedar_amd_solver *s, int lvl, const char *what, cons
 	else cedar_amd_memcpy_h2d(dst, in, n * sizeof(real_t));
 	if (L.Ailv && (!strcmp(what, "A") || !strcmp(what, "SOR0")))
 		ilv_build(L.A, L.SOR0 + L.npts, L.Ailv, L.II, L.JJ, L.KK, st);
-	float *&c32 = L.nst == 14 ? L.A32 : L.A7f; // the level's float copy, of either kind
+	float *&c32 = s->nd == 2 ? L.A2f : L.nst == 14 ? L.A32 : L.A7f; // the level's float copy, of any kind
 	if (c32 && (!strcmp(what, "A") || !strcmp(what, "SOR0")) && op32_build(s, L, c32, st)) {
 		// the new entries do not fit float: the level goes back to the FP64 planes (the captured cycle names the copy)
 		char msg[] = "cedar_amd_solver_set: an entry of the new array overflows single precision; the level reads the FP64 "

@@ -274,6 +274,17 @@ public:
 		}
 		return cedar_amd_solver_use_fp32_operator_all(h, min_rows);
 	}
+	// the switch for a 2D solver, one or several right-hand sides, Dirichlet point relaxation
+	// (cedar_amd_solver_use_fp32_operator_2d): min_rows > 0 takes every smoothed level with at least that many rows,
+	// five- and nine-point alike; min_rows = 0: the measured default (levels of at least 1024 rows)
+	int use_fp32_operator_2d(int min_rows = 0)
+	{
+		if (!h) {
+			log::error << "use_fp32_operator_2d: needs the device-resident solver (every kernel \"hip\")" << std::endl;
+			return -1;
+		}
+		return cedar_amd_solver_use_fp32_operator_2d(h, min_rows);
+	}
 	int fp32_levels() const { return h ? cedar_amd_solver_fp32_levels(h) : 0; }
 
 	void vcycle(grid_func & x, const grid_func & b)

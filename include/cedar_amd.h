@@ -210,6 +210,25 @@ int cedar_amd_residual7_op32(real_t *so, real_t *qf, real_t *q, real_t *res, len
  * those F rows.  Same contract as cedar_amd_relax3_gs_psum; the resident solver runs it on levels with at least 4096 rows
  * (rows of 2048 to 4350 points; CEDAR_AMD_FRUN2 = run length).  Returns 1, or 0 when the reference-order sweep ran. */
 int cedar_amd_relax2_gs_psum(real_t *so, real_t *qf, real_t *q, real_t *sor, len_t ii, len_t jj, int updown);
+/* The 2D point sweep and residual on the operator and 1/diag rounded to single precision (so: nstncl = 5 | 3 planes; what
+ * a 2D level runs after cedar_amd_solver_use_fp32_operator_2d): a row-interleaved float copy of KW, KS, [KSW, KNW,] KO and
+ * 1/diag is built for the call and dropped after it; entries are promoted to double on load, vectors and arithmetic stay
+ * FP64 -- bit for bit BMG2_SymStd_relax_GS / BMG2_SymStd_residual (and cedar_amd_relax2_gs_psum, at the same run length)
+ * on so and sor rounded to float.  Rows of any length.
+ *   cedar_amd_relax2_gs_op32       reference order (CEDAR_AMD_FRUN2 picks band-fused or two launches as for
+ *                                  BMG2_SymStd_relax_GS); returns 0;
+ *   cedar_amd_relax2_gs_psum_op32  nine-point only; returns 1, or 0 when the reference-order sweep ran, as
+ *                                  cedar_amd_relax2_gs_psum does;
+ *   cedar_amd_residual2_op32       returns 0.
+ * A NULL array, nstncl other than 3 / 5, or an entry that overflows float: print_error, -1, q / res untouched. */
+int cedar_amd_relax2_gs_op32(real_t *so, real_t *qf, real_t *q, real_t *sor, len_t ii, len_t jj, int nstncl, int updown);
+int cedar_amd_relax2_gs_psum_op32(real_t *so, real_t *qf, real_t *q, real_t *sor, len_t ii, len_t jj, int updown);
+int cedar_amd_residual2_op32(real_t *so, real_t *qf, real_t *q, real_t *res, len_t ii, len_t jj, int nstncl);
+/* the same on nrhs (1 .. 32) items stored back to back, the operator shared: item m has the bits of the single call on
+ * item m alone; nrhs outside 1 .. 32: print_error, -1 */
+int cedar_amd_relax2_gs_many_op32(int nrhs, real_t *so, real_t *qf, real_t *q, real_t *sor, len_t ii, len_t jj, int nstncl,
+                                  int updown);
+int cedar_amd_residual2_many_op32(int nrhs, real_t *so, real_t *qf, real_t *q, real_t *res, len_t ii, len_t jj, int nstncl);
 /* recompute column icol (0-based incl. ghost) of that row class after its x-neighbour column changed */
 void cedar_amd_relax3_fixup(real_t *so, real_t *qf, real_t *q, real_t *sor, len_t ii, len_t jj, len_t kk,
                             int icol, int jb, int kb);
@@ -496,6 +515,30 @@ int cedar_amd_solver_use_fp32_operator_many(cedar_amd_solver *s, int min_rows);
  * cedar_amd_solver_set "A" / "SOR0" on level 0 rebuild the copy (overflow: reported, the level reads FP64 again).
  * The two calls above are unchanged: on a 7-point handle they switch the 27-point levels only. */
 int cedar_amd_solver_use_fp32_operator_all(cedar_amd_solver *s, int min_rows);
+/* The switch for a 2D handle, single or of cedar_amd_solver_create_many: Dirichlet (ibc == 0), point relaxation, V- or
+ * F-cycle.  Every smoothed level (all but the coarsest) that the call takes -- the five-point level 0 and the nine-point
+ * levels alike -- gets a row-interleaved float copy of its operator and 1/diag (KW, KS, [KSW, KNW,] KO, 1/diag; DESIGN.md
+ * section 16), which its sweeps (two row-class launches, band-fused, or the partial-sum sweep where the level would run
+ * it in FP64, at the same run length) and the cycle's residual read; the reported residual, the Krylov passes,
+ * interpolation's diagonal, restriction and the coarsest solve keep reading the FP64 operator.  The presence of a level's
+ * copy alone decides what its sweeps and the cycle's residual read: a level of at most 64 x 64 unknowns that took a copy
+ * runs the row kernels instead of the LDS-resident small-level kernels.
+ *   min_rows > 0: every smoothed level with at least min_rows rows.
+ *   min_rows 0  : the measured default, levels of at least 1024 rows (CEDAR_AMD_OP32_MIN_ROWS overrides it, read at the
+ *                 call).  DESIGN.md section 16: with level 0 switched the V-cycle runs in 0.87 .. 0.93 of its FP64 time
+ *                 at 4096^2, 0.87 .. 0.91 at 2048^2 and 0.94 .. 0.96 at 1024^2 (nine- and five-point, V(1,1) and
+ *                 V(2,1)); at 512^2 the two are equal within the spread, so smaller levels stay FP64 unless min_rows > 0
+ *                 asks for them.
+ * Copies are built and checked before the handle changes, captured graphs are dropped, the call may be repeated and never
+ * switches a level back; returns cedar_amd_solver_fp32_levels.  Refused -- print_error, -1, handle unchanged -- for a NULL
+ * handle, a 3D handle (use cedar_amd_solver_use_fp32_operator_all), ibc != 0, line relaxation, a negative min_rows, an
+ * entry of A or 1/diag that overflows float, and out of device memory.  The other calls behave as on a switched 3D
+ * handle (above): _vcycle / _vcycle_many run the cycle of the rounded operator, _pcg / _fcg / _pcg_many / _fcg_many /
+ * _precondition precondition with it and run the recurrence on the FP64 operator, _solve / _solve_many go to
+ * defect-correction form, an F-cycle handle's _solve starts each cycle from x = 0 and reports the FP64 residual, and
+ * cedar_amd_solver_set "A" / "SOR0" on a switched level rebuild its copy (overflow: reported, the level reads FP64 again).
+ * The three calls above keep refusing 2D handles. */
+int cedar_amd_solver_use_fp32_operator_2d(cedar_amd_solver *s, int min_rows);
 
 /* Several right-hand sides at once on one resident hierarchy.  The operator, 1/diag and the interpolation weights are
  * the same for every right-hand side, so the batched 3D kernels (many3d.hip) fetch them once per workgroup task and apply
