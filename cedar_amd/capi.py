@@ -193,6 +193,19 @@ class Kernels:
         return lib.cedar_amd_relax2_gs_many_op32(q.shape[0] if nrhs is None else nrhs, _p(so), _p(qf), _p(q), _p(sor),
                                                  u(II), u(JJ), nst, updown)
 
+    def relax2_lines_op32(self, so, qf, q, sor, dir, updown):
+        """one zebra line sweep (dir 0: x lines, 1: y lines with sor = SOR(JJ,II,2)) on the operator and the line factors
+        rounded to single precision (cedar_amd_relax2_lines_op32); 0, or -1 if refused (q untouched)"""
+        nst, JJ, II = so.shape
+        return lib.cedar_amd_relax2_lines_op32(_p(so), _p(qf), _p(q), _p(sor), u(II), u(JJ), nst, dir, updown)
+
+    def relax2_lines_many_op32(self, so, qf, q, sor, dir, updown, nrhs=None):
+        """relax2_lines_op32 on the items of qf, q of shape (nrhs,) + grid (cedar_amd_relax2_lines_many_op32); 0, or -1 if
+        refused"""
+        nst, JJ, II = so.shape
+        return lib.cedar_amd_relax2_lines_many_op32(q.shape[0] if nrhs is None else nrhs, _p(so), _p(qf), _p(q), _p(sor),
+                                                    u(II), u(JJ), nst, dir, updown)
+
     def residual2_many_op32(self, so, qf, q, res, nrhs=None):
         """residual2_op32 on the items of qf, q, res (cedar_amd_residual2_many_op32); 0, or -1 if refused"""
         nst, JJ, II = so.shape
@@ -579,6 +592,8 @@ lib.cedar_amd_solver_use_fp32_operator_all.restype = C.c_int
 lib.cedar_amd_solver_use_fp32_operator_all.argtypes = [C.c_void_p, C.c_int]
 lib.cedar_amd_solver_use_fp32_operator_2d.restype = C.c_int
 lib.cedar_amd_solver_use_fp32_operator_2d.argtypes = [C.c_void_p, C.c_int]
+lib.cedar_amd_solver_use_fp32_operator_lines.restype = C.c_int
+lib.cedar_amd_solver_use_fp32_operator_lines.argtypes = [C.c_void_p, C.c_int]
 lib.cedar_amd_solver_fp32_levels.restype = C.c_int
 lib.cedar_amd_solver_fp32_levels.argtypes = [C.c_void_p]
 
@@ -746,6 +761,13 @@ class Solver:
         min_rows > 0 switches every smoothed level with at least that many rows, five- and nine-point alike; 0 takes the
         measured default (levels of at least 1024 rows).  Returns the number of levels that read a float copy, -1 if refused"""
         return lib.cedar_amd_solver_use_fp32_operator_2d(self.h, int(min_rows))
+
+    def use_fp32_operator_lines(self, min_rows=0):
+        """the switch for a 2D handle, single or batch, Dirichlet line relaxation (cedar_amd_solver_use_fp32_operator_lines):
+        min_rows > 0 switches every smoothed level with at least that many rows that the small-level kernels do not serve
+        (more than 64 x 64 unknowns); 0 takes the measured default.  Returns the number of levels that read float copies,
+        -1 if refused"""
+        return lib.cedar_amd_solver_use_fp32_operator_lines(self.h, int(min_rows))
 
     def fp32_levels(self):
         return lib.cedar_amd_solver_fp32_levels(self.h)

@@ -1081,6 +1081,79 @@ int cedar_amd_residual2_many_op32(int nrhs, real_t *so, real_t *qf, real_t *q, r
 	return op32_2d("cedar_amd_residual2_many_op32", 2, nrhs, so, qf, q, res, ii, jj, nstncl, 0);
 }
 
+// ---- one zebra line sweep on single-precision copies of the operator and the line factors built for the call
+// (linesf.hip; include/cedar_amd.h).  dir 0: x lines; dir 1: y lines on transposed arrays (sor = SOR(JJ,II,2))
+static int op32_lines(const char *who, int nrhs, real_t *so, real_t *qf, real_t *q, real_t *sor, len_t ii, len_t jj, int nstncl,
+                      int dir, int updown)
+{
+	const int II = (int)ii, JJ = (int)jj;
+	const int n = dir ? JJ - 2 : II - 2, nlines = dir ? II - 2 : JJ - 2; // unknowns of a line, lines
+	const char *why = nrhs < 1 || nrhs > CEDAR_AMD_MAX_RHS ? "nrhs must be 1 .. 32"
+	                  : nstncl != 3 && nstncl != 5 ? "nstncl must be 3 or 5"
+	                  : !(so && qf && q && sor) ? "a required array is NULL"
+	                  : dir != 0 && dir != 1 ? "dir must be 0 (x lines) or 1 (y lines)"
+	                  : n > 0 && !line_fits_lds_host(n) ? "a line does not fit the 160 KB LDS of a CU" : nullptr;
+	char buf[200];
+	if (why) {
+		snprintf(buf, sizeof(buf), "%s: %s; nothing done", who, why);
+		report(buf);
+		return -1;
+	}
+	if (II < 3 || JJ < 3) return 0; // no unknowns
+	const size_t P = (size_t)ii * jj;
+	Staged sso(so, P * nstncl, true, false), sqf(qf, P * nrhs, true, false), sq(q, P * nrhs, true, true), ssor(sor, P * 2, true, false);
+	hipStream_t st = current_stream();
+	// the grid the kernel sees: for y lines the transposed one (JJ fast)
+	const int GI = dir ? JJ : II, GJ = dir ? II : JJ;
+	const size_t abytes = op2f_floats(GI, GJ, nstncl) * sizeof(float);
+	const size_t npf = lines_permuted_doubles(n, nlines);
+	const size_t fbytes = (npf ? npf : P * 2) * sizeof(float);
+	const size_t tbytes = dir ? P * sizeof(real_t) : 0; // transposed planes, right-hand sides and scratch for q^T
+	float *c = static_cast<float *>(pool_get(abytes)), *f = static_cast<float *>(pool_get(fbytes));
+	real_t *sot = dir ? static_cast<real_t *>(pool_get(tbytes * nstncl)) : nullptr;
+	real_t *qft = dir ? static_cast<real_t *>(pool_get(tbytes * nrhs)) : nullptr, *qt = dir ? static_cast<real_t *>(pool_get(tbytes * nrhs)) : nullptr;
+	int *flag = static_cast<int *>(pool_get(sizeof(int))), host = 0;
+	CEDAR_HIP_CHECK(hipMemsetAsync(flag, 0, sizeof(int), st));
+	const Batch bt{nrhs, P};
+	if (dir) {
+		zero_fill(sot, P * nstncl, st); // (the centre plane is not transposed: setup_lines_yt)
+		setup_lines_yt(sso.get(), sot, II, JJ, nstncl, st);
+		transpose2(sqf.get(), qft, II, JJ, st, bt);
+	}
+	op2f_build(dir ? sot : sso.get(), nullptr, c, GI, GJ, nstncl, flag, st);
+	if (npf) linesf_permute(ssor.get(), f, n, GI, nlines, P, flag, st);
+	else linesf_image(ssor.get(), f, II, JJ, flag, st);
+	CEDAR_HIP_CHECK(hipMemcpyAsync(&host, flag, sizeof(int), hipMemcpyDeviceToHost, st));
+	CEDAR_HIP_CHECK(hipStreamSynchronize(st));
+	pool_put(flag, sizeof(int));
+	int ret = 0;
+	if (host) {
+		snprintf(buf, sizeof(buf), "%s: an entry of the operator or of a line factor overflows single precision; nothing done", who);
+		report(buf);
+		ret = -1; // (staged host arrays go back as they came)
+	} else {
+		const Op2f A = op2f_view(c, GI, nstncl);
+		const float *fs = npf ? nullptr : f, *fp = npf ? f : nullptr;
+		if (dir) relax_lines_yt_op(A, qft, sq.get(), qt, fs, II, JJ, nstncl, updown, st, fp, bt);
+		else relax_lines_x_op(A, sqf.get(), sq.get(), fs, II, JJ, nstncl, updown, st, fp, bt);
+		CEDAR_HIP_CHECK(hipStreamSynchronize(st));
+	}
+	if (dir) { pool_put(sot, tbytes * nstncl); pool_put(qft, tbytes * nrhs); pool_put(qt, tbytes * nrhs); }
+	pool_put(c, abytes); pool_put(f, fbytes);
+	return ret;
+}
+
+int cedar_amd_relax2_lines_op32(real_t *so, real_t *qf, real_t *q, real_t *sor, len_t ii, len_t jj, int nstncl, int dir, int updown)
+{
+	return op32_lines("cedar_amd_relax2_lines_op32", 1, so, qf, q, sor, ii, jj, nstncl, dir, updown);
+}
+
+int cedar_amd_relax2_lines_many_op32(int nrhs, real_t *so, real_t *qf, real_t *q, real_t *sor, len_t ii, len_t jj, int nstncl,
+                                     int dir, int updown)
+{
+	return op32_lines("cedar_amd_relax2_lines_many_op32", nrhs, so, qf, q, sor, ii, jj, nstncl, dir, updown);
+}
+
 int cedar_amd_restrict3_many(int nrhs, real_t *q, real_t *qc, real_t *ci, len_t ii, len_t jj, len_t kk, len_t iic, len_t jjc,
                              len_t kkc)
 {

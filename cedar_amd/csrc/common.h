@@ -173,6 +173,7 @@ static inline Op2f op2f_view(const float *a, int II, int nstncl)
 }
 // build it from the Cedar planes (nstncl 5 | 3 of them) and the 1/diag plane (round to nearest even); *overflow as for
 // ilv32_build
+// sor_msor == nullptr (a line-relaxed level, which has no 1/diag plane): that slot-row is zeros
 void op2f_build(const real_t *so, const real_t *sor_msor, float *out, int II, int JJ, int nstncl, int *overflow, hipStream_t st);
 // The 2D point sweep and residual on that view, batches as for the FP64 kernels (the item from the launch grid):
 // relax2_gs_op -- reference order (CEDAR_AMD_FRUN2 picks band-fused or two launches, as relax2_gs does); relax2_gs9_psum_op --
@@ -183,6 +184,21 @@ void relax2_gs_op(const Op2f &A, const real_t *qf, real_t *q, int II, int JJ, in
 void relax2_gs9_psum_op(const Op2f &A, const real_t *qf, real_t *q, int II, int JJ, int updown, hipStream_t st, Batch bt = Batch());
 void residual2_op(const Op2f &A, const real_t *qf, const real_t *q, real_t *res, int II, int JJ, int nstncl, hipStream_t st,
                   Batch bt = Batch());
+
+// Line relaxation on such copies (cedar_amd_solver_use_fp32_operator_lines; linesf.hip): the operator
+// as Op2f (the 1/diag slot-row zeros), for y lines the Op2f of the transposed planes (setup_lines_yt) on the transposed grid;
+// the factors as floats in the two forms the FP64 kernels read -- linesf_image: the two SOR planes, element for element;
+// linesf_permute: the scan-ordered copy (lines_permuted_doubles elements; a lane's eight values of a kind are two 16-byte
+// loads).  Both round the FP64 factors to nearest even and raise *overflow as op2f_build does.  relax_lines_x_op /
+// relax_lines_yt_op: relax_lines_x / relax_lines_yt (Dirichlet) on these arrays, bit for bit the FP64 kernels on the rounded
+// operator and factors (the device bodies are the same code: lines_dev.h); pff == nullptr: the factors are read from sorf
+void linesf_image(const real_t *sor, float *out, int II, int JJ, int *overflow, hipStream_t st);
+void linesf_permute(const real_t *sor, float *pf, int n, int ld, int nlines, size_t PS, int *overflow, hipStream_t st);
+void relax_lines_x_op(const Op2f &A, const real_t *qf, real_t *q, const float *sorf, int II, int JJ, int nstncl, int updown,
+                      hipStream_t st, const float *pff = nullptr, Batch bt = Batch());
+void relax_lines_yt_op(const Op2f &At, const real_t *qft, real_t *q, real_t *qt, const float *sorf, int II, int JJ, int nstncl,
+                       int updown, hipStream_t st, const float *pff = nullptr, Batch bt = Batch());
+bool line_fits_lds_host(int n); // lines.hip: a line of n unknowns fits the LDS of a CU
 
 // ---- kernel launchers (device pointers, asynchronous on `st`) ----
 // relax3d.hip

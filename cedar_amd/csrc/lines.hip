@@ -24,6 +24,7 @@
 // layout the reference uses for the y factors, SOR(JJ,II,2)), solved by the
 // same kernel, and scattered back.
 #include "common.h"
+#include "lines_dev.h"
 
 namespace cedar_amd {
 
@@ -104,214 +105,9 @@ void setup_lines_y(const real_t *so, real_t *sor, int II, int JJ, hipStream_t st
 	hipLaunchKernelGGL(lines_factor, dim3((II - 2 + 63) / 64), dim3(64), 0, st, sor, JJ - 2, JJ, II - 2, (size_t)II * JJ);
 }
 
-// ------------------------------------------------------------------ affine scan
-// Every lane owns CH consecutive unknowns of the line.  A sweep over a tile of BS*CH unknowns is
-//   (1) lane-local: compose the CH maps  y -> a*y + c  of the chunk            (sequential, exact order)
-//   (2) workgroup scan of the BS composites: Kogge-Stone over wavefront shuffles, cross-wave fix-up
-//       through LDS, scalar carry from the previous tile
-//   (3) lane-local: re-run the chunk from the value entering it.
-// Only step (2) re-associates the recurrence.
-constexpr int CH = 8;
-__device__ __forceinline__ int lpad(int i) { return i + (i >> 3); } // LDS index: one pad per 8 -> stride-9 chunks, no bank conflicts
-
-// (p[0], p[1]) with one 16-byte load (8-byte aligned)
-__device__ __forceinline__ void ldpair2(const real_t *__restrict__ p, real_t *out)
-{
-	const d2u v = *reinterpret_cast<const d2u *>(p);
-	out[0] = v.x; out[1] = v.y;
-}
-
-template <int BS>
-__device__ __forceinline__ void affine_scan(real_t a, real_t c, real_t carry, real_t *wa, real_t *wc,
-                                            real_t &y_in, real_t &y_last)
-{
-	const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-#pragma unroll
-	for (int off = 1; off < 64; off <<= 1) {
-		const real_t ap = __shfl_up(a, off, 64), cp = __shfl_up(c, off, 64);
-		if (lane >= off) {
-			c = a * cp + c;
-			a = a * ap;
-		}
-	}
-	real_t ae = __shfl_up(a, 1, 64), ce = __shfl_up(c, 1, 64); // composite of the lanes before this one
-	if (lane == 0) { ae = 1.0; ce = 0.0; }
-	constexpr int NW = BS / 64;
-	if (NW > 1) {
-		if (lane == 63) { wa[w] = a; wc[w] = c; }
-		__syncthreads();
-		real_t y = carry;
-		for (int u = 0; u < w; u++) y = wa[u] * y + wc[u];
-		carry = y;
-	}
-	y_in = ae * carry + ce;
-	y_last = a * carry + c;
-}
-
-// Solve L D L^T x = y for the line held in LDS (padded index lpad(i)); d[0..n), e[0..n-1) in HBM.
-template <int BS>
-__device__ __forceinline__ void line_pttrs(real_t *y, int n, const real_t *__restrict__ d, const real_t *__restrict__ e,
-                                           real_t *wa, real_t *wc, real_t *carry_slot)
-{
-	// forward: y_i = y_i - e_{i-1} y_{i-1}
-	real_t carry = 0.0;
-	for (int base = 0; base < n; base += BS * CH) {
-		const int i0 = base + (int)threadIdx.x * CH;
-		real_t a[CH], c[CH];
-#pragma unroll
-		for (int m = 0; m < CH; m++) {
-			const int i = i0 + m;
-			if (i < n) { c[m] = y[lpad(i)]; a[m] = i > 0 ? -e[i - 1] : 0.0; }
-			else { c[m] = 0.0; a[m] = 0.0; }
-		}
-		real_t A = 1.0, Cc = 0.0;
-#pragma unroll
-		for (int m = 0; m < CH; m++) { Cc = a[m] * Cc + c[m]; A = a[m] * A; }
-		real_t v, last;
-		affine_scan<BS>(A, Cc, carry, wa, wc, v, last);
-#pragma unroll
-		for (int m = 0; m < CH; m++) {
-			v = a[m] * v + c[m];
-			if (i0 + m < n) y[lpad(i0 + m)] = v;
-		}
-		if (threadIdx.x == BS - 1) *carry_slot = last;
-		__syncthreads();
-		carry = *carry_slot;
-		__syncthreads();
-	}
-	// backward: x_i = y_i/d_i - e_i x_{i+1}; reversed position r <-> i = n-1-r
-	carry = 0.0;
-	for (int base = 0; base < n; base += BS * CH) {
-		const int r0 = base + (int)threadIdx.x * CH;
-		real_t a[CH], c[CH];
-#pragma unroll
-		for (int m = 0; m < CH; m++) {
-			const int r = r0 + m, i = n - 1 - r;
-			if (r < n) { c[m] = y[lpad(i)] / d[i]; a[m] = r > 0 ? -e[i] : 0.0; }
-			else { c[m] = 0.0; a[m] = 0.0; }
-		}
-		real_t A = 1.0, Cc = 0.0;
-#pragma unroll
-		for (int m = 0; m < CH; m++) { Cc = a[m] * Cc + c[m]; A = a[m] * A; }
-		real_t v, last;
-		affine_scan<BS>(A, Cc, carry, wa, wc, v, last);
-#pragma unroll
-		for (int m = 0; m < CH; m++) {
-			v = a[m] * v + c[m];
-			if (r0 + m < n) y[lpad(n - 1 - r0 - m)] = v;
-		}
-		if (threadIdx.x == BS - 1) *carry_slot = last;
-		__syncthreads();
-		carry = *carry_slot;
-		__syncthreads();
-	}
-}
-
-// The same solve on a scan-ordered copy of the factors (resident solver, lines longer than a wavefront tile).
-// line_pttrs reads e / d where the scan needs them: lane L owns unknowns 8L .. 8L+7 of a tile, so one wave
-// instruction gathers 64 x 8 bytes spread over 4 KB -- 32 cache lines for 512 useful bytes -- and the sweeps of a
-// line wait on eight such gathers.  Measured at 8192^2 (profiles/r02_experiment_line_relax.log): 0.52 of the 1.34 ms
-// of an x sweep is this solve, 0.22 ms of it the gathers alone.  The copy stores, per line and tile of BS*CH unknowns,
-// the forward multipliers a = -e(i-1), the backward multipliers a = -e(i) and the pivots d(i) in the order the lanes
-// consume them: [tile][kind][m/2][lane][m%2], so every load is a coalesced 16-byte-per-lane stream, and the next
-// tile's factors are requested before the current tile is scanned.  Same values, same chunks, same scan =>
-// bit-identical to line_pttrs.
-template <int BS> __host__ __device__ inline size_t pf_tiles(int n) { return (size_t)(n + BS * CH - 1) / (BS * CH); }
-template <int BS> __host__ __device__ inline size_t pf_line_doubles(int n) { return pf_tiles<BS>(n) * 3 * CH * BS; }
-template <int BS> __device__ __forceinline__ size_t pf_off(int t, int kind, int m, int lane)
-{
-	return ((((size_t)t * 3 + kind) * (CH / 2) + (m >> 1)) * BS + lane) * 2 + (m & 1);
-}
-
-template <int BS>
-__global__ __launch_bounds__(BS) void lines_permute_kernel(const real_t *__restrict__ sor, real_t *__restrict__ pf,
-                                                            int n, int ld, size_t PS)
-{
-	const int l = blockIdx.x;
-	const real_t *d = sor + (size_t)ld * (l + 1) + 1, *e = sor + PS + (size_t)ld * (l + 1) + 2;
-	real_t *out = pf + (size_t)l * pf_line_doubles<BS>(n);
-	const int nt = (int)pf_tiles<BS>(n);
-	for (int t = 0; t < nt; t++)
-		for (int m = 0; m < CH; m++) {
-			const int r = t * BS * CH + (int)threadIdx.x * CH + m, i = n - 1 - r; // forward position r, backward unknown i
-			out[pf_off<BS>(t, 0, m, threadIdx.x)] = (r < n && r > 0) ? -e[r - 1] : 0.0;
-			out[pf_off<BS>(t, 1, m, threadIdx.x)] = (r < n && r > 0) ? -e[i] : 0.0;
-			out[pf_off<BS>(t, 2, m, threadIdx.x)] = r < n ? d[i] : 1.0;
-		}
-}
-
-template <int BS>
-__device__ __forceinline__ void pf_load(const real_t *__restrict__ pfl, int t, int kind, real_t (&v)[CH])
-{
-#pragma unroll
-	for (int mp = 0; mp < CH / 2; mp++) {
-		const d2u w = *reinterpret_cast<const d2u *>(pfl + pf_off<BS>(t, kind, 2 * mp, threadIdx.x));
-		v[2 * mp] = w.x; v[2 * mp + 1] = w.y;
-	}
-}
-
-template <int BS>
-__device__ __forceinline__ void line_pttrs_pf(real_t *y, int n, const real_t *__restrict__ pfl,
-                                              real_t *wa, real_t *wc, real_t *carry_slot)
-{
-	const int nt = (int)pf_tiles<BS>(n);
-	real_t a[CH], an[CH], dn[CH], dd[CH];
-	pf_load<BS>(pfl, 0, 0, a);
-	real_t carry = 0.0;
-	for (int t = 0; t < nt; t++) {
-		if (t + 1 < nt) pf_load<BS>(pfl, t + 1, 0, an); // next tile, or ...
-		else { pf_load<BS>(pfl, 0, 1, an); pf_load<BS>(pfl, 0, 2, dn); } // ... the first backward tile
-		const int i0 = t * BS * CH + (int)threadIdx.x * CH;
-		real_t c[CH];
-#pragma unroll
-		for (int m = 0; m < CH; m++) c[m] = i0 + m < n ? y[lpad(i0 + m)] : 0.0;
-		real_t A = 1.0, Cc = 0.0;
-#pragma unroll
-		for (int m = 0; m < CH; m++) { Cc = a[m] * Cc + c[m]; A = a[m] * A; }
-		real_t v, last;
-		affine_scan<BS>(A, Cc, carry, wa, wc, v, last);
-#pragma unroll
-		for (int m = 0; m < CH; m++) {
-			v = a[m] * v + c[m];
-			if (i0 + m < n) y[lpad(i0 + m)] = v;
-		}
-		if (threadIdx.x == BS - 1) *carry_slot = last;
-		__syncthreads();
-		carry = *carry_slot;
-		__syncthreads();
-#pragma unroll
-		for (int m = 0; m < CH; m++) a[m] = an[m];
-	}
-#pragma unroll
-	for (int m = 0; m < CH; m++) dd[m] = dn[m];
-	carry = 0.0;
-	for (int t = 0; t < nt; t++) {
-		if (t + 1 < nt) { pf_load<BS>(pfl, t + 1, 1, an); pf_load<BS>(pfl, t + 1, 2, dn); }
-		const int r0 = t * BS * CH + (int)threadIdx.x * CH;
-		real_t c[CH];
-#pragma unroll
-		for (int m = 0; m < CH; m++) {
-			const int r = r0 + m;
-			c[m] = r < n ? y[lpad(n - 1 - r)] / dd[m] : 0.0;
-		}
-		real_t A = 1.0, Cc = 0.0;
-#pragma unroll
-		for (int m = 0; m < CH; m++) { Cc = a[m] * Cc + c[m]; A = a[m] * A; }
-		real_t v, last;
-		affine_scan<BS>(A, Cc, carry, wa, wc, v, last);
-#pragma unroll
-		for (int m = 0; m < CH; m++) {
-			v = a[m] * v + c[m];
-			if (r0 + m < n) y[lpad(n - 1 - r0 - m)] = v;
-		}
-		if (threadIdx.x == BS - 1) *carry_slot = last;
-		__syncthreads();
-		carry = *carry_slot;
-		__syncthreads();
-#pragma unroll
-		for (int m = 0; m < CH; m++) { a[m] = an[m]; dd[m] = dn[m]; }
-	}
-}
+// ------------------------------------------------------------------ line solves
+// The affine scan, both DPTTRS forms, the right-hand-side formation, the x-line kernel and its launchers are in
+// lines_dev.h, shared with the single-precision instantiations of linesf.hip; this file instantiates the FP64 forms.
 
 // Generic first-order recurrence over line-contiguous data, one workgroup per line:
 //   forward  (reverse = 0): y_i = a_i * y_{i-1} + c_i,  i = 0..n-1,   y_{-1} = 0
@@ -362,215 +158,6 @@ void affine_lines(real_t *y, const real_t *a, const real_t *div, int nlines, int
 	else hipLaunchKernelGGL(affine_lines_kernel<256>, dim3(nlines), dim3(256), 0, st, y, a, div, n, ld, reverse);
 }
 
-// doubles of LDS a line of n unknowns needs (padded line + scan scratch)
-static inline size_t line_lds_doubles(int n) { return (size_t)n + (size_t)(n >> 3) + 40; } // line + 16 + 16 wave aggregates + carry
-
-// ------------------------------------------------------------------ x-lines
-// Sherman-Morrison closure of a cyclic line held in LDS: y holds the solution of the folded system;
-// a second solve with the rank-one column u (-c_first at the first, -c_last at the last unknown),
-// alpha = u_1 + u_n, beta = (y_1 + y_n) / (1 + alpha), x = y - beta u (relax_lines_x.f90:212-226).
-// On return `y` holds u and every lane holds beta; ys[t] (lane-strided) kept the first solution.
-template <int BS>
-__device__ __forceinline__ real_t line_sherman_morrison(real_t *y, int n, const real_t *__restrict__ d,
-                                                        const real_t *__restrict__ e, real_t cfirst, real_t clast,
-                                                        real_t *wa, real_t *wc, real_t *cs, real_t &y1, real_t &yn)
-{
-	y1 = y[lpad(0)];
-	yn = y[lpad(n - 1)];
-	__syncthreads();
-	for (int t = threadIdx.x; t < n; t += BS) y[lpad(t)] = 0.0;
-	__syncthreads();
-	if (threadIdx.x == 0) {
-		y[lpad(0)] = -cfirst;
-		y[lpad(n - 1)] = -clast; // n == 1: the second assignment wins, as in the reference
-	}
-	__syncthreads();
-	line_pttrs<BS>(y, n, d, e, wa, wc, cs);
-	const real_t alpha = y[lpad(0)] + y[lpad(n - 1)];
-	real_t beta = y1 + yn;
-	beta = beta / (1.0 + alpha);
-	return beta;
-}
-
-// YT: the arrays are the transposed ones of a y-line sweep (setup_lines_yt): rows are the y lines, and the two
-// cross terms are added in relax_lines_y.f90's order
-template <int BS, bool NINE, bool SM = false, bool YT = false, bool PERM = false>
-__global__ __launch_bounds__(BS) void relax_lines_x_kernel(const real_t *__restrict__ so, const real_t *__restrict__ qf,
-                                                            real_t *__restrict__ q, const real_t *__restrict__ sor,
-                                                            int II, int JJ, int jb, int nlines, int dbg,
-                                                            const real_t *__restrict__ pf, size_t bstride)
-{
-	extern __shared__ __attribute__((aligned(16))) real_t lds[];
-	const int npad = (II - 2) + ((II - 2) >> 3) + 1;
-	real_t *y = lds, *wa = lds + npad, *wc = wa + 16, *cs = wc + 16;
-	const unsigned L = xcd_remap(blockIdx.x, (unsigned)nlines);
-	if (L >= (unsigned)nlines) return;
-	qf += bstride * blockIdx.y; q += bstride * blockIdx.y; // batch item (common.h Batch)
-	const size_t sj = II, PS = (size_t)II * JJ;
-	const size_t row = (size_t)(1 + jb + 2 * (int)L) * sj;
-	const int n = II - 2;
-	// right-hand side (relax_lines_x.f90:106-111 / :128-129), reference term order.
-	// Lines longer than a wavefront tile: every lane forms the right-hand side of RU pairs of unknowns per pass
-	// with 16-byte loads, all 11 x RU loads of a pass requested before the first is used.  With one point per lane
-	// and pass (below) a wave waits out one HBM round trip per 64 unknowns -- 72 % of the wave cycles of this
-	// kernel were such waits (profiles/r02_lines_sq_counters.txt).
-	int tdone = 0;
-	if (dbg & 2) tdone = n; // experiment: no right-hand side (LDS left as is)
-	else if (BS >= 256) {
-		constexpr int RU = 4;
-		const int npair = n >> 1;
-		for (int pb0 = 0; pb0 < npair; pb0 += BS * RU) {
-			real_t f[RU][2], ks[RU][2], ksn[RU][2], ksw[RU][2], knwe[RU][2], knwn[RU][2], kswne[RU][2], qs[RU][4], qn[RU][4];
-#pragma unroll
-			for (int u = 0; u < RU; u++) {
-				const int pr = pb0 + u * BS + (int)threadIdx.x;
-				if (pr < npair) {
-					const size_t x = row + 1 + 2 * (size_t)pr;
-					ldpair2(qf + x, f[u]);
-					ldpair2(so + KS * PS + x, ks[u]);
-					ldpair2(so + KS * PS + x + sj, ksn[u]);
-					ldpair2(q + x - 1 - sj, &qs[u][0]); ldpair2(q + x + 1 - sj, &qs[u][2]);
-					ldpair2(q + x - 1 + sj, &qn[u][0]); ldpair2(q + x + 1 + sj, &qn[u][2]);
-					if (NINE) {
-						ldpair2(so + KSW * PS + x, ksw[u]);
-						ldpair2(so + KNW * PS + x + 1, knwe[u]);
-						ldpair2(so + KNW * PS + x + sj, knwn[u]);
-						ldpair2(so + KSW * PS + x + 1 + sj, kswne[u]);
-					}
-				}
-			}
-#pragma unroll
-			for (int u = 0; u < RU; u++) {
-				const int pr = pb0 + u * BS + (int)threadIdx.x;
-				if (pr < npair) {
-#pragma unroll
-					for (int h = 0; h < 2; h++) {
-						real_t s = f[u][h];
-						s = s + ks[u][h] * qs[u][1 + h];
-						s = s + ksn[u][h] * qn[u][1 + h];
-						if (NINE) {
-							s = s + ksw[u][h] * qs[u][h];
-							if (YT) {
-								s = s + knwn[u][h] * qn[u][h];
-								s = s + knwe[u][h] * qs[u][2 + h];
-							} else {
-								s = s + knwe[u][h] * qs[u][2 + h];
-								s = s + knwn[u][h] * qn[u][h];
-							}
-							s = s + kswne[u][h] * qn[u][2 + h];
-						}
-						y[lpad(2 * pr + h)] = s;
-					}
-				}
-			}
-		}
-		tdone = npair * 2; // an odd last unknown goes through the scalar loop
-	}
-	for (int t = tdone + threadIdx.x; t < n; t += BS) {
-		const size_t x = row + 1 + t;
-		real_t s = qf[x];
-		s = s + so[KS * PS + x] * q[x - sj];
-		s = s + so[KS * PS + x + sj] * q[x + sj];
-		if (NINE) {
-			s = s + so[KSW * PS + x] * q[x - 1 - sj];
-			if (YT) { // (i+1,j-1) is (row+1, col-1) of the transposed arrays and comes first
-				s = s + so[KNW * PS + x + sj] * q[x - 1 + sj];
-				s = s + so[KNW * PS + x + 1] * q[x + 1 - sj];
-			} else {
-				s = s + so[KNW * PS + x + 1] * q[x + 1 - sj];
-				s = s + so[KNW * PS + x + sj] * q[x - 1 + sj];
-			}
-			s = s + so[KSW * PS + x + 1 + sj] * q[x + 1 + sj];
-		}
-		y[lpad(t)] = s;
-	}
-	__syncthreads();
-	if (dbg & 1) { /* experiment: no solve */ }
-	else if (PERM) line_pttrs_pf<BS>(y, n, pf + (size_t)(jb + 2 * (int)L) * pf_line_doubles<BS>(n), wa, wc, cs);
-	else line_pttrs<BS>(y, n, sor + row + 1, sor + PS + row + 2, wa, wc, cs);
-	for (int t = threadIdx.x; t < n; t += BS) q[row + 1 + t] = y[lpad(t)];
-	if (SM) {
-		real_t y1, yn;
-		const real_t beta = line_sherman_morrison<BS>(y, n, sor + row + 1, sor + PS + row + 2, so[KW * PS + row + 1],
-		                                              so[KW * PS + row + II - 1], wa, wc, cs, y1, yn);
-		for (int t = threadIdx.x; t < n; t += BS) q[row + 1 + t] = q[row + 1 + t] - beta * y[lpad(t)]; // same lane wrote it
-	}
-}
-
-// lanes per line: one wavefront up to 512 unknowns, else CEDAR_AMD_LINE_BS (256 / 512 / 1024).  The size fixes the
-// association of the scan, so every launcher of a line solve takes it from here.
-static int line_bs(int n)
-{
-	if (n <= 512) return 64;
-	static const int e = getenv("CEDAR_AMD_LINE_BS") ? atoi(getenv("CEDAR_AMD_LINE_BS")) : 256;
-	return (e == 512 || e == 1024) ? e : 256;
-}
-
-// a line must fit the 160 KB of LDS (up to ~18,000 unknowns); longer lines are refused through the
-// host's print_error callback like every other unsupported request, the sweep is skipped
-extern "C" void print_error(char *msg);
-static bool lds_ok(int n, const char *who)
-{
-	if (line_lds_doubles(n) * sizeof(real_t) > 160 * 1024 - 512) {
-		char buf[160];
-		snprintf(buf, sizeof(buf), "%s: a line of %d unknowns does not fit the 160 KB LDS of a CU; sweep skipped", who, n);
-		print_error(buf);
-		return false;
-	}
-	return true;
-}
-
-template <int BS, bool NINE, bool SM, bool YT, bool PERM>
-static void launch_x_kp(const real_t *so, const real_t *qf, real_t *q, const real_t *sor, int II, int JJ, int jb, int nlines,
-                        hipStream_t st, const real_t *pf, Batch bt)
-{
-	size_t shm = line_lds_doubles(II - 2) * sizeof(real_t);
-	auto k = relax_lines_x_kernel<BS, NINE, SM, YT, PERM>;
-	if (shm > 64 * 1024) CEDAR_HIP_CHECK(hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
-	const char *ed = getenv("CEDAR_AMD_LINE_DBG"); // timing experiments only (1: no solve, 2: no right-hand side)
-	hipLaunchKernelGGL(k, dim3(xcd_grid(nlines), bt.n), dim3(BS), shm, st, so, qf, q, sor, II, JJ, jb, nlines, ed ? atoi(ed) : 0, pf,
-	                   bt.stride);
-}
-
-// pf != nullptr: the scan-ordered factor copy of this line direction (lines_permute), Dirichlet lines of the 256-lane kernel
-template <int BS, bool NINE, bool SM, bool YT = false>
-static void launch_x_k(const real_t *so, const real_t *qf, real_t *q, const real_t *sor, int II, int JJ, int jb, int nlines,
-                       hipStream_t st, const real_t *pf, Batch bt)
-{
-	if (!SM && pf && BS >= 256) launch_x_kp<BS, NINE, false, YT, true>(so, qf, q, sor, II, JJ, jb, nlines, st, pf, bt);
-	else launch_x_kp<BS, NINE, SM, YT, false>(so, qf, q, sor, II, JJ, jb, nlines, st, nullptr, bt);
-}
-
-template <int BS>
-static void launch_x_n(const real_t *so, const real_t *qf, real_t *q, const real_t *sor, int II, int JJ,
-                       int nstncl, int jb, hipStream_t st, bool sm, bool yt, const real_t *pf, Batch bt)
-{
-	int nlines = (JJ - 2 - jb + 1) / 2;
-	if (nlines <= 0) return;
-	if (yt) { // Dirichlet only
-		if (nstncl == 5) launch_x_k<BS, true, false, true>(so, qf, q, sor, II, JJ, jb, nlines, st, pf, bt);
-		else launch_x_k<BS, false, false, true>(so, qf, q, sor, II, JJ, jb, nlines, st, pf, bt);
-	} else if (nstncl == 5) {
-		if (sm) launch_x_k<BS, true, true>(so, qf, q, sor, II, JJ, jb, nlines, st, pf, bt);
-		else launch_x_k<BS, true, false>(so, qf, q, sor, II, JJ, jb, nlines, st, pf, bt);
-	} else {
-		if (sm) launch_x_k<BS, false, true>(so, qf, q, sor, II, JJ, jb, nlines, st, pf, bt);
-		else launch_x_k<BS, false, false>(so, qf, q, sor, II, JJ, jb, nlines, st, pf, bt);
-	}
-}
-
-static void launch_x(const real_t *so, const real_t *qf, real_t *q, const real_t *sor, int II, int JJ,
-                     int nstncl, int jb, hipStream_t st, bool sm = false, bool yt = false, const real_t *pf = nullptr,
-                     Batch bt = Batch())
-{
-	switch (line_bs(II - 2)) {
-	case 64: launch_x_n<64>(so, qf, q, sor, II, JJ, nstncl, jb, st, sm, yt, pf, bt); break;
-	case 512: launch_x_n<512>(so, qf, q, sor, II, JJ, nstncl, jb, st, sm, yt, pf, bt); break;
-	case 1024: launch_x_n<1024>(so, qf, q, sor, II, JJ, nstncl, jb, st, sm, yt, pf, bt); break;
-	default: launch_x_n<256>(so, qf, q, sor, II, JJ, nstncl, jb, st, sm, yt, pf, bt);
-	}
-}
-
 // ipn: 0 Dirichlet; 1 periodic in y only: ordinary solves, one y wrap after the sweep (relax_lines_x.f90:75-176);
 // 2 / 3 periodic in x (/ and y): cyclic lines, y then x wrap after each colour (:178-300)
 // scan-ordered factor copy for the lines of `sor` (n unknowns per line, line stride ld, nlines lines): 0 doubles when
@@ -585,15 +172,11 @@ size_t lines_permuted_doubles(int n, int nlines)
 	}
 }
 
+bool line_fits_lds_host(int n) { return line_fits_lds(n); }
+
 void lines_permute(const real_t *sor, real_t *pf, int n, int ld, int nlines, size_t PS, hipStream_t st)
 {
-	if (nlines <= 0 || n <= 0) return;
-	switch (line_bs(n)) {
-	case 256: hipLaunchKernelGGL(lines_permute_kernel<256>, dim3(nlines), dim3(256), 0, st, sor, pf, n, ld, PS); break;
-	case 512: hipLaunchKernelGGL(lines_permute_kernel<512>, dim3(nlines), dim3(512), 0, st, sor, pf, n, ld, PS); break;
-	case 1024: hipLaunchKernelGGL(lines_permute_kernel<1024>, dim3(nlines), dim3(1024), 0, st, sor, pf, n, ld, PS); break;
-	default: break;
-	}
+	lines_permute_t<real_t>(sor, pf, n, ld, nlines, PS, nullptr, st);
 }
 
 void relax_lines_x(const real_t *so, const real_t *qf, real_t *q, const real_t *sor,
@@ -605,7 +188,7 @@ void relax_lines_x(const real_t *so, const real_t *qf, real_t *q, const real_t *
 	for (int c = 0; c < 2; c++) {
 		// DOWN: lines J = 3,5,.. first (0-based rows 2,4,.. => jb = 1), then J = 2,4,..
 		int jb = (updown == BMG_DOWN) ? 1 - c : c;
-		launch_x(so, qf, q, sor, II, JJ, nstncl, jb, st, sm, false, sm ? nullptr : pf, bt);
+		launch_x(op2_cedar(so, nullptr, II, JJ), qf, q, sor, II, JJ, nstncl, jb, st, sm, false, sm ? nullptr : pf, bt);
 		if (sm) wrap2(q, II, JJ, 1, ipn == 3, 1, st);
 	}
 	if (ipn == 1) wrap2(q, II, JJ, 1, 1, 0, st);
@@ -843,7 +426,7 @@ void relax_lines_yt(const real_t *sot, const real_t *qft, real_t *q, real_t *qt,
 		const int nlines = (II - 2 - ib + 1) / 2;
 		if (nlines <= 0) continue;
 		// transposed grid: JJ is the fast extent, II the number of rows
-		launch_x(sot, qft, qt, sor, JJ, II, nstncl, ib, st, false, true, pf, bt);
+		launch_x(op2_cedar(sot, nullptr, JJ, II), qft, qt, sor, JJ, II, nstncl, ib, st, false, true, pf, bt);
 	}
 	transpose2(qt, q, JJ, II, st, bt);
 }

@@ -23,10 +23,11 @@ __global__ __launch_bounds__(256) void op2f_build_kernel(const real_t *__restric
 	bool bad = false;
 	for (int s = 0; s < ns; s++) {
 		// nine-point: KW, KS, KSW, KNW, KO, 1/diag; five-point: KW, KS, KO, 1/diag
+		// (sor == nullptr: a line-relaxed level has no 1/diag plane, its slot-row is zeros)
 		const real_t *from = s == ns - 1 ? sor : s == ns - 2 ? so + KO * PS : so + (size_t)(s + 1) * PS;
-		from += j * (size_t)II;
+		if (from) from += j * (size_t)II;
 		for (size_t o = threadIdx.x; o < RS; o += 256) {
-			const real_t v = (o >= 1 && o <= (size_t)II) ? from[o - 1] : 0.0;
+			const real_t v = (from && o >= 1 && o <= (size_t)II) ? from[o - 1] : 0.0;
 			const float f = (float)v; // v_cvt_f32_f64: round to nearest even
 			bad = bad || (isinf(f) && !isinf(v));
 			dst[(size_t)s * RS + o] = f;

@@ -54,6 +54,12 @@ struct Level {
 	// cedar_amd_solver_use_fp32_operator_2d; the level's sweeps and the cycle's residual read it, A itself stays FP64.  Its
 	// presence alone decides that: a level that keeps it runs the row kernels, never the LDS-resident small-level ones
 	float *A2f = nullptr;
+	// 2D, Dirichlet line relaxation after cedar_amd_solver_use_fp32_operator_lines (linesf.hip): A2f is
+	// the copy of A with a zero 1/diag slot-row (the x-line right-hand sides and the cycle's residual read it), At2f the
+	// same form of the transposed planes At where the level runs y lines, and the factors of each direction in use are
+	// floats in the form the FP64 kernel of that direction reads: the scan-ordered copy (PFx32 / PFy32) where the level
+	// keeps PFx / PFy, else the plain image of the two SOR planes (Fx32 / Fy32).  A, At, SOR*, PF* stay
+	float *At2f = nullptr, *Fx32 = nullptr, *Fy32 = nullptr, *PFx32 = nullptr, *PFy32 = nullptr;
 	// 3D 27-point: partial-sum scratch of the relax sweep (relax3d_psum.hip), one vector
 	real_t *T = nullptr;
 	// the set-up products (A, P, SOR, At, PF*) belong to another solver of the same operator (plane relaxation:
@@ -96,6 +102,16 @@ template <class F, class G> void with_cycle_view2(const Level &L, F &&f, G &&g)
 {
 	if (L.A2f) f(op2f_view(L.A2f, L.II, L.nst));
 	else g();
+}
+
+// The same choice for one direction of a line-relaxed 2D level, made here and nowhere else: f(operator copy, float
+// factors, their scan-ordered copy) where the level keeps the float copies -- for y lines the copy of the transposed
+// planes -- else g() on today's FP64 arrays.
+template <class F, class G> void with_line_view(const Level &L, bool ylines, F &&f, G &&g)
+{
+	if (!L.A2f) g();
+	else if (ylines) f(op2f_view(L.At2f, L.JJ, L.nst), L.Fy32, L.PFy32);
+	else f(op2f_view(L.A2f, L.II, L.nst), L.Fx32, L.PFx32);
 }
 
 // include/cedar/3d/relax_planes.h:164-246.  The reference keeps one 2D solver per plane; copy_coeff gives all of
@@ -264,7 +280,21 @@ void lines_y(const Level &L, real_t *x, const real_t *b, const real_t *sor, int 
 		transpose2(b, L.bt, L.II, L.JJ, st, bt);
 		L.bt_fresh = true;
 	}
-	relax_lines_yt(L.At, L.bt, x, L.xt, sor, L.II, L.JJ, L.nst, updown, st, L.PFy, bt);
+	with_line_view(
+	    L, true,
+	    [&](const Op2f &At, const float *f, const float *pf) {
+		    relax_lines_yt_op(At, L.bt, x, L.xt, f, L.II, L.JJ, L.nst, updown, st, pf, bt);
+	    },
+	    [&]() { relax_lines_yt(L.At, L.bt, x, L.xt, sor, L.II, L.JJ, L.nst, updown, st, L.PFy, bt); });
+}
+
+// one x-line sweep
+void lines_x(const Level &L, real_t *x, const real_t *b, int updown, int ipn, hipStream_t st, Batch bt)
+{
+	with_line_view(
+	    L, false,
+	    [&](const Op2f &A, const float *f, const float *pf) { relax_lines_x_op(A, b, x, f, L.II, L.JJ, L.nst, updown, st, pf, bt); },
+	    [&]() { relax_lines_x(L.A, b, x, L.SOR0, L.II, L.JJ, L.nst, updown, st, ipn, L.PFx, bt); });
 }
 
 double l2_dev(cedar_amd_solver *s, const Level &L, const real_t *v)
@@ -410,7 +440,7 @@ void planes_relax(cedar_amd_solver *s3, PlaneSet &ps, const Level &L, real_t *x,
 void smooth(const cedar_amd_solver *s, const Level &L, real_t *x, const real_t *b, int updown, int n, hipStream_t st)
 {
 	if (s->nd == 2 && s->st.ibc == 0 && s->st.relaxation >= CEDAR_AMD_RELAX_LINE_X && s->st.relaxation <= CEDAR_AMD_RELAX_LINE_XY
-	    && lines_small_ok(L.II, L.JJ)) {
+	    && !L.A2f && lines_small_ok(L.II, L.JJ)) {
 		// a small level: every sweep of this visit in one launch, the level resident in LDS (lines_small.hip)
 		const int kind = s->st.relaxation == CEDAR_AMD_RELAX_LINE_X ? 1 : s->st.relaxation == CEDAR_AMD_RELAX_LINE_Y ? 2 : 3;
 		relax_lines_small(L.A, b, x, L.SOR0, kind == 2 ? L.SOR0 : L.SOR1, L.II, L.JJ, L.nst, kind, updown, n, st, Batch{s->nb, L.npts});
@@ -474,15 +504,15 @@ void smooth(const cedar_amd_solver *s, const Level &L, real_t *x, const real_t *
 				    else relax2_gs(L.A, b, x, L.SOR0, L.II, L.JJ, L.nst, updown, st, bt);
 			    });
 			break;
-		case CEDAR_AMD_RELAX_LINE_X: relax_lines_x(L.A, b, x, L.SOR0, L.II, L.JJ, L.nst, updown, st, ipn, L.PFx, bt); break;
+		case CEDAR_AMD_RELAX_LINE_X: lines_x(L, x, b, updown, ipn, st, bt); break;
 		case CEDAR_AMD_RELAX_LINE_Y: lines_y(L, x, b, L.SOR0, updown, ipn, st, bt); break;
 		default:
 			if (updown == BMG_DOWN) {
-				relax_lines_x(L.A, b, x, L.SOR0, L.II, L.JJ, L.nst, updown, st, ipn, L.PFx, bt);
+				lines_x(L, x, b, updown, ipn, st, bt);
 				lines_y(L, x, b, L.SOR1, updown, ipn, st, bt);
 			} else {
 				lines_y(L, x, b, L.SOR1, updown, ipn, st, bt);
-				relax_lines_x(L.A, b, x, L.SOR0, L.II, L.JJ, L.nst, updown, st, ipn, L.PFx, bt);
+				lines_x(L, x, b, updown, ipn, st, bt);
 			}
 		}
 	}
@@ -889,6 +919,7 @@ void cedar_amd_solver_destroy(cedar_amd_solver *s)
 			(void)hipFree(L.A32);
 			(void)hipFree(L.A7f);
 			(void)hipFree(L.A2f);
+			(void)hipFree(L.At2f); (void)hipFree(L.Fx32); (void)hipFree(L.Fy32); (void)hipFree(L.PFx32); (void)hipFree(L.PFy32);
 			(void)hipFree(L.PFx); (void)hipFree(L.PFy);
 		}
 		(void)hipFree(L.res); (void)hipFree(L.yscr); (void)hipFree(L.bt); (void)hipFree(L.xt); (void)hipFree(L.T);
@@ -1141,6 +1172,129 @@ int cedar_amd_solver_use_fp32_operator_2d(cedar_amd_solver *s, int min_rows)
 	return fp32_count(s);
 }
 
+// ---- the switch for 2D handles with line relaxation (single or batch, Dirichlet, V- or F-cycle; linesf.hip)
+// the float copies of one level: what the level's fields of the same names hold
+struct Lines32 {
+	float *A2f = nullptr, *At2f = nullptr, *Fx32 = nullptr, *Fy32 = nullptr, *PFx32 = nullptr, *PFy32 = nullptr;
+	void release()
+	{
+		(void)hipFree(A2f); (void)hipFree(At2f); (void)hipFree(Fx32); (void)hipFree(Fy32); (void)hipFree(PFx32); (void)hipFree(PFy32);
+		*this = Lines32();
+	}
+};
+enum { LINES32_A = 1, LINES32_X = 2, LINES32_Y = 4 };
+
+static bool lines_x_used(const cedar_amd_solver *s) { return s->st.relaxation == CEDAR_AMD_RELAX_LINE_X || s->st.relaxation == CEDAR_AMD_RELAX_LINE_XY; }
+static bool lines_y_used(const cedar_amd_solver *s) { return s->st.relaxation == CEDAR_AMD_RELAX_LINE_Y || s->st.relaxation == CEDAR_AMD_RELAX_LINE_XY; }
+// the y factors SOR(JJ,II,2): SOR0 of a line-y handle, SOR1 of a line-xy one
+static const real_t *lines_y_sor(const cedar_amd_solver *s, const Level &L) { return s->st.relaxation == CEDAR_AMD_RELAX_LINE_Y ? L.SOR0 : L.SOR1; }
+
+// allocate the copies a level needs; false = out of device memory (nothing kept)
+static bool lines32_alloc(const cedar_amd_solver *s, const Level &L, Lines32 &c)
+{
+	auto get = [&](float *&p, size_t nfl) {
+		if (hipMalloc((void **)&p, (nfl ? nfl : 1) * sizeof(float)) == hipSuccess) return true;
+		(void)hipGetLastError();
+		p = nullptr;
+		return false;
+	};
+	bool ok = get(c.A2f, op2f_floats(L.II, L.JJ, L.nst));
+	if (ok && lines_y_used(s)) ok = get(c.At2f, op2f_floats(L.JJ, L.II, L.nst));
+	if (ok && lines_x_used(s))
+		ok = L.PFx ? get(c.PFx32, lines_permuted_doubles(L.nx, L.ny)) : get(c.Fx32, L.npts * 2);
+	if (ok && lines_y_used(s))
+		ok = L.PFy ? get(c.PFy32, lines_permuted_doubles(L.ny, L.nx)) : get(c.Fy32, L.npts * 2);
+	if (!ok) c.release();
+	return ok;
+}
+
+// (re)build the copies named by `what` (LINES32_*) from the level's FP64 arrays, all values rounded to nearest even; true =
+// an entry of A or of a factor does not fit float
+static bool lines32_build(cedar_amd_solver *s, const Level &L, const Lines32 &c, int what, hipStream_t st)
+{
+	int *flag = s->dinfo + 1, host = 0; // (dinfo[0]: the coarse factorisation's info)
+	CEDAR_HIP_CHECK(hipMemsetAsync(flag, 0, sizeof(int), st));
+	if (what & LINES32_A) {
+		op2f_build(L.A, nullptr, c.A2f, L.II, L.JJ, L.nst, flag, st);
+		if (c.At2f) op2f_build(L.At, nullptr, c.At2f, L.JJ, L.II, L.nst, flag, st); // the transposed grid is JJ fast
+	}
+	if (what & LINES32_X) {
+		if (c.PFx32) linesf_permute(L.SOR0, c.PFx32, L.nx, L.II, L.ny, L.npts, flag, st);
+		if (c.Fx32) linesf_image(L.SOR0, c.Fx32, L.II, L.JJ, flag, st);
+	}
+	if (what & LINES32_Y) {
+		if (c.PFy32) linesf_permute(lines_y_sor(s, L), c.PFy32, L.ny, L.JJ, L.nx, L.npts, flag, st);
+		if (c.Fy32) linesf_image(lines_y_sor(s, L), c.Fy32, L.II, L.JJ, flag, st);
+	}
+	CEDAR_HIP_CHECK(hipMemcpyAsync(&host, flag, sizeof(int), hipMemcpyDeviceToHost, st));
+	CEDAR_HIP_CHECK(hipStreamSynchronize(st));
+	return host != 0;
+}
+
+static Lines32 lines32_of(const Level &L) { return Lines32{L.A2f, L.At2f, L.Fx32, L.Fy32, L.PFx32, L.PFy32}; }
+static void lines32_put(Level &L, const Lines32 &c)
+{
+	L.A2f = c.A2f; L.At2f = c.At2f; L.Fx32 = c.Fx32; L.Fy32 = c.Fy32; L.PFx32 = c.PFx32; L.PFy32 = c.PFy32;
+}
+
+// min_rows = 0, the default: levels of at least 1024 rows.  Measured (tools/op32_lines_time.py, profiles/op32_lines_time.json;
+// DESIGN.md section 17) on the nine-point varcoef9 and the five-point gallery::poisson under line-xy: with level 0 alone
+// switched the V(1,1) / V(2,1) cycle runs in 0.86 / 0.85 and 0.93 / 0.90 of its FP64 time at 8192^2, 0.85 / 0.85 and
+// 0.91 / 0.89 at 4096^2, 0.91 / 0.91 and 0.96 / 0.95 at 2048^2, 0.93 / 0.92 and 0.94 / 0.96 at 1024^2, each gain many times
+// the spread of the repetitions; at 512^2 it is 1.00 / 1.00 and 1.01 / 1.00, and adding a level of 512 rows to a larger
+// handle's set gains nothing (2048^2: 0.882 -> 0.883) or loses (1024^2 V(2,1): 0.924 -> 0.942).  So levels of 512 rows and
+// fewer stay FP64 unless min_rows > 0 asks.
+enum { OP32_LINES_DEFAULT_MIN_ROWS = 1024 };
+
+int cedar_amd_solver_use_fp32_operator_lines(cedar_amd_solver *s, int min_rows)
+{
+	const char *who = "cedar_amd_solver_use_fp32_operator_lines";
+	if (null_handle(s, who)) return -1;
+	auto refuse = [&](const char *reason) {
+		char msg[256];
+		snprintf(msg, sizeof(msg), "%s: %s; the handle is unchanged", who, reason);
+		print_error(msg);
+		return -1;
+	};
+	if (s->nd != 2) return refuse("3D handles are not supported (use cedar_amd_solver_use_fp32_operator_all)");
+	if (s->st.relaxation == CEDAR_AMD_RELAX_POINT) return refuse("point relaxation is not supported (use cedar_amd_solver_use_fp32_operator_2d)");
+	if (s->st.ibc != 0) return refuse("periodic boundary conditions (ibc != 0) are not supported");
+	if (lines_y_used(s) && !s->lv[0].At)
+		return refuse("y lines that do not keep transposed arrays (CEDAR_AMD_YLINES_TRANSPOSED=0) are not supported");
+	if (min_rows < 0) return refuse("min_rows must not be negative");
+	if (min_rows == 0) {
+		const char *e = getenv("CEDAR_AMD_OP32_MIN_ROWS"); // read per call, like CEDAR_AMD_PSUM
+		min_rows = e && atoi(e) > 0 ? atoi(e) : (int)OP32_LINES_DEFAULT_MIN_ROWS;
+	}
+	// every smoothed level with at least min_rows rows that the LDS-resident small-level kernels do not serve; all copies
+	// are built and checked before the handle changes
+	hipStream_t st = current_stream();
+	std::vector<std::pair<int, Lines32>> fresh;
+	auto undo = [&]() {
+		for (auto &f : fresh) f.second.release();
+	};
+	for (int l = 0; min_rows > 0 && l + 1 < (int)s->lv.size(); l++) {
+		const Level &L = s->lv[l];
+		if (L.A2f || L.ny < min_rows || lines_small_ok(L.II, L.JJ)) continue;
+		Lines32 c;
+		if (!lines32_alloc(s, L, c)) {
+			undo();
+			return refuse("out of device memory for the single-precision copies");
+		}
+		fresh.emplace_back(l, c);
+		if (lines32_build(s, L, c, LINES32_A | LINES32_X | LINES32_Y, st)) {
+			undo();
+			return refuse("an entry of the operator or of a line factor overflows single precision");
+		}
+	}
+	if (!fresh.empty()) {
+		graphs_drop(s);
+		for (auto &f : fresh) lines32_put(s->lv[f.first], f.second);
+	}
+	launch_check(who);
+	return fp32_count(s);
+}
+
 // levels[lvl].A / .P / .SOR / ABD are public members of the reference's solver (include/cedar/level.h:14-41,
 // include/cedar/2d/solver.h:56): a caller may replace a set-up product.  Solver-internal copies that derive from the
 // array (row-interleaved solve copy, transposed y-line planes, scan-ordered line factors) are rebuilt.
@@ -1162,8 +1316,9 @@ size_t cedar_amd_solver_set(cedar_amd_solver *s, int lvl, const char *what, cons
 	else cedar_amd_memcpy_h2d(dst, in, n * sizeof(real_t));
 	if (L.Ailv && (!strcmp(what, "A") || !strcmp(what, "SOR0")))
 		ilv_build(L.A, L.SOR0 + L.npts, L.Ailv, L.II, L.JJ, L.KK, st);
+	const bool lines32 = s->nd == 2 && L.A2f && s->st.relaxation != CEDAR_AMD_RELAX_POINT; // rebuilt below, after At
 	float *&c32 = s->nd == 2 ? L.A2f : L.nst == 14 ? L.A32 : L.A7f; // the level's float copy, of any kind
-	if (c32 && (!strcmp(what, "A") || !strcmp(what, "SOR0")) && op32_build(s, L, c32, st)) {
+	if (!lines32 && c32 && (!strcmp(what, "A") || !strcmp(what, "SOR0")) && op32_build(s, L, c32, st)) {
 		// the new entries do not fit float: the level goes back to the FP64 planes (the captured cycle names the copy)
 		char msg[] = "cedar_amd_solver_set: an entry of the new array overflows single precision; the level reads the FP64 "
 		             "operator again";
@@ -1176,6 +1331,21 @@ size_t cedar_amd_solver_set(cedar_amd_solver *s, int lvl, const char *what, cons
 	if (L.PFx && !strcmp(what, "SOR0")) lines_permute(L.SOR0, L.PFx, L.nx, L.II, L.ny, L.npts, st);
 	if (L.PFy && !strcmp(what, s->st.relaxation == CEDAR_AMD_RELAX_LINE_Y ? "SOR0" : "SOR1"))
 		lines_permute(s->st.relaxation == CEDAR_AMD_RELAX_LINE_Y ? L.SOR0 : L.SOR1, L.PFy, L.ny, L.JJ, L.nx, L.npts, st);
+	if (lines32) {
+		// a line level's float copies: "A" feeds both operator copies, "SOR0" / "SOR1" the factor copies of their direction
+		const bool yfac = lines_y_used(s) && !strcmp(what, s->st.relaxation == CEDAR_AMD_RELAX_LINE_Y ? "SOR0" : "SOR1");
+		const int which = (!strcmp(what, "A") ? LINES32_A : 0) | (lines_x_used(s) && !strcmp(what, "SOR0") ? LINES32_X : 0)
+		                  | (yfac ? LINES32_Y : 0);
+		if (which && lines32_build(s, L, lines32_of(L), which, st)) {
+			char msg[] = "cedar_amd_solver_set: an entry of the new array overflows single precision; the level reads the FP64 "
+			             "operator and factors again";
+			print_error(msg);
+			graphs_drop(s);
+			Lines32 c = lines32_of(L);
+			c.release();
+			lines32_put(L, c);
+		}
+	}
 	CEDAR_HIP_CHECK(hipStreamSynchronize(st));
 	launch_check("cedar_amd_solver_set");
 	return n;

@@ -285,6 +285,17 @@ public:
 		}
 		return cedar_amd_solver_use_fp32_operator_2d(h, min_rows);
 	}
+	// the switch for a 2D solver with line relaxation, one or several right-hand sides, Dirichlet
+	// (cedar_amd_solver_use_fp32_operator_lines): min_rows > 0 takes every smoothed level with at least that many rows
+	// that the small-level kernels do not serve; min_rows = 0: the measured default
+	int use_fp32_operator_lines(int min_rows = 0)
+	{
+		if (!h) {
+			log::error << "use_fp32_operator_lines: needs the device-resident solver (every kernel \"hip\")" << std::endl;
+			return -1;
+		}
+		return cedar_amd_solver_use_fp32_operator_lines(h, min_rows);
+	}
 	int fp32_levels() const { return h ? cedar_amd_solver_fp32_levels(h) : 0; }
 
 	void vcycle(grid_func & x, const grid_func & b)

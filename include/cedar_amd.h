@@ -229,6 +229,21 @@ int cedar_amd_residual2_op32(real_t *so, real_t *qf, real_t *q, real_t *res, len
 int cedar_amd_relax2_gs_many_op32(int nrhs, real_t *so, real_t *qf, real_t *q, real_t *sor, len_t ii, len_t jj, int nstncl,
                                   int updown);
 int cedar_amd_residual2_many_op32(int nrhs, real_t *so, real_t *qf, real_t *q, real_t *res, len_t ii, len_t jj, int nstncl);
+/* One zebra line sweep (both colours) on the operator and the line factors rounded to single precision (so: nstncl = 5 | 3
+ * planes; what a 2D level runs after cedar_amd_solver_use_fp32_operator_lines): the row-interleaved float copy of the
+ * operator and float copies of the factors are built for the call and dropped after it; entries and factors are promoted to
+ * double on load, vectors, the scan and all arithmetic stay FP64 -- bit for bit BMG2_SymStd_relax_lines_x / _y (Dirichlet)
+ * on so and sor rounded to float.
+ *   dir 0: x lines, sor as BMG2_SymStd_SETUP_lines_x leaves it;
+ *   dir 1: y lines, sor the transposed SOR(JJ,II,2) of BMG2_SymStd_SETUP_lines_y; runs on transposed arrays, as the
+ *          resident solver does.
+ * _many: nrhs (1 .. 32) items stored back to back, operator and factors shared; item m has the bits of the single call on
+ * item m alone.  Returns 0; a NULL array, nrhs outside 1 .. 32, nstncl other than 3 / 5, an entry or factor that
+ * overflows float, or a line that does not fit the LDS of a CU: print_error, -1, q untouched. */
+int cedar_amd_relax2_lines_op32(real_t *so, real_t *qf, real_t *q, real_t *sor, len_t ii, len_t jj, int nstncl, int dir,
+                                int updown);
+int cedar_amd_relax2_lines_many_op32(int nrhs, real_t *so, real_t *qf, real_t *q, real_t *sor, len_t ii, len_t jj, int nstncl,
+                                     int dir, int updown);
 /* recompute column icol (0-based incl. ghost) of that row class after its x-neighbour column changed */
 void cedar_amd_relax3_fixup(real_t *so, real_t *qf, real_t *q, real_t *sor, len_t ii, len_t jj, len_t kk,
                             int icol, int jb, int kb);
@@ -539,6 +554,39 @@ int cedar_amd_solver_use_fp32_operator_all(cedar_amd_solver *s, int min_rows);
  * cedar_amd_solver_set "A" / "SOR0" on a switched level rebuild its copy (overflow: reported, the level reads FP64 again).
  * The three calls above keep refusing 2D handles. */
 int cedar_amd_solver_use_fp32_operator_2d(cedar_amd_solver *s, int min_rows);
+/* The switch for a 2D handle with line relaxation (line-x, line-y or line-xy), single or of cedar_amd_solver_create_many:
+ * Dirichlet (ibc == 0), V- or F-cycle.  A smoothed level (all but the coarsest) that the call takes keeps, beside its
+ * FP64 arrays:
+ *   - a row-interleaved float copy of its operator (KW, KS, [KSW, KNW,] KO and a slot-row of zeros where a point-relaxed
+ *     level keeps 1/diag), which the x-line right-hand sides and the cycle's residual read;
+ *   - where it runs y lines, the same form of the transposed operator planes;
+ *   - its line factors as floats in the form the FP64 kernel of that direction reads: the scan-ordered copy where the
+ *     level keeps one (lines of more than 512 unknowns), else the plain image of the two SOR planes.
+ * All values are the FP64 ones rounded to nearest even; the factors are those of the unrounded operator.  Every sweep has
+ * the bits of the FP64 line kernel on the rounded operator and factors.  The reported residual, the Krylov passes,
+ * interpolation's diagonal, restriction and the coarsest solve keep reading the FP64 operator.  Levels that the
+ * LDS-resident small-level kernels serve (at most 64 x 64 unknowns) always stay FP64 and are never counted.
+ *   min_rows > 0: every smoothed level with at least min_rows rows that is not such a small level.
+ *   min_rows 0  : the measured default, levels of at least 1024 rows (CEDAR_AMD_OP32_MIN_ROWS overrides it, read at the
+ *                 call).  DESIGN.md section 17, profiles/op32_lines_time.json: with level 0 switched the line-xy V-cycle
+ *                 runs in 0.85 .. 0.93 of its FP64 time at 8192^2 (V(2,1) nine-point, the benchmark's third configuration:
+ *                 15.6 -> 13.3 ms) and 4096^2, 0.91 .. 0.96 at 2048^2, 0.92 .. 0.96 at 1024^2 (nine- and five-point,
+ *                 V(1,1) and V(2,1)); a level-0 x sweep alone in 0.69 .. 0.85, where the byte model says 0.65 (nine-point)
+ *                 and 0.78 (five-point).  At 512^2 the two are equal within 1 %, so smaller levels stay FP64 unless
+ *                 min_rows > 0 asks for them.
+ * The copies take about 72 bytes per unknown of a nine-point line-xy level (5 GB at 8192^2).
+ * Copies are built and checked before the handle changes, captured graphs are dropped, the call may be repeated and never
+ * switches a level back; returns cedar_amd_solver_fp32_levels.  Refused -- print_error, -1, handle unchanged -- for a NULL
+ * handle, a 3D handle, point relaxation (use cedar_amd_solver_use_fp32_operator_2d), ibc != 0, y lines that do not keep
+ * transposed arrays (CEDAR_AMD_YLINES_TRANSPOSED=0), a negative min_rows, an entry of A or of a factor that overflows
+ * float, and out of device memory.  The other calls behave as on a handle switched by the _2d call: _vcycle /
+ * _vcycle_many run the cycle that reads the rounded arrays, _pcg / _fcg / _pcg_many / _fcg_many / _precondition
+ * precondition with that cycle and run their recurrence on the FP64 operator, _solve / _solve_many go to
+ * defect-correction form, an F-cycle handle's _solve starts each cycle from x = 0 and reports the FP64 residual.
+ * cedar_amd_solver_set on a switched level: "A" rebuilds both operator copies, "SOR0" / "SOR1" the factor copies they
+ * feed (overflow: reported, the level drops its float copies and reads FP64 again).  The four calls above are unchanged
+ * and keep refusing what they refuse. */
+int cedar_amd_solver_use_fp32_operator_lines(cedar_amd_solver *s, int min_rows);
 
 /* Several right-hand sides at once on one resident hierarchy.  The operator, 1/diag and the interpolation weights are
  * the same for every right-hand side, so the batched 3D kernels (many3d.hip) fetch them once per workgroup task and apply
