@@ -424,6 +424,43 @@ class Kernels:
                    lib.cedar_amd_interp_add3_many(n if nrhs is None else nrhs, _p(q), _p(qc), _p(so), _p(res), _p(ci), u(IIC), u(JJC), u(KKC),
                                                   u(II), u(JJ), u(KK), so.shape[0]))
 
+    # ---- the transfers on the interpolation weights rounded to single precision (transferf.hip): a float copy of ci is built
+    # for the call; arguments as the FP64 methods above (Dirichlet).  0 when served, non-zero when refused (nothing written)
+    def restrict2_ci32(self, q, qc, ci):
+        JJ, II = q.shape
+        JJC, IIC = qc.shape
+        return lib.cedar_amd_restrict2_ci32(_p(q), _p(qc), _p(ci), II, JJ, IIC, JJC)
+
+    def interp_add2_ci32(self, q, qc, res, so, ci):
+        JJ, II = q.shape
+        JJC, IIC = qc.shape
+        return lib.cedar_amd_interp_add2_ci32(_p(q), _p(qc), _p(res), _p(so), _p(ci), u(IIC), u(JJC), u(II), u(JJ), so.shape[0])
+
+    def restrict3_ci32(self, q, qc, ci):
+        KK, JJ, II = q.shape
+        KKC, JJC, IIC = qc.shape
+        return lib.cedar_amd_restrict3_ci32(_p(q), _p(qc), _p(ci), u(II), u(JJ), u(KK), u(IIC), u(JJC), u(KKC))
+
+    def interp_add3_ci32(self, q, qc, so, res, ci):
+        KK, JJ, II = q.shape
+        KKC, JJC, IIC = qc.shape
+        return lib.cedar_amd_interp_add3_ci32(_p(q), _p(qc), _p(so), _p(res), _p(ci), u(IIC), u(JJC), u(KKC), u(II), u(JJ), u(KK),
+                                              so.shape[0])
+
+    def restrict3_many_ci32(self, q, qc, ci, nrhs=None):
+        n, KK, JJ, II = q.shape
+        nc, KKC, JJC, IIC = qc.shape
+        assert n == nc
+        return lib.cedar_amd_restrict3_many_ci32(n if nrhs is None else nrhs, _p(q), _p(qc), _p(ci), u(II), u(JJ), u(KK), u(IIC),
+                                                 u(JJC), u(KKC))
+
+    def interp_add3_many_ci32(self, q, qc, so, res, ci, nrhs=None):
+        n, KK, JJ, II = q.shape
+        nc, KKC, JJC, IIC = qc.shape
+        assert n == nc and res.shape == q.shape
+        return lib.cedar_amd_interp_add3_many_ci32(n if nrhs is None else nrhs, _p(q), _p(qc), _p(so), _p(res), _p(ci), u(IIC),
+                                                   u(JJC), u(KKC), u(II), u(JJ), u(KK), so.shape[0])
+
     # ---- the passes of a CG iteration (krylov.hip), one launcher each; sc: the PCG_NSC scalar block, in and out
     @staticmethod
     def _dims(a):
@@ -596,6 +633,13 @@ lib.cedar_amd_solver_use_fp32_operator_lines.restype = C.c_int
 lib.cedar_amd_solver_use_fp32_operator_lines.argtypes = [C.c_void_p, C.c_int]
 lib.cedar_amd_solver_fp32_levels.restype = C.c_int
 lib.cedar_amd_solver_fp32_levels.argtypes = [C.c_void_p]
+lib.cedar_amd_solver_use_fp32_interpolation.restype = C.c_int
+lib.cedar_amd_solver_use_fp32_interpolation.argtypes = [C.c_void_p, C.c_int]
+lib.cedar_amd_solver_fp32_interp_levels.restype = C.c_int
+lib.cedar_amd_solver_fp32_interp_levels.argtypes = [C.c_void_p]
+for _f in (lib.cedar_amd_restrict2_ci32, lib.cedar_amd_interp_add2_ci32, lib.cedar_amd_restrict3_ci32, lib.cedar_amd_interp_add3_ci32,
+           lib.cedar_amd_restrict3_many_ci32, lib.cedar_amd_interp_add3_many_ci32):
+    _f.restype = C.c_int
 
 
 class Solver:
@@ -771,6 +815,17 @@ class Solver:
 
     def fp32_levels(self):
         return lib.cedar_amd_solver_fp32_levels(self.h)
+
+    def use_fp32_interpolation(self, min_rows=0):
+        """keep the interpolation weights that the cycle's restriction and interpolation-and-add read in single precision
+        (cedar_amd_solver_use_fp32_interpolation): every level pair whose fine level has at least min_rows rows (0: the
+        default, 128 rows in 3D, 1024 in 2D) and is not served by the small-level kernels.  Independent of the
+        use_fp32_operator* switches.  Returns the number of level pairs that read a float copy, -1 if refused (the reason
+        is printed, the handle is unchanged)"""
+        return lib.cedar_amd_solver_use_fp32_interpolation(self.h, int(min_rows))
+
+    def fp32_interp_levels(self):
+        return lib.cedar_amd_solver_fp32_interp_levels(self.h)
 
     def time_vcycles(self, x, b, n):
         return lib.cedar_amd_solver_time_vcycles(self.h, x.ptr, b.ptr, n)

@@ -157,6 +157,44 @@ static bool with_op32_copy(const real_t *so, const real_t *sor_msor, int II, int
 	return !host;
 }
 
+// run f(weights view, stream) on a temporary float copy (common.h Ci3f) of the weights ci: built for the call, back in the
+// pool once the stream has drained.  false = refused (reported), f not run
+template <class F>
+static bool with_ci32_copy(const real_t *ci, int IIC, int JJC, int KKC, int nslots, const char *who, F &&f)
+{
+	hipStream_t st = current_stream();
+	const size_t bytes = ci32_floats(IIC, JJC, KKC, nslots) * sizeof(float);
+	float *c = static_cast<float *>(pool_get(bytes));
+	int *flag = static_cast<int *>(pool_get(sizeof(int))), host = 0;
+	CEDAR_HIP_CHECK(hipMemsetAsync(flag, 0, sizeof(int), st));
+	ci32_build(ci, c, IIC, JJC, KKC, nslots, flag, st);
+	CEDAR_HIP_CHECK(hipMemcpyAsync(&host, flag, sizeof(int), hipMemcpyDeviceToHost, st));
+	CEDAR_HIP_CHECK(hipStreamSynchronize(st));
+	pool_put(flag, sizeof(int));
+	if (host) {
+		char buf[200];
+		snprintf(buf, sizeof(buf), "%s: an interpolation weight overflows single precision; nothing done", who);
+		report(buf);
+	} else {
+		f(ci32_view(c, IIC, JJC, KKC), st);
+		CEDAR_HIP_CHECK(hipStreamSynchronize(st));
+	}
+	pool_put(c, bytes);
+	return !host;
+}
+
+// extents (ghosts included) and arrays a _ci32 entry point serves; nst_ok: the stencil code where the call takes one
+static bool ci32_args_refused(bool arrays_ok, bool extents_ok, bool nst_ok, const char *who)
+{
+	const char *why = !arrays_ok ? "a required array is NULL" : !extents_ok ? "every extent (ghosts included) must be at least 3"
+	                  : !nst_ok ? "nstncl is not a stencil code of this dimension" : nullptr;
+	if (!why) return false;
+	char msg[200];
+	snprintf(msg, sizeof(msg), "%s: %s; nothing done", who, why);
+	print_error(msg);
+	return true;
+}
+
 // the same for a 7-point operator (common.h Op7f, op7f.hip): rows of any length
 template <class F>
 static bool with_op7f_copy(const real_t *so, const real_t *sor_msor, int II, int JJ, int KK, const char *who, F &&f)
@@ -1175,6 +1213,73 @@ int cedar_amd_interp_add3_many(int nrhs, real_t *q, real_t *qc, real_t *so, real
 	interp_add3_many(sq.get(), sqc.get(), sso.get(), sr.get(), sci.get(), (int)iic, (int)jjc, (int)kkc, (int)iif, (int)jjf,
 	                 (int)kkf, current_stream(), Batch{nrhs, P}, Batch{nrhs, PC});
 	return 0;
+}
+
+// ------------------------------------------------------------------ transfers on single-precision weights
+int cedar_amd_restrict2_ci32(real_t *q, real_t *qc, real_t *ci, int ii, int jj, int iic, int jjc)
+{
+	const char *who = "cedar_amd_restrict2_ci32";
+	if (ci32_args_refused(q && qc && ci, ii >= 3 && jj >= 3 && iic >= 3 && jjc >= 3, true, who)) return -1;
+	const size_t P = (size_t)ii * jj, PC = (size_t)iic * jjc;
+	Staged sq(q, P, true, false), sqc(qc, PC, true, true), sci(ci, PC * 8, true, false);
+	return with_ci32_copy(sci.get(), iic, jjc, 1, 8, who, [&](const Ci2f &W, hipStream_t st) {
+		restrict2_ci(W, sq.get(), sqc.get(), ii, jj, iic, jjc, st);
+	}) ? 0 : -1;
+}
+
+int cedar_amd_interp_add2_ci32(real_t *q, real_t *qc, real_t *res, real_t *so, real_t *ci, len_t iic, len_t jjc, len_t ii,
+                               len_t jj, int nstncl)
+{
+	const char *who = "cedar_amd_interp_add2_ci32";
+	if (ci32_args_refused(q && qc && res && so && ci, ii >= 3 && jj >= 3 && iic >= 3 && jjc >= 3, nstncl == 3 || nstncl == 5, who))
+		return -1;
+	const size_t P = (size_t)ii * jj, PC = (size_t)iic * jjc;
+	Staged sq(q, P, true, true), sqc(qc, PC, true, false), sr(res, P, true, true), sso(so, P * nstncl, true, false),
+	    sci(ci, PC * 8, true, false);
+	return with_ci32_copy(sci.get(), (int)iic, (int)jjc, 1, 8, who, [&](const Ci2f &W, hipStream_t st) {
+		interp_add2_ci(W, sq.get(), sqc.get(), sr.get(), sso.get(), (int)iic, (int)jjc, (int)ii, (int)jj, st);
+	}) ? 0 : -1;
+}
+
+int cedar_amd_restrict3_many_ci32(int nrhs, real_t *q, real_t *qc, real_t *ci, len_t ii, len_t jj, len_t kk, len_t iic, len_t jjc,
+                                  len_t kkc)
+{
+	const char *who = "cedar_amd_restrict3_many_ci32";
+	if (many_args_refused(nrhs, q && qc && ci, true, who)) return -1;
+	if (ci32_args_refused(true, ii >= 3 && jj >= 3 && kk >= 3 && iic >= 3 && jjc >= 3 && kkc >= 3, true, who)) return -1;
+	const size_t P = (size_t)ii * jj * kk, PC = (size_t)iic * jjc * kkc;
+	Staged sq(q, P * nrhs, true, false), sqc(qc, PC * nrhs, true, true), sci(ci, PC * 26, true, false);
+	return with_ci32_copy(sci.get(), (int)iic, (int)jjc, (int)kkc, 26, who, [&](const Ci3f &W, hipStream_t st) {
+		restrict3_ci(W, sq.get(), sqc.get(), (int)ii, (int)jj, (int)kk, (int)iic, (int)jjc, (int)kkc, st, Batch{nrhs, P},
+		             Batch{nrhs, PC});
+	}) ? 0 : -1;
+}
+
+int cedar_amd_interp_add3_many_ci32(int nrhs, real_t *q, real_t *qc, real_t *so, real_t *res, real_t *ci, len_t iic, len_t jjc,
+                                    len_t kkc, len_t iif, len_t jjf, len_t kkf, int nstncl)
+{
+	const char *who = "cedar_amd_interp_add3_many_ci32";
+	if (many_args_refused(nrhs, q && qc && so && res && ci, nstncl == 4 || nstncl == 14, who)) return -1;
+	if (ci32_args_refused(true, iif >= 3 && jjf >= 3 && kkf >= 3 && iic >= 3 && jjc >= 3 && kkc >= 3, true, who)) return -1;
+	const size_t P = (size_t)iif * jjf * kkf, PC = (size_t)iic * jjc * kkc;
+	Staged sq(q, P * nrhs, true, true), sqc(qc, PC * nrhs, true, false), sso(so, P * nstncl, true, false),
+	    sr(res, P * nrhs, true, true), sci(ci, PC * 26, true, false);
+	return with_ci32_copy(sci.get(), (int)iic, (int)jjc, (int)kkc, 26, who, [&](const Ci3f &W, hipStream_t st) {
+		interp_add3_ci(W, sq.get(), sqc.get(), sso.get(), sr.get(), (int)iic, (int)jjc, (int)kkc, (int)iif, (int)jjf, (int)kkf, st,
+		               Batch{nrhs, P}, Batch{nrhs, PC});
+	}) ? 0 : -1;
+}
+
+// the single-vector pair: one item of the batched entry points (nrhs = 1 runs the single-vector kernels)
+int cedar_amd_restrict3_ci32(real_t *q, real_t *qc, real_t *ci, len_t ii, len_t jj, len_t kk, len_t iic, len_t jjc, len_t kkc)
+{
+	return cedar_amd_restrict3_many_ci32(1, q, qc, ci, ii, jj, kk, iic, jjc, kkc);
+}
+
+int cedar_amd_interp_add3_ci32(real_t *q, real_t *qc, real_t *so, real_t *res, real_t *ci, len_t iic, len_t jjc, len_t kkc,
+                               len_t ii, len_t jj, len_t kk, int nstncl)
+{
+	return cedar_amd_interp_add3_many_ci32(1, q, qc, so, res, ci, iic, jjc, kkc, ii, jj, kk, nstncl);
 }
 
 // ------------------------------------------------------------------ 3D drop-ins

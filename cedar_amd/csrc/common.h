@@ -200,6 +200,48 @@ void relax_lines_yt_op(const Op2f &At, const real_t *qft, real_t *q, real_t *qt,
                        int updown, hipStream_t st, const float *pff = nullptr, Batch bt = Batch());
 bool line_fits_lds_host(int n); // lines.hip: a line of n unknowns fits the LDS of a CU
 
+// View of a level's interpolation weights for the transfer kernels (transfer_dev.h): entry (slot, ic, jc, kc) =
+// p[slot*ss + kc*sk + jc*sj + ic], coarse indices 0-based with the ghosts; 2D: kc = 0.
+//   Cedar layout (the boundary), T = real_t: sj = IIC, sk = IIC*JJC, ss = IIC*JJC*KKC.
+//   single-precision copy (cedar_amd_solver_use_fp32_interpolation; transferf.hip), T = float: the
+//   slots stay in planes, every coarse row padded to RS floats (a multiple of 32 => every row of every slot starts on a
+//   128-byte line).  Element ic of a row sits at offset ic + 1: the restrictions give a lane the coarse columns (ic, ic+1)
+//   with ic odd, so the one float of lead puts its pairs on 8-byte boundaries; RS >= IIC + 3, so the element ic + 2 a lane
+//   reads beside its last pair stays in the row.  p points at element 0 of the first row.
+template <class T> struct CiW {
+	const T *p;
+	size_t sj, sk, ss;
+};
+typedef CiW<real_t> Ci3d; // 2D and 3D alike
+typedef CiW<float> Ci3f;
+typedef Ci3f Ci2f;
+static inline Ci3d ci_cedar(const real_t *ci, int IIC, int JJC, int KKC = 1)
+{
+	const size_t sk = (size_t)IIC * JJC;
+	return Ci3d{ci, (size_t)IIC, sk, sk * (size_t)KKC};
+}
+static inline size_t ci32_row_stride(int IIC) { return ilv32_row_stride(IIC + 3); }
+static inline size_t ci32_floats(int IIC, int JJC, int KKC, int nslots) { return ci32_row_stride(IIC) * (size_t)JJC * KKC * nslots; }
+static inline Ci3f ci32_view(const float *a, int IIC, int JJC, int KKC = 1)
+{
+	const size_t RS = ci32_row_stride(IIC);
+	return Ci3f{a + 1, RS, RS * (size_t)JJC, RS * (size_t)JJC * KKC};
+}
+// build it from the Cedar-layout weights (nslots 26 | 8; round to nearest even; lead and tail of every row zero); *overflow
+// as for ilv32_build
+void ci32_build(const real_t *ci, float *out, int IIC, int JJC, int KKC, int nslots, int *overflow, hipStream_t st);
+// The transfers on that view (transferf.hip), bit for bit restrict2 / interp_add2 / restrict3 / interp_add3 and the _many
+// pair on the rounded weights (the device bodies are the same code: transfer_dev.h).  The 3D pair takes a batch: bf.n = 1
+// is the single-vector kernel's work.
+void restrict2_ci(const Ci2f &W, const real_t *q, real_t *qc, int II, int JJ, int IIC, int JJC, hipStream_t st,
+                  Batch bf = Batch(), Batch bc = Batch());
+void interp_add2_ci(const Ci2f &W, real_t *q, const real_t *qc, real_t *res, const real_t *so, int IIC, int JJC, int IIF, int JJF,
+                    hipStream_t st, Batch bf = Batch(), Batch bc = Batch());
+void restrict3_ci(const Ci3f &W, const real_t *q, real_t *qc, int II, int JJ, int KK, int IIC, int JJC, int KKC, hipStream_t st,
+                  Batch bf = Batch(), Batch bc = Batch());
+void interp_add3_ci(const Ci3f &W, real_t *q, const real_t *qc, const real_t *so, real_t *res, int IIC, int JJC, int KKC,
+                    int IIF, int JJF, int KKF, hipStream_t st, Batch bf = Batch(), Batch bc = Batch());
+
 // ---- kernel launchers (device pointers, asynchronous on `st`) ----
 // relax3d.hip
 void setup_recip(const real_t *so_diag, real_t *sor_msor, size_t II, size_t JJ, size_t KK, hipStream_t st);

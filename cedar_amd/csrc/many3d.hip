@@ -10,6 +10,7 @@
 // the items it would buy little).
 #include "common.h"
 #include "relax27_dev.h"
+#include "transfer_dev.h"
 #include <type_traits>
 
 namespace cedar_amd {
@@ -288,241 +289,27 @@ void residual7_many(const real_t *so, const real_t *qf, const real_t *q, real_t 
 	hipLaunchKernelGGL(residual7_many_kernel, dim3(xcd_grid(nrows)), dim3(bs), 0, st, so, qf, q, res, II, JJ, KK, nrows, bt.n, bt.stride);
 }
 
-// ------------------------------------------------------------------ restriction
-// restrict3_kernel (transfer.hip): the 26 CI entries of a coarse point once, the items inside
-__global__ __launch_bounds__(128) void restrict3_many_kernel(const real_t *__restrict__ q, real_t *__restrict__ qc,
-                                                              const real_t *__restrict__ ci, int II, int JJ, int KK,
-                                                              int IIC, int JJC, int KKC, int nitems, size_t bsf, size_t bsc)
-{
-	const int ic = blockIdx.x * blockDim.x + threadIdx.x + 1;
-	const int jc = blockIdx.y + 1, kc = blockIdx.z + 1;
-	if (ic > IIC - 2) return;
-	const size_t sc = IIC, tc = (size_t)IIC * JJC, PC = tc * KKC;
-	const size_t sf = II, tf = (size_t)II * JJ;
-	const size_t c = (size_t)ic + sc * jc + tc * kc;
-	const size_t f = (size_t)(2 * ic - 1) + sf * (size_t)(2 * jc - 1) + tf * (size_t)(2 * kc - 1);
-#define CIv(slot, off) ci[(size_t)(slot)*PC + c + (off)]
-	const real_t xyne = CIv(LXYNE, 0), xya = CIv(LXYA, 0), xynw = CIv(LXYNW, 1), xyr = CIv(LXYR, 0), xyl = CIv(LXYL, 1);
-	const real_t xyse = CIv(LXYSE, sc), xyb = CIv(LXYB, sc), xysw = CIv(LXYSW, 1 + sc);
-	const real_t tne = CIv(LTNE, 0), yznw = CIv(LYZNW, 0), tnw = CIv(LTNW, 1), xzne = CIv(LXZNE, 0), xza = CIv(LXZA, 0);
-	const real_t xznw = CIv(LXZNW, 1), tse = CIv(LTSE, sc), yzne = CIv(LYZNE, sc), tsw = CIv(LTSW, 1 + sc);
-	const real_t bne = CIv(LBNE, tc), yzsw = CIv(LYZSW, tc), bnw = CIv(LBNW, 1 + tc), xzse = CIv(LXZSE, tc), xzb = CIv(LXZB, tc);
-	const real_t xzsw = CIv(LXZSW, 1 + tc), bse = CIv(LBSE, sc + tc), yzse = CIv(LYZSE, sc + tc), bsw = CIv(LBSW, 1 + sc + tc);
-#undef CIv
-	for (int m = 0; m < nitems; m++) {
-		const real_t *qm = q + (size_t)m * bsf;
-		real_t s = xyne * qm[f - 1 - sf];
-		s = s + xya * qm[f - sf];
-		s = s + xynw * qm[f + 1 - sf];
-		s = s + xyr * qm[f - 1];
-		s = s + qm[f];
-		s = s + xyl * qm[f + 1];
-		s = s + xyse * qm[f - 1 + sf];
-		s = s + xyb * qm[f + sf];
-		s = s + xysw * qm[f + 1 + sf];
-		s = s + tne * qm[f - 1 - sf - tf];
-		s = s + yznw * qm[f - sf - tf];
-		s = s + tnw * qm[f + 1 - sf - tf];
-		s = s + xzne * qm[f - 1 - tf];
-		s = s + xza * qm[f - tf];
-		s = s + xznw * qm[f + 1 - tf];
-		s = s + tse * qm[f - 1 + sf - tf];
-		s = s + yzne * qm[f + sf - tf];
-		s = s + tsw * qm[f + 1 + sf - tf];
-		s = s + bne * qm[f - 1 - sf + tf];
-		s = s + yzsw * qm[f - sf + tf];
-		s = s + bnw * qm[f + 1 - sf + tf];
-		s = s + xzse * qm[f - 1 + tf];
-		s = s + xzb * qm[f + tf];
-		s = s + xzsw * qm[f + 1 + tf];
-		s = s + bse * qm[f - 1 + sf + tf];
-		s = s + yzse * qm[f + sf + tf];
-		s = s + bsw * qm[f + 1 + sf + tf];
-		qc[(size_t)m * bsc + c] = s;
-	}
-}
-
+// ------------------------------------------------------------------ restriction, interpolation and add
+// restrict3_kernel / interp_add3_kernel with the CI entries of a lane's point or pair (and interp_add's two diagonal
+// entries) in registers across the item loop: the device bodies of transfer_dev.h on the Cedar layout (transferf.hip: on the
+// single-precision copy)
 void restrict3_many(const real_t *q, real_t *qc, const real_t *ci, int II, int JJ, int KK, int IIC, int JJC, int KKC,
                     hipStream_t st, Batch bf, Batch bc)
 {
 	if (IIC < 3 || JJC < 3 || KKC < 3 || bf.n < 1) return;
 	dim3 grid((IIC - 2 + 127) / 128, JJC - 2, KKC - 2);
-	hipLaunchKernelGGL(restrict3_many_kernel, grid, dim3(128), 0, st, q, qc, ci, II, JJ, KK, IIC, JJC, KKC, bf.n, bf.stride, bc.stride);
-}
-
-// ------------------------------------------------------------------ interpolation and add
-// interp_add3_kernel (transfer.hip) with the CI entries of a lane's pair (up to 4 for the even column, 8 for the odd one,
-// by the (j,k) parity of the row) and the two diagonal entries in registers across the item loop.  The expressions of
-// interp_add3_pair, in its order.
-struct InterpCoef {
-	real_t e[4], o[8];
-};
-
-template <bool KO, bool JO>
-__device__ __forceinline__ void interp_coef3(InterpCoef &w, bool upd_e, bool upd_o, const real_t *__restrict__ ci, size_t ce, size_t PC)
-{
-	const size_t co = ce + 1;
-#define CIe(slot) ci[(size_t)(slot)*PC + ce]
-#define CIo(slot) ci[(size_t)(slot)*PC + co]
-	if (!KO) {
-		if (!JO) {
-			if (upd_o) { w.o[0] = CIo(LXYR); w.o[1] = CIo(LXYL); }
-		} else {
-			if (upd_e) { w.e[0] = CIe(LXYA); w.e[1] = CIe(LXYB); }
-			if (upd_o) { w.o[0] = CIo(LXYSW); w.o[1] = CIo(LXYNW); w.o[2] = CIo(LXYNE); w.o[3] = CIo(LXYSE); }
-		}
-	} else {
-		if (!JO) {
-			if (upd_e) { w.e[0] = CIe(LXZA); w.e[1] = CIe(LXZB); }
-			if (upd_o) { w.o[0] = CIo(LXZNW); w.o[1] = CIo(LXZNE); w.o[2] = CIo(LXZSW); w.o[3] = CIo(LXZSE); }
-		} else {
-			if (upd_e) { w.e[0] = CIe(LYZNW); w.e[1] = CIe(LYZNE); w.e[2] = CIe(LYZSW); w.e[3] = CIe(LYZSE); }
-			if (upd_o) {
-				w.o[0] = CIo(LTNW); w.o[1] = CIo(LTNE); w.o[2] = CIo(LTSW); w.o[3] = CIo(LTSE);
-				w.o[4] = CIo(LBNW); w.o[5] = CIo(LBNE); w.o[6] = CIo(LBSW); w.o[7] = CIo(LBSE);
-			}
-		}
-	}
-#undef CIe
-#undef CIo
-}
-
-template <bool KO, bool JO>
-__device__ __forceinline__ void interp_apply3(const InterpCoef &w, real_t &ve, real_t &vo, real_t re, real_t ro, bool upd_e,
-                                              bool upd_o, const real_t *__restrict__ qc, size_t ce, size_t sc, size_t tc)
-{
-	const size_t co = ce + 1;
-	if (!KO) {
-		if (!JO) {
-			if (upd_e) ve = ve + qc[ce];
-			if (upd_o) {
-				real_t a = w.o[0] * qc[co] + w.o[1] * qc[co - 1];
-				vo = vo + a + ro;
-			}
-		} else {
-			if (upd_e) {
-				real_t a = w.e[0] * qc[ce] + w.e[1] * qc[ce - sc];
-				ve = ve + a + re;
-			}
-			if (upd_o) {
-				real_t a = w.o[0] * qc[co - 1 - sc] + w.o[1] * qc[co - 1] + w.o[2] * qc[co] + w.o[3] * qc[co - sc];
-				vo = vo + a + ro;
-			}
-		}
-	} else {
-		if (!JO) {
-			if (upd_e) ve = ve + w.e[0] * qc[ce] + w.e[1] * qc[ce - tc] + re;
-			if (upd_o)
-				vo = vo + w.o[0] * qc[co - 1] + w.o[1] * qc[co] + w.o[2] * qc[co - 1 - tc] + w.o[3] * qc[co - tc] + ro;
-		} else {
-			if (upd_e)
-				ve = ve + w.e[0] * qc[ce] + w.e[1] * qc[ce - sc] + w.e[2] * qc[ce - tc] + w.e[3] * qc[ce - sc - tc] + re;
-			if (upd_o)
-				vo = vo + w.o[0] * qc[co - 1] + w.o[1] * qc[co] + w.o[2] * qc[co - 1 - sc] + w.o[3] * qc[co - sc]
-				     + w.o[4] * qc[co - 1 - tc] + w.o[5] * qc[co - tc] + w.o[6] * qc[co - 1 - sc - tc] + w.o[7] * qc[co - sc - tc] + ro;
-		}
-	}
-}
-
-template <bool KO, bool JO>
-__device__ __forceinline__ void interp_add3_row_many(real_t *__restrict__ q, const real_t *__restrict__ qc,
-                                                     const real_t *__restrict__ so_diag, real_t *__restrict__ res,
-                                                     const real_t *__restrict__ ci, int IIF, size_t rowf, size_t rowc,
-                                                     size_t sc, size_t tc, size_t PC, bool row_in_range, bool row_interior,
-                                                     int imax_e, int imax_all, int nitems, size_t bsf, size_t bsc)
-{
-	for (int p = threadIdx.x; 2 * p + 2 <= IIF; p += blockDim.x) {
-		const int ie = 2 * p + 2, io = ie + 1; // 1-based
-		const bool have_o = io <= IIF;
-		const size_t x = rowf + (size_t)(ie - 1);
-		const bool int_e = row_interior && ie <= IIF - 1, int_o = row_interior && have_o && io <= IIF - 1;
-		const bool upd_e = row_in_range && (KO ? ie <= imax_e : ie <= imax_all);
-		const bool upd_o = row_in_range && have_o && (KO ? io <= imax_all - 1 : io <= imax_all);
-		if (!(int_e || int_o || upd_e || upd_o)) continue;
-		real_t de = 1.0, dn = 1.0;
-		if (have_o) {
-			d2u t = *reinterpret_cast<const d2u *>(so_diag + x); de = t.x; dn = t.y;
-		} else
-			de = so_diag[x];
-		const size_t ce = rowc + (size_t)(ie / 2); // 0-based: ic-1 = i/2
-		InterpCoef w;
-		interp_coef3<KO, JO>(w, upd_e, upd_o, ci, ce, PC);
-		for (int m = 0; m < nitems; m++) {
-			real_t *qm = q + (size_t)m * bsf, *rm = res + (size_t)m * bsf;
-			real_t re = 0.0, ro = 0.0, ve = 0.0, vo = 0.0;
-			if (have_o) {
-				d2u t = *reinterpret_cast<const d2u *>(rm + x); re = t.x; ro = t.y;
-				t = *reinterpret_cast<const d2u *>(qm + x); ve = t.x; vo = t.y;
-			} else {
-				re = rm[x]; ve = qm[x];
-			}
-			if (int_e) re = re / de;
-			if (int_o) ro = ro / dn;
-			if (int_e && int_o) {
-				d2u t; t.x = re; t.y = ro;
-				*reinterpret_cast<d2u *>(rm + x) = t;
-			} else {
-				if (int_e) rm[x] = re;
-				if (int_o) rm[x + 1] = ro;
-			}
-			if (!(upd_e || upd_o)) continue;
-			interp_apply3<KO, JO>(w, ve, vo, re, ro, upd_e, upd_o, qc + (size_t)m * bsc, ce, sc, tc);
-			if (upd_e && upd_o) {
-				d2u t; t.x = ve; t.y = vo;
-				*reinterpret_cast<d2u *>(qm + x) = t;
-			} else {
-				if (upd_e) qm[x] = ve;
-				if (upd_o) qm[x + 1] = vo;
-			}
-		}
-	}
-}
-
-__global__ __launch_bounds__(256) void interp_add3_many_kernel(real_t *__restrict__ q, const real_t *__restrict__ qc,
-                                                                const real_t *__restrict__ so_diag, real_t *__restrict__ res,
-                                                                const real_t *__restrict__ ci,
-                                                                int IIC, int JJC, int KKC, int IIF, int JJF, int KKF,
-                                                                int imax_e, int imax_all, int jmax, int kmax_e, int kmax_o,
-                                                                unsigned nrows, int nitems, size_t bsf, size_t bsc)
-{
-	const unsigned L = xcd_remap(blockIdx.x, nrows);
-	if (L >= nrows) return;
-	const int j = (int)(L % (unsigned)(JJF - 1)) + 2, k = (int)(L / (unsigned)(JJF - 1)) + 2; // 1-based, 2..JJF / 2..KKF
-	const size_t sf = IIF, tf = (size_t)IIF * JJF;
-	const size_t sc = IIC, tc = (size_t)IIC * JJC, PC = tc * KKC;
-	const bool jo = j & 1, ko = k & 1;
-	const int jc = jo ? (j + 1) / 2 + 1 : j / 2 + 1, kc = ko ? (k + 1) / 2 + 1 : k / 2 + 1;
-	const bool row_in_range = j <= jmax && k <= (ko ? kmax_o : kmax_e);
-	const bool row_interior = j <= JJF - 1 && k <= KKF - 1;
-	const size_t rowf = sf * (size_t)(j - 1) + tf * (size_t)(k - 1);
-	const size_t rowc = sc * (size_t)(jc - 1) + tc * (size_t)(kc - 1);
-#define ROW(KOv, JOv)                                                                                                       \
-	interp_add3_row_many<KOv, JOv>(q, qc, so_diag, res, ci, IIF, rowf, rowc, sc, tc, PC, row_in_range, row_interior, imax_e, \
-	                               imax_all, nitems, bsf, bsc)
-	if (ko) {
-		if (jo) ROW(true, true);
-		else ROW(true, false);
-	} else {
-		if (jo) ROW(false, true);
-		else ROW(false, false);
-	}
-#undef ROW
+	hipLaunchKernelGGL(restrict3_many_kernel<real_t>, grid, dim3(128), 0, st, q, qc, ci_cedar(ci, IIC, JJC, KKC), II, JJ, KK, IIC,
+	                   JJC, KKC, bf.n, bf.stride, bc.stride);
 }
 
 void interp_add3_many(real_t *q, const real_t *qc, const real_t *so, real_t *res, const real_t *ci,
                       int IIC, int JJC, int KKC, int IIF, int JJF, int KKF, hipStream_t st, Batch bf, Batch bc)
 {
 	if (IIF < 3 || JJF < 3 || KKF < 3 || bf.n < 1) return;
-	const int iicf1 = (IIF - 2) / 2 + 2, jjcf1 = (JJF - 2) / 2 + 2, kkcf1 = (KKF - 2) / 2 + 2;
-	const int imax_all = 2 * (iicf1 - 1);
-	const int imax_e = 2 * (IIC - 2);
-	const int jmax = 2 * (jjcf1 - 1);
-	const int kmax_e = 2 * (KKC - 2);
-	const int kmax_o = 2 * (kkcf1 - 1) - 1;
-	const unsigned nrows = (unsigned)(JJF - 1) * (unsigned)(KKF - 1);
-	const int bs = IIF / 2 >= 256 ? 256 : (IIF / 2 > 64 ? 128 : 64); // one lane per column pair
-	hipLaunchKernelGGL(interp_add3_many_kernel, dim3(xcd_grid(nrows)), dim3(bs), 0, st, q, qc, so /* KP plane */, res, ci,
-	                   IIC, JJC, KKC, IIF, JJF, KKF, imax_e, imax_all, jmax, kmax_e, kmax_o, nrows, bf.n, bf.stride, bc.stride);
+	const InterpRanges3 r = interp_ranges3(IIC, JJC, KKC, IIF, JJF, KKF);
+	hipLaunchKernelGGL(interp_add3_many_kernel<real_t>, dim3(xcd_grid(r.nrows)), dim3(r.bs), 0, st, q, qc, so /* KP plane */, res,
+	                   ci_cedar(ci, IIC, JJC, KKC), IIC, JJC, KKC, IIF, JJF, KKF, r.imax_e, r.imax_all, r.jmax, r.kmax_e, r.kmax_o,
+	                   r.nrows, bf.n, bf.stride, bc.stride);
 }
 
 } // namespace cedar_amd

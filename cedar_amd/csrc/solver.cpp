@@ -60,6 +60,10 @@ struct Level {
 	// floats in the form the FP64 kernel of that direction reads: the scan-ordered copy (PFx32 / PFy32) where the level
 	// keeps PFx / PFy, else the plain image of the two SOR planes (Fx32 / Fy32).  A, At, SOR*, PF* stay
 	float *At2f = nullptr, *Fx32 = nullptr, *Fy32 = nullptr, *PFx32 = nullptr, *PFy32 = nullptr;
+	// the single-precision copy of P (common.h Ci3f; transferf.hip) after
+	// cedar_amd_solver_use_fp32_interpolation: the cycle's transfers between this level and the next finer one read it, P
+	// itself stays FP64.  Never kept where the LDS-resident small-level kernels serve the finer level
+	float *P32 = nullptr;
 	// 3D 27-point: partial-sum scratch of the relax sweep (relax3d_psum.hip), one vector
 	real_t *T = nullptr;
 	// the set-up products (A, P, SOR, At, PF*) belong to another solver of the same operator (plane relaxation:
@@ -542,14 +546,28 @@ void coarse_solve(cedar_amd_solver *s, real_t *x, const real_t *b, hipStream_t s
 	else solve_cg3(x, b, C.II, C.JJ, C.KK, s->ABD, s->bbd, s->nabd1, s->nabd2, st, Batch{s->nb, C.npts});
 }
 
+// The LDS-resident small-level kernels serve the visit of 2D level L (lines_small.hip): each half of the visit is one launch
+// that fuses the transfers and reads the FP64 K.P.  A level that keeps a float copy of its operator runs the row kernels on
+// it: the copy's presence decides, before the small-level path.
+bool visit_fused(const cedar_amd_solver *s, const Level &L)
+{
+	return s->nd == 2 && s->st.ibc == 0 && s->st.relaxation <= CEDAR_AMD_RELAX_LINE_XY && !L.A2f && lines_small_ok(L.II, L.JJ);
+}
+
 // The transfers between a level L and the next coarser K, the one place that chooses their kernels by dimension, boundary
 // code and batch count.  restrict_to: K.b := P^T src; the periodic kernels first refresh the ghosts of src (restrict.f90:
-// 78-103), so it is not const.  interp_add_from: x += P K.x, with the residual correction from L.res.
+// 78-103), so it is not const.  interp_add_from: x += P K.x, with the residual correction from L.res.  Where K keeps the
+// single-precision copy of its weights (cedar_amd_solver_use_fp32_interpolation: Dirichlet handles only) both read it;
+// the diagonal interp_add divides by is the FP64 one always.  A level pair whose visit is fused never took the copy; should
+// its fine level return to that path (cedar_amd_solver_set dropped its operator copy), the F-cycle's transfers follow it.
 void restrict_to(const cedar_amd_solver *s, const Level &L, const Level &K, real_t *src, hipStream_t st)
 {
 	const int ibc = s->st.ibc;
 	const Batch bf{s->nb, L.npts}, bc{s->nb, K.npts};
-	if (s->nd == 2 && ibc) restrict2_per(src, K.b, K.P, L.II, L.JJ, K.II, K.JJ, ibc, st);
+	const bool p32 = K.P32 && !visit_fused(s, L);
+	if (p32 && s->nd == 2) restrict2_ci(ci32_view(K.P32, K.II, K.JJ), src, K.b, L.II, L.JJ, K.II, K.JJ, st, bf, bc);
+	else if (p32) restrict3_ci(ci32_view(K.P32, K.II, K.JJ, K.KK), src, K.b, L.II, L.JJ, L.KK, K.II, K.JJ, K.KK, st, bf, bc);
+	else if (s->nd == 2 && ibc) restrict2_per(src, K.b, K.P, L.II, L.JJ, K.II, K.JJ, ibc, st);
 	else if (s->nd == 2) restrict2(src, K.b, K.P, L.II, L.JJ, K.II, K.JJ, st, bf, bc);
 	else if (ibc) restrict3_per(src, K.b, K.P, L.II, L.JJ, L.KK, K.II, K.JJ, K.KK, ibc, st);
 	else if (s->nb > 1) restrict3_many(src, K.b, K.P, L.II, L.JJ, L.KK, K.II, K.JJ, K.KK, st, bf, bc);
@@ -560,7 +578,11 @@ void interp_add_from(const cedar_amd_solver *s, const Level &L, const Level &K, 
 {
 	const int ibc = s->st.ibc;
 	const Batch bf{s->nb, L.npts}, bc{s->nb, K.npts};
-	if (s->nd == 2 && ibc) interp_add2_per(x, K.x, L.res, L.A, K.P, K.II, K.JJ, L.II, L.JJ, ibc, st);
+	const bool p32 = K.P32 && !visit_fused(s, L);
+	if (p32 && s->nd == 2) interp_add2_ci(ci32_view(K.P32, K.II, K.JJ), x, K.x, L.res, L.A, K.II, K.JJ, L.II, L.JJ, st, bf, bc);
+	else if (p32)
+		interp_add3_ci(ci32_view(K.P32, K.II, K.JJ, K.KK), x, K.x, L.A, L.res, K.II, K.JJ, K.KK, L.II, L.JJ, L.KK, st, bf, bc);
+	else if (s->nd == 2 && ibc) interp_add2_per(x, K.x, L.res, L.A, K.P, K.II, K.JJ, L.II, L.JJ, ibc, st);
 	else if (s->nd == 2) interp_add2(x, K.x, L.res, L.A, K.P, K.II, K.JJ, L.II, L.JJ, st, bf, bc);
 	else if (ibc) interp_add3_per(x, K.x, L.A, L.res, K.P, K.II, K.JJ, K.KK, L.II, L.JJ, L.KK, ibc, st);
 	else if (s->nb > 1) interp_add3_many(x, K.x, L.A, L.res, K.P, K.II, K.JJ, K.KK, L.II, L.JJ, L.KK, st, bf, bc);
@@ -572,8 +594,7 @@ void ncycle(cedar_amd_solver *s, int lvl, real_t *x, const real_t *b, hipStream_
 	Level &L = s->lv[lvl], &K = s->lv[lvl + 1];
 	L.bt_fresh = false; // b of this visit has not been transposed yet
 	// a small 2D level: each half of the visit is one launch with the level resident in LDS (lines_small.hip)
-	// (a level that keeps a float copy runs the row kernels on it: the copy's presence decides, before the small-level path)
-	const bool small = s->nd == 2 && s->st.ibc == 0 && s->st.relaxation <= CEDAR_AMD_RELAX_LINE_XY && !L.A2f && lines_small_ok(L.II, L.JJ);
+	const bool small = visit_fused(s, L);
 	const int kind = s->st.relaxation == CEDAR_AMD_RELAX_POINT ? 0 : s->st.relaxation == CEDAR_AMD_RELAX_LINE_X ? 1
 	               : s->st.relaxation == CEDAR_AMD_RELAX_LINE_Y ? 2 : 3;
 	const real_t *sory = kind == 2 ? L.SOR0 : L.SOR1;
@@ -919,6 +940,7 @@ void cedar_amd_solver_destroy(cedar_amd_solver *s)
 			(void)hipFree(L.A32);
 			(void)hipFree(L.A7f);
 			(void)hipFree(L.A2f);
+			(void)hipFree(L.P32);
 			(void)hipFree(L.At2f); (void)hipFree(L.Fx32); (void)hipFree(L.Fy32); (void)hipFree(L.PFx32); (void)hipFree(L.PFy32);
 			(void)hipFree(L.PFx); (void)hipFree(L.PFy);
 		}
@@ -1295,6 +1317,86 @@ int cedar_amd_solver_use_fp32_operator_lines(cedar_amd_solver *s, int min_rows)
 	return fp32_count(s);
 }
 
+// ---- single-precision interpolation weights (include/cedar_amd.h cedar_amd_solver_use_fp32_interpolation; transferf.hip;
+// DESIGN.md section 18)
+static int ci32_count(const cedar_amd_solver *s)
+{
+	int n = 0;
+	for (const Level &L : s->lv) n += L.P32 ? 1 : 0;
+	return n;
+}
+
+// (re)build the float copy of K.P into `out`; true = a finite weight does not fit float
+static bool ci32_rebuild(cedar_amd_solver *s, const Level &K, float *out, hipStream_t st)
+{
+	int *flag = s->dinfo + 1, host = 0; // (dinfo[0]: the coarse factorisation's info)
+	CEDAR_HIP_CHECK(hipMemsetAsync(flag, 0, sizeof(int), st));
+	ci32_build(K.P, out, K.II, K.JJ, K.KK, s->nd == 3 ? 26 : 8, flag, st);
+	CEDAR_HIP_CHECK(hipMemcpyAsync(&host, flag, sizeof(int), hipMemcpyDeviceToHost, st));
+	CEDAR_HIP_CHECK(hipStreamSynchronize(st));
+	return host != 0;
+}
+
+// Smallest row count of the fine level from which a level pair takes the copy by default, per dimension: the defaults of
+// the operator switches, kept after the measurement of tools/ci32_time.py (profiles/ci32_time.json).
+// The level-0 restriction runs in 0.73 - 0.75 of its FP64 time at 512^3, 0.77 - 0.82 at 256^3 and 0.81 - 0.83 at 128^3,
+// interpolation-and-add in 0.77 - 0.91, 0.84 - 0.86 and 0.92 - 0.93; 2D 0.74 - 0.86 and 0.81 - 0.91 from 4096^2 down to
+// 1024^2.  The cycle gains 1 - 6 %, which is within what two FP64 handles of one operator differ by (up to 4.6 % at
+// 512^3), so the rule is "not slower beyond that spread": it holds at every size measured, and nothing smaller was measured
+enum { CI32_DEFAULT_MIN_ROWS_3D = 128, CI32_DEFAULT_MIN_ROWS_2D = 1024 };
+
+int cedar_amd_solver_fp32_interp_levels(const cedar_amd_solver *s)
+{
+	return null_handle(s, "cedar_amd_solver_fp32_interp_levels") ? 0 : ci32_count(s);
+}
+
+int cedar_amd_solver_use_fp32_interpolation(cedar_amd_solver *s, int min_rows)
+{
+	const char *who = "cedar_amd_solver_use_fp32_interpolation";
+	if (null_handle(s, who)) return -1;
+	auto refuse = [&](const char *reason) {
+		char msg[256];
+		snprintf(msg, sizeof(msg), "%s: %s; the handle is unchanged", who, reason);
+		print_error(msg);
+		return -1;
+	};
+	if (s->st.ibc != 0) return refuse("periodic boundary conditions (ibc != 0) are not supported");
+	if (s->nd == 3 && s->st.relaxation != CEDAR_AMD_RELAX_POINT) return refuse("plane relaxation is not supported");
+	if (min_rows < 0) return refuse("min_rows must not be negative");
+	if (min_rows == 0) {
+		const char *e = getenv("CEDAR_AMD_CI32_MIN_ROWS"); // read per call, like CEDAR_AMD_OP32_MIN_ROWS
+		min_rows = e && atoi(e) > 0 ? atoi(e) : s->nd == 3 ? (int)CI32_DEFAULT_MIN_ROWS_3D : (int)CI32_DEFAULT_MIN_ROWS_2D;
+	}
+	// every pair (fine L, coarse K) whose fine level has at least min_rows rows and runs the transfer kernels; all copies
+	// are built and checked before the handle changes
+	hipStream_t st = current_stream();
+	std::vector<std::pair<int, float *>> fresh;
+	auto undo = [&]() {
+		for (auto &f : fresh) (void)hipFree(f.second);
+	};
+	for (int l = 0; l + 1 < (int)s->lv.size(); l++) {
+		const Level &L = s->lv[l], &K = s->lv[l + 1];
+		if (K.P32 || !K.P || L.ny < min_rows || visit_fused(s, L)) continue;
+		float *c = nullptr;
+		if (hipMalloc((void **)&c, ci32_floats(K.II, K.JJ, K.KK, s->nd == 3 ? 26 : 8) * sizeof(float)) != hipSuccess) {
+			(void)hipGetLastError();
+			undo();
+			return refuse("out of device memory for the single-precision copy");
+		}
+		fresh.emplace_back(l + 1, c);
+		if (ci32_rebuild(s, K, c, st)) {
+			undo();
+			return refuse("an interpolation weight overflows single precision");
+		}
+	}
+	if (!fresh.empty()) {
+		graphs_drop(s);
+		for (auto &f : fresh) s->lv[f.first].P32 = f.second;
+	}
+	launch_check(who);
+	return ci32_count(s);
+}
+
 // levels[lvl].A / .P / .SOR / ABD are public members of the reference's solver (include/cedar/level.h:14-41,
 // include/cedar/2d/solver.h:56): a caller may replace a set-up product.  Solver-internal copies that derive from the
 // array (row-interleaved solve copy, transposed y-line planes, scan-ordered line factors) are rebuilt.
@@ -1326,6 +1428,14 @@ size_t cedar_amd_solver_set(cedar_amd_solver *s, int lvl, const char *what, cons
 		graphs_drop(s);
 		(void)hipFree(c32);
 		c32 = nullptr;
+	}
+	if (L.P32 && !strcmp(what, "P") && ci32_rebuild(s, L, L.P32, st)) {
+		char msg[] = "cedar_amd_solver_set: a weight of the new array overflows single precision; the level's transfers read the "
+		             "FP64 weights again";
+		print_error(msg);
+		graphs_drop(s);
+		(void)hipFree(L.P32);
+		L.P32 = nullptr;
 	}
 	if (L.At && !strcmp(what, "A")) setup_lines_yt(L.A, L.At, L.II, L.JJ, L.nst, st);
 	if (L.PFx && !strcmp(what, "SOR0")) lines_permute(L.SOR0, L.PFx, L.nx, L.II, L.ny, L.npts, st);

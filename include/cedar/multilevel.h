@@ -297,6 +297,19 @@ public:
 		return cedar_amd_solver_use_fp32_operator_lines(h, min_rows);
 	}
 	int fp32_levels() const { return h ? cedar_amd_solver_fp32_levels(h) : 0; }
+	// single-precision interpolation weights for the cycle's restriction and interpolation-and-add
+	// (cedar_amd_solver_use_fp32_interpolation): 2D and 3D, independent of the operator switches above; min_rows > 0 takes
+	// every level pair whose fine level has at least that many rows; min_rows = 0: the default (128 rows in 3D, 1024 in 2D).
+	// Returns the number of level pairs that read a float copy, -1 if refused
+	int use_fp32_interpolation(int min_rows = 0)
+	{
+		if (!h) {
+			log::error << "use_fp32_interpolation: needs the device-resident solver (every kernel \"hip\")" << std::endl;
+			return -1;
+		}
+		return cedar_amd_solver_use_fp32_interpolation(h, min_rows);
+	}
+	int fp32_interp_levels() const { return h ? cedar_amd_solver_fp32_interp_levels(h) : 0; }
 
 	void vcycle(grid_func & x, const grid_func & b)
 	{

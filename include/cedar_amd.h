@@ -587,6 +587,48 @@ int cedar_amd_solver_use_fp32_operator_2d(cedar_amd_solver *s, int min_rows);
  * feed (overflow: reported, the level drops its float copies and reads FP64 again).  The four calls above are unchanged
  * and keep refusing what they refuse. */
 int cedar_amd_solver_use_fp32_operator_lines(cedar_amd_solver *s, int min_rows);
+/* Single-precision interpolation weights for the cycle's grid transfers (transferf.hip): 2D and 3D,
+ * 5/9/7/27-point, Dirichlet (ibc == 0), point relaxation in 3D, point and line relaxation in 2D, V- and F-cycles, handles
+ * of cedar_amd_solver_create and _create_many.  For every pair (fine level L, coarse level K) whose fine level has at least
+ * min_rows rows, K keeps a float copy of its weights K.P (rounded to nearest even; slot planes, every coarse row on a
+ * 128-byte line), and the cycle's restriction and interpolation-and-add between the two read it: each has the bits of the
+ * FP64 kernel on the rounded weights.  K.P stays FP64 and unrounded (cedar_amd_solver_get "P" returns it as before), and
+ * the diagonal that interpolation-and-add divides by stays the FP64 one.  A 2D pair whose fine level the LDS-resident
+ * small-level kernels serve (they fuse the transfers) keeps FP64 weights and is not counted; the copy never moves a level
+ * off that path.
+ * The weights enter a cycle through the coarse-grid correction only, never through the residual, and R = P^T uses the
+ * same rounded weights.  So cedar_amd_solver_solve / _solve_many stay plain iterations of the cycle and converge to the
+ * solution of the operator given (no defect-correction form), the preconditioner stays symmetric and _pcg serves it;
+ * _vcycle / _vcycle_many run the cycle with the rounded weights; _pcg / _fcg, their _many forms and _precondition use it
+ * as the preconditioner, their Krylov passes are untouched.
+ * The switch is independent of the five operator switches above: it may be called before or after any of them, and each
+ * keeps its own count (cedar_amd_solver_fp32_levels does not count weights, cedar_amd_solver_fp32_interp_levels does not
+ * count operators).
+ *   min_rows > 0: every pair whose fine level has at least min_rows rows.
+ *   min_rows 0  : the default, fine levels of at least 128 rows in 3D and 1024 rows in 2D (CEDAR_AMD_CI32_MIN_ROWS overrides
+ *                 it, read at the call); DESIGN.md section 18 and profiles/ci32_time.json hold what it rests on.
+ * Copies are built and checked before the handle changes, captured graphs are dropped, the call may be repeated and never
+ * switches a pair back; returns the number of level pairs that read a float copy (0 is valid), which
+ * cedar_amd_solver_fp32_interp_levels reports too.  Refused -- print_error, -1, handle unchanged -- for a NULL handle,
+ * ibc != 0, 3D plane relaxation, a negative min_rows, a weight that is finite in FP64 and not in float, and out of device
+ * memory.  cedar_amd_solver_set "P" on a switched level rebuilds its copy (overflow: reported, the level's transfers read
+ * the FP64 weights again). */
+int cedar_amd_solver_use_fp32_interpolation(cedar_amd_solver *s, int min_rows);
+int cedar_amd_solver_fp32_interp_levels(const cedar_amd_solver *s);
+/* The transfer kernels on a float copy of the weights built for the call (for tests): the arguments of
+ * BMG2_/BMG3_SymStd_restrict, _interp_add (Dirichlet: no boundary code), cedar_amd_restrict3_many and
+ * cedar_amd_interp_add3_many; every result has the bits of that entry point on the weights rounded to float.  0 when
+ * served; non-zero, with nothing written, when refused (a NULL array, an extent below 3, a weight that overflows float). */
+int cedar_amd_restrict2_ci32(real_t *q, real_t *qc, real_t *ci, int ii, int jj, int iic, int jjc);
+int cedar_amd_interp_add2_ci32(real_t *q, real_t *qc, real_t *res, real_t *so, real_t *ci, len_t iic, len_t jjc, len_t ii,
+                               len_t jj, int nstncl);
+int cedar_amd_restrict3_ci32(real_t *q, real_t *qc, real_t *ci, len_t ii, len_t jj, len_t kk, len_t iic, len_t jjc, len_t kkc);
+int cedar_amd_interp_add3_ci32(real_t *q, real_t *qc, real_t *so, real_t *res, real_t *ci, len_t iic, len_t jjc, len_t kkc,
+                               len_t ii, len_t jj, len_t kk, int nstncl);
+int cedar_amd_restrict3_many_ci32(int nrhs, real_t *q, real_t *qc, real_t *ci, len_t ii, len_t jj, len_t kk, len_t iic,
+                                  len_t jjc, len_t kkc);
+int cedar_amd_interp_add3_many_ci32(int nrhs, real_t *q, real_t *qc, real_t *so, real_t *res, real_t *ci, len_t iic, len_t jjc,
+                                    len_t kkc, len_t iif, len_t jjf, len_t kkf, int nstncl);
 
 /* Several right-hand sides at once on one resident hierarchy.  The operator, 1/diag and the interpolation weights are
  * the same for every right-hand side, so the batched 3D kernels (many3d.hip) fetch them once per workgroup task and apply
