@@ -475,6 +475,15 @@ class Kernels:
                                        _p(sc), _p(partial)) != 0:
             raise RuntimeError("cedar_amd_pcg_direction refused")
 
+    def pcg_direction_periodic(self, so, z, p, pn, w, ibc, first, sc, partial=None):
+        """pcg_direction on a level with the periodic directions of boundary code ibc: a neighbour on the ghost layer of
+        a periodic direction is read at the opposite interior end; no such ghost of z or p contributes to a result"""
+        assert tuple(so.shape[1:]) == tuple(z.shape) and all(a is None or a.shape == z.shape for a in (p, pn, w))
+        assert sc.size == 8 and (partial is None or partial.size >= 1)
+        if lib.cedar_amd_pcg_direction_periodic(_p(so), _p(z), _p(p), _p(pn), _p(w), *self._dims(z), so.shape[0], int(ibc),
+                                                int(first), _p(sc), _p(partial)) != 0:
+            raise RuntimeError("cedar_amd_pcg_direction_periodic refused")
+
     def pcg_update(self, zmode, move, x, r, p, w, z, diag, first, sc, partial=None):
         """x += alpha p, r -= alpha w (move), r.r and r.z by zmode -> sc (or partial[0:2], sc untouched)"""
         assert all(a is None or a.shape == r.shape for a in (x, p, w, z, diag))
@@ -621,6 +630,8 @@ lib.cedar_amd_solver_fcg.restype = C.c_int
 lib.cedar_amd_solver_fcg.argtypes = lib.cedar_amd_solver_pcg.argtypes
 lib.cedar_amd_solver_fcg_many.restype = C.c_int
 lib.cedar_amd_solver_fcg_many.argtypes = lib.cedar_amd_solver_pcg_many.argtypes
+lib.cedar_amd_solver_fcg_periodic.restype = C.c_int
+lib.cedar_amd_solver_fcg_periodic.argtypes = lib.cedar_amd_solver_pcg.argtypes
 lib.cedar_amd_solver_use_fp32_operator.restype = C.c_int
 lib.cedar_amd_solver_use_fp32_operator.argtypes = [C.c_void_p, C.c_int]
 lib.cedar_amd_solver_use_fp32_operator_many.restype = C.c_int
@@ -774,6 +785,12 @@ class Solver:
         """flexible conjugate gradients (cedar_amd_solver_fcg): pcg with the Polak-Ribiere beta, so any cycle of the
         handle may be the preconditioner -- V(m,n), F-cycles, plane relaxation.  Same arguments and return as pcg"""
         return self._cg("cedar_amd_solver_fcg", b, x, max_iter, tol, stop, precon, nmg_cycles)
+
+    def fcg_periodic(self, b, x, max_iter=50, tol=1e-8, stop="rel_l2", precon="mg", nmg_cycles=1):
+        """flexible conjugate gradients on a handle made with ibc != 0 (cedar_amd_solver_fcg_periodic): the operator pass
+        wraps around in the periodic directions, the ghost layers of b and x do not matter and x comes back with the
+        periodic image in its ghosts.  A handle with ibc = 0 is served by fcg.  Same arguments and return as pcg"""
+        return self._cg("cedar_amd_solver_fcg_periodic", b, x, max_iter, tol, stop, precon, nmg_cycles)
 
     def fcg_many(self, b, x, max_iter=50, tol=1e-8, stop="rel_l2", precon="mg", nmg_cycles=1, hist=None):
         """fcg for the items of b, x in lockstep (cedar_amd_solver_fcg_many); same arguments and return as pcg_many"""

@@ -806,6 +806,27 @@ int cedar_amd_pcg_direction(const real_t *so, const real_t *z, const real_t *p, 
 	return 0;
 }
 
+// the pass of a periodic level (krylov.hip pcg_direction_periodic); a 27-point operator is read from its Cedar planes
+int cedar_amd_pcg_direction_periodic(const real_t *so, const real_t *z, const real_t *p, real_t *pn, real_t *w, len_t ii,
+                                     len_t jj, len_t kk, int nstncl, int ibc, int first, real_t *sc, real_t *partial)
+{
+	const char *who = "cedar_amd_pcg_direction_periodic";
+	if (ibc == 0) return cedar_amd_pcg_direction(so, z, p, pn, w, ii, jj, kk, nstncl, first, sc, partial);
+	if (pcg_shape_refused(ii, jj, kk, who)) return -1;
+	const int nd = kk == 1 ? 2 : 3;
+	if (nd == 2 ? (ibc < 1 || ibc > 3) : (ibc < 1 || !periodic3_code_ok(ibc)))
+		return pcg_refuse(who, "ibc must be 0..3 (2D), 0..3 or 5..8 (3D)"), -1;
+	if (nd == 2 ? (nstncl != 3 && nstncl != 5) : (nstncl != 4 && nstncl != 14)) return pcg_refuse(who, "nstncl must be 3|5 (2D), 4|14 (3D)"), -1;
+	if (!so || !z || !pn || !w || !sc || (!first && !p)) return pcg_refuse(who, "a required array is NULL"), -1;
+	const size_t P = (size_t)ii * jj * kk;
+	NanSlab slab(pcg_slab_doubles(nd, nstncl, (int)ii, (int)jj, (int)kk));
+	Staged sso(so, P * nstncl, true, false), sz(z, P, true, false), sp(first ? nullptr : p, P, true, false),
+	    spn(pn, P, true, true), sw(w, P, true, true), ssc(sc, PCG_NSC, true, partial == nullptr), spart(partial, 1, true, true);
+	pcg_direction_periodic(sso.get(), sz.get(), sp.get(), spn.get(), sw.get(), nd, nstncl, (int)ii, (int)jj, (int)kk, ibc,
+	                       first != 0, slab.dev, ssc.get(), current_stream(), spart.get());
+	return 0;
+}
+
 int cedar_amd_pcg_update(int zmode, int move, real_t *x, real_t *r, const real_t *p, const real_t *w, real_t *z,
                          const real_t *diag, len_t ii, len_t jj, len_t kk, int first, real_t *sc, real_t *partial)
 {

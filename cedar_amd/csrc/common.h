@@ -437,6 +437,24 @@ size_t pcg_slab_doubles(int nd, int nst, int II, int JJ, int KK); // partial-sum
 void pcg_direction(const real_t *so, const Op3 *op27, const real_t *z, const real_t *p, real_t *pn, real_t *w, int nd,
                    int nst, int II, int JJ, int KK, bool first, real_t *slab, real_t *sc, hipStream_t st,
                    real_t *partial = nullptr);
+// The same pass on a level with periodic directions (cedar_amd_solver_fcg_periodic): a stencil neighbour that falls on the
+// ghost layer of a periodic direction is read at the opposite interior end (index 0 -> extent - 2, extent - 1 -> 1, edges
+// and corners in every combination), so no ghost cell of z or p in a periodic direction contributes to a result; ghosts
+// of the other directions are read as in pcg_direction.  Operator entries are read where pcg_direction reads them (their
+// ghost layers hold the periodic image, as the periodic cycle requires).  Same slab, same second stage; 27-point: the
+// Cedar planes.
+struct PerDirs {
+	int x, y, z;
+};
+// the periodic directions of a boundary code (2D: 1 y, 2 x, 3 xy; 3D: 1 y, 2 x, 3 xy, 5 z, 6 xz, 7 yz, 8 xyz)
+static inline PerDirs per_dirs(int nd, int ibc)
+{
+	return PerDirs{ibc == 2 || ibc == 3 || (nd == 3 && (ibc == 6 || ibc == 8)), ibc == 1 || ibc == 3 || (nd == 3 && (ibc == 7 || ibc == 8)),
+	               nd == 3 && ibc >= 5 && ibc <= 8};
+}
+void pcg_direction_periodic(const real_t *so, const real_t *z, const real_t *p, real_t *pn, real_t *w, int nd, int nst, int II,
+                            int JJ, int KK, int ibc, bool first, real_t *slab, real_t *sc, hipStream_t st,
+                            real_t *partial = nullptr);
 // move: x += alpha p, r -= alpha w; then r.r and by zmode 0 (z = r) / 1 (z = r / diag, written) / 2 (z read) r.z with
 // the new rho and beta (first: beta = 0); zmode 3: r.r only.  diag: the operator's centre slot.  KK = 1 for 2D.
 void pcg_update(int zmode, bool move, real_t *x, real_t *r, const real_t *p, const real_t *w, real_t *z,

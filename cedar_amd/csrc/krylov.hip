@@ -3,7 +3,9 @@
 //
 //   pcg_direction  p' = z + beta p, w = A p', sigma = p'.w          (p' in the other buffer of a pair: p is read at
 //                  the stencil neighbours, so it cannot be overwritten in place)
-//   pcg_update     x += alpha p', r -= alpha w, r.r  [precon = diag: z = r / a_ii and r.z fused]
+//   pcg_direction_periodic   the same pass on a level with periodic directions (cedar_amd_solver_fcg_periodic): the
+//                  neighbours across a periodic boundary are read at the opposite interior end; same bytes per point
+//   pcg_update    x += alpha p', r -= alpha w, r.r  [precon = diag: z = r / a_ii and r.z fused]
 //                  or, without the x / r update: r.r and r.z of the preconditioned residual
 //
 // Every pass streams the interior only, leaves one partial sum per workgroup in a slab and is followed by a
@@ -124,6 +126,87 @@ __global__ __launch_bounds__(256) void pcg_dir2(const real_t *__restrict__ so, c
 	dir2_segment<NINE, FIRST>(so, z, p, pn, w, sc, II, JJ, part);
 }
 
+// ---------------------------------------------------------------- the same on a level with periodic directions
+// (pcg_direction_periodic).  A neighbour index on the ghost layer of a periodic direction becomes the opposite interior end:
+// 0 -> extent - 2, extent - 1 -> 1.  Only the ADDRESS of z / p changes -- the expression z + beta p, the operator entries
+// (read where the kernels above read them; their ghost layers hold the periodic image) and the term order are the same, so
+// w has the bits of matvec2 / matvec3 on a vector whose ghosts were wrapped first.  pd is uniform over the launch.
+__device__ __forceinline__ int wrap_lo(int i, int n, int per) { return per && i == 0 ? n - 2 : i; }     // i - 1 of a point
+__device__ __forceinline__ int wrap_hi(int i, int n, int per) { return per && i == n - 1 ? 1 : i; }     // i + 1 of a point
+
+template <bool NINE, bool FIRST>
+__global__ __launch_bounds__(256) void pcg_dir2_per(const real_t *__restrict__ so, const real_t *__restrict__ z,
+                                                    const real_t *__restrict__ p, real_t *__restrict__ pn,
+                                                    real_t *__restrict__ w, const real_t *__restrict__ sc, int II, int JJ,
+                                                    PerDirs pd, real_t *__restrict__ part)
+{
+	__shared__ real_t lds[4];
+	const int i = blockIdx.x * blockDim.x + threadIdx.x + 1;
+	const int j = blockIdx.y + 1;
+	const real_t beta = FIRST ? 0.0 : sc[PCG_BETA];
+	real_t acc = 0.0;
+	if (i <= II - 2) {
+		const size_t sj = II, PS = (size_t)II * JJ;
+		const size_t x = (size_t)i + sj * (size_t)j;
+		const size_t iw = wrap_lo(i - 1, II, pd.x), ie = wrap_hi(i + 1, II, pd.x);
+		const size_t rs = sj * (size_t)wrap_lo(j - 1, JJ, pd.y), rc = sj * (size_t)j, rn = sj * (size_t)wrap_hi(j + 1, JJ, pd.y);
+		auto P = [&](size_t y) -> real_t { return FIRST ? z[y] : z[y] + beta * p[y]; };
+		const real_t pc = P(x);
+		real_t s = so[KO * PS + x] * pc;
+		s = s - so[KW * PS + x] * P(rc + iw);
+		s = s - so[KW * PS + x + 1] * P(rc + ie);
+		s = s - so[KS * PS + x] * P(rs + i);
+		s = s - so[KS * PS + x + sj] * P(rn + i);
+		if (NINE) {
+			s = s - so[KSW * PS + x] * P(rs + iw);
+			s = s - so[KNW * PS + x + 1] * P(rs + ie);
+			s = s - so[KNW * PS + x + sj] * P(rn + iw);
+			s = s - so[KSW * PS + x + 1 + sj] * P(rn + ie);
+		}
+		pn[x] = pc;
+		w[x] = s;
+		acc = pc * s;
+	}
+	const real_t t = block_sum_k<256>(acc, lds);
+	if (threadIdx.x == 0) part[blockIdx.x + (size_t)gridDim.x * blockIdx.y] = t;
+}
+
+template <bool FIRST>
+__global__ __launch_bounds__(256) void pcg_dir7_per(const real_t *__restrict__ so, const real_t *__restrict__ z,
+                                                    const real_t *__restrict__ p, real_t *__restrict__ pn,
+                                                    real_t *__restrict__ w, const real_t *__restrict__ sc, int II, int JJ,
+                                                    int KK, unsigned nrows, PerDirs pd, real_t *__restrict__ part)
+{
+	__shared__ real_t lds[4];
+	const unsigned L = xcd_remap(blockIdx.x, nrows);
+	if (L >= nrows) return; // grid padding of xcd_grid: no slab entry
+	const int j = (int)(L % (unsigned)(JJ - 2)) + 1, k = (int)(L / (unsigned)(JJ - 2)) + 1;
+	const size_t sj = II, sk = (size_t)II * JJ, PS = sk * KK;
+	const size_t row = sj * (size_t)j + sk * (size_t)k;
+	// the four neighbour rows, wrapped (uniform over the workgroup)
+	const size_t rs = sj * (size_t)wrap_lo(j - 1, JJ, pd.y) + sk * (size_t)k, rn = sj * (size_t)wrap_hi(j + 1, JJ, pd.y) + sk * (size_t)k;
+	const size_t rb = sj * (size_t)j + sk * (size_t)wrap_lo(k - 1, KK, pd.z), rt = sj * (size_t)j + sk * (size_t)wrap_hi(k + 1, KK, pd.z);
+	const real_t beta = FIRST ? 0.0 : sc[PCG_BETA];
+	auto P = [&](size_t y) -> real_t { return FIRST ? z[y] : z[y] + beta * p[y]; };
+	real_t acc = 0.0;
+	for (int i = threadIdx.x + 1; i <= II - 2; i += blockDim.x) {
+		const size_t x = row + (size_t)i;
+		const real_t pc = P(x);
+		real_t s = so[KP * PS + x] * pc;
+		s = s - so[KPW * PS + x] * P(row + (size_t)wrap_lo(i - 1, II, pd.x));
+		s = s - so[KPS * PS + x + sj] * P(rn + (size_t)i);
+		s = s - so[KPW * PS + x + 1] * P(row + (size_t)wrap_hi(i + 1, II, pd.x));
+		s = s - so[KPS * PS + x] * P(rs + (size_t)i);
+		s = s - so[KB * PS + x] * P(rb + (size_t)i);
+		s = s - so[KB * PS + x + sk] * P(rt + (size_t)i);
+		pn[x] = pc;
+		w[x] = s;
+		acc += pc * s;
+	}
+	const real_t t = block_sum_k<256>(acc, lds);
+	if (threadIdx.x == 0) part[L] = t;
+}
+
 // 3D 7-point: one workgroup per grid row (residual3_kernel's layout); partial of logical row L at part[L]
 template <bool FIRST>
 __global__ __launch_bounds__(256) void pcg_dir7(const real_t *__restrict__ so, const real_t *__restrict__ z,
@@ -199,6 +282,101 @@ __global__ __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(2))) void pc
 						qo[dk][dj][1] = qe[dk][dj][2];
 						qo[dk][dj][2] = w3 + beta * qo[dk][dj][2];
 					}
+			}
+			const real_t we = mv27(de, ce, qe);
+			const real_t pe = qe[1][1][1];
+			acc += pe * we;
+			if (o_ok) {
+				const real_t wo = mv27(dn, co, qo);
+				const real_t po = qo[1][1][1];
+				acc += po * wo;
+				d2u v; v.x = we; v.y = wo;
+				*reinterpret_cast<d2u *>(w + row + ie) = v;
+				v.x = pe; v.y = po;
+				*reinterpret_cast<d2u *>(pn + row + ie) = v;
+			} else {
+				w[row + ie] = we;
+				pn[row + ie] = pe;
+			}
+		}
+	}
+	const real_t t = block_sum_k<BS>(acc, lds);
+	if (threadIdx.x == 0) part[L] = t;
+}
+
+// pcg_dir27 on a level with periodic directions.  Wrapping j and k changes the row pointer of a window row (uniform over
+// the workgroup).  Wrapping i concerns two elements of a row's windows only: the left element of the lane that owns point 1
+// and the right element of the lane that owns the last point (an odd nx ends in a half pair: its right neighbour, the
+// element ldpair read at io, is the wrap) -- those are replaced by z + beta p at the wrapped address after the pair loads,
+// so nothing formed from a ghost value reaches w, pn or the sum.  The coefficients: load_coef27 on the Cedar planes, as
+// pcg_dir27 (a periodic level has no row-interleaved copy).
+template <int BS, bool FIRST>
+__global__ __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(2))) void pcg_dir27_per(
+    const Op3 A, const real_t *__restrict__ z, const real_t *__restrict__ p, real_t *__restrict__ pn, real_t *__restrict__ w,
+    const real_t *__restrict__ sc, int II, int JJ, int KK, unsigned nblk, TileShape ts, PerDirs pd, real_t *__restrict__ part)
+{
+	__shared__ real_t lds[(BS + 63) / 64];
+	const unsigned L = xcd_remap(blockIdx.x, nblk);
+	if (L >= nblk) return; // grid padding: no slab entry
+	unsigned jr, kr;
+	real_t acc = 0.0;
+	if (tile_rows(L, (unsigned)(JJ - 2), (unsigned)(KK - 2), ts, jr, kr)) {
+		const real_t beta = FIRST ? 0.0 : sc[PCG_BETA];
+		const int j = (int)jr + 1, k = (int)kr + 1;
+		const size_t sj = (size_t)II, sk = (size_t)II * JJ;
+		const size_t row = (size_t)j * sj + (size_t)k * sk, rowA = (size_t)j * A.SJ + (size_t)k * A.SK;
+		// the window rows (j-1, j, j+1) x (k-1, k, k+1), wrapped
+		const size_t oj[3] = {sj * (size_t)wrap_lo(j - 1, JJ, pd.y), sj * (size_t)j, sj * (size_t)wrap_hi(j + 1, JJ, pd.y)};
+		const size_t ok[3] = {sk * (size_t)wrap_lo(k - 1, KK, pd.z), sk * (size_t)k, sk * (size_t)wrap_hi(k + 1, KK, pd.z)};
+		for (int q = threadIdx.x; 2 * q + 1 <= II - 2; q += BS) {
+			const int ie = 2 * q + 1, io = 2 * q + 2;
+			const bool o_ok = io <= II - 2, two = io + 1 <= II - 1;
+			C27 ce, co;
+			real_t qe[3][3][3], qo[3][3][3], de, dn;
+			load_coef27<false, false, false>(A, rowA, ie, io, two, ce, co);
+			ldpair(A.so + rowA + ie, true, de, dn); // KP plane
+			// the nine window rows as pcg_dir27 loads them (every load of the task issued before any patch below)
+#pragma unroll
+			for (int dk = 0; dk < 3; dk++)
+#pragma unroll
+				for (int dj = 0; dj < 3; dj++) {
+					const size_t y = oj[dj] + ok[dk];
+					real_t w0, w1, w2, w3;
+					ldpair(z + y + ie - 1, true, w0, w1);
+					ldpair(z + y + io, two, w2, w3);
+					if (!FIRST) {
+						real_t p0, p1, p2, p3;
+						ldpair(p + y + ie - 1, true, p0, p1);
+						ldpair(p + y + io, two, p2, p3);
+						w0 = w0 + beta * p0;
+						w1 = w1 + beta * p1;
+						w2 = w2 + beta * p2;
+						w3 = w3 + beta * p3;
+					}
+					qe[dk][dj][0] = w0; qe[dk][dj][1] = w1; qe[dk][dj][2] = w2;
+					qo[dk][dj][0] = w1; qo[dk][dj][1] = w2; qo[dk][dj][2] = w3;
+				}
+			// periodic x (uniform branch): the window elements formed from a ghost of the row -- index 0 in the lane of point
+			// 1; index II - 1 in the lane of the last point, its w3, or its w2 when the row ends in a half pair -- are
+			// replaced by the same expression at the wrapped address, so what was formed from the ghost is dropped unused
+			if (pd.x) {
+				auto P = [&](size_t y) -> real_t { return FIRST ? z[y] : z[y] + beta * p[y]; };
+				if (ie == 1) {
+#pragma unroll
+					for (int dk = 0; dk < 3; dk++)
+#pragma unroll
+						for (int dj = 0; dj < 3; dj++) qe[dk][dj][0] = P(oj[dj] + ok[dk] + II - 2);
+				}
+				if (io + 1 >= II - 1) {
+#pragma unroll
+					for (int dk = 0; dk < 3; dk++)
+#pragma unroll
+						for (int dj = 0; dj < 3; dj++) {
+							const real_t v = P(oj[dj] + ok[dk] + 1);
+							if (two) qo[dk][dj][2] = v;
+							else qe[dk][dj][2] = v;
+						}
+				}
 			}
 			const real_t we = mv27(de, ce, qe);
 			const real_t pe = qe[1][1][1];
@@ -829,6 +1007,39 @@ void pcg_direction(const real_t *so, const Op3 *op27, const real_t *z, const rea
 		n = tile_blocks((unsigned)(JJ - 2), (unsigned)(KK - 2), ts);
 		const int npairs = (II - 2 + 1) / 2;
 #define L27_(BS, F) hipLaunchKernelGGL((pcg_dir27<BS, F>), dim3(xcd_grid(n)), dim3(BS), 0, st, A, z, p, pn, w, sc, II, JJ, KK, n, ts, slab)
+		if (npairs <= 64) { if (first) L27_(64, true); else L27_(64, false); }
+		else if (npairs <= 128) { if (first) L27_(128, true); else L27_(128, false); }
+		else { if (first) L27_(256, true); else L27_(256, false); }
+#undef L27_
+	}
+	if (partial) hipLaunchKernelGGL(pcg_partial, dim3(1), dim3(RED_BS), 0, st, slab, n, 1, partial);
+	else hipLaunchKernelGGL(pcg_alpha, dim3(1), dim3(RED_BS), 0, st, slab, n, sc);
+}
+
+// pcg_direction's launch geometry (grid, workgroup width, slab layout) and second stage with the wrap-around kernels
+void pcg_direction_periodic(const real_t *so, const real_t *z, const real_t *p, real_t *pn, real_t *w, int nd, int nst, int II,
+                            int JJ, int KK, int ibc, bool first, real_t *slab, real_t *sc, hipStream_t st, real_t *partial)
+{
+	const PerDirs pd = per_dirs(nd, ibc);
+	unsigned n = 0;
+	if (nd == 2) {
+		dim3 grid((II - 2 + 255) / 256, JJ - 2);
+		n = grid.x * grid.y;
+#define L2_(NINE, F) hipLaunchKernelGGL((pcg_dir2_per<NINE, F>), grid, dim3(256), 0, st, so, z, p, pn, w, sc, II, JJ, pd, slab)
+		if (nst == 5) { if (first) L2_(true, true); else L2_(true, false); }
+		else { if (first) L2_(false, true); else L2_(false, false); }
+#undef L2_
+	} else if (nst == 4) {
+		n = (unsigned)(JJ - 2) * (unsigned)(KK - 2);
+		const int bs = II - 2 >= 256 ? 256 : (II - 2 > 64 ? 128 : 64);
+		if (first) hipLaunchKernelGGL(pcg_dir7_per<true>, dim3(xcd_grid(n)), dim3(bs), 0, st, so, z, p, pn, w, sc, II, JJ, KK, n, pd, slab);
+		else hipLaunchKernelGGL(pcg_dir7_per<false>, dim3(xcd_grid(n)), dim3(bs), 0, st, so, z, p, pn, w, sc, II, JJ, KK, n, pd, slab);
+	} else {
+		const Op3 A = op3_cedar(so, nullptr, II, JJ, KK);
+		const TileShape ts = tile_shape_resid();
+		n = tile_blocks((unsigned)(JJ - 2), (unsigned)(KK - 2), ts);
+		const int npairs = (II - 2 + 1) / 2;
+#define L27_(BS, F) hipLaunchKernelGGL((pcg_dir27_per<BS, F>), dim3(xcd_grid(n)), dim3(BS), 0, st, A, z, p, pn, w, sc, II, JJ, KK, n, ts, pd, slab)
 		if (npairs <= 64) { if (first) L27_(64, true); else L27_(64, false); }
 		else if (npairs <= 128) { if (first) L27_(128, true); else L27_(128, false); }
 		else { if (first) L27_(256, true); else L27_(256, false); }

@@ -1713,9 +1713,18 @@ static int pcg_run(cedar_amd_solver *s, int nrhs, const real_t *b, real_t *x, co
 	double sc[CEDAR_AMD_MAX_RHS * PCG_NSC], r0[CEDAR_AMD_MAX_RHS], m0[CEDAR_AMD_MAX_RHS];
 	int itm[CEDAR_AMD_MAX_RHS];
 	unsigned active = nrhs >= 32 ? ~0u : (1u << nrhs) - 1u;
+	// a periodic handle (cedar_amd_solver_fcg_periodic only, one right-hand side): x gets the periodic image in its ghost
+	// layers before the residual reads them and again on return; the direction pass wraps its own reads (krylov.hip)
+	const int ibc = s->st.ibc;
+	auto wrap_x = [&]() {
+		if (ibc && s->nd == 2) wrap2(X, L.II, L.JJ, 1, ibc == 1 || ibc == 3, ibc == 2 || ibc == 3, st);
+		else if (ibc) wrap3(X, L.II, L.JJ, L.KK, 1, ibc, st);
+	};
 	// the two passes on the active items; update: pn = nullptr leaves x and r where they are (dot products only)
 	auto direction = [&](const real_t *pold, real_t *pn, bool first) {
-		if (nrhs == 1)
+		if (ibc)
+			pcg_direction_periodic(L.A, Z, pold, pn, s->kw, s->nd, L.nst, L.II, L.JJ, L.KK, ibc, first, s->kslab, s->ksc, st);
+		else if (nrhs == 1)
 			pcg_direction(L.A, op27, Z, pold, pn, s->kw, s->nd, L.nst, L.II, L.JJ, L.KK, first, s->kslab, s->ksc, st);
 		else
 			pcg_direction_many(L.A, op27, Z, pold, pn, s->kw, s->nd, L.nst, L.II, L.JJ, L.KK, first, s->kslab, s->ksc, st, bt, active);
@@ -1739,6 +1748,7 @@ static int pcg_run(cedar_amd_solver *s, int nrhs, const real_t *b, real_t *x, co
 
 	// r0 = b - A x0, z0 = M^-1 r0, rho0 = r0.z0 of every item (the update pass without the update)
 	zero_fill(s->ksc, (size_t)PCG_NSC * nrhs, st);
+	wrap_x();
 	residual_true(s, L, X, sb.get(), s->kr, st);
 	if (zm == 2) pcg_precondition(s, p.nmg_cycles, st);
 	update(zm, nullptr, true);
@@ -1768,6 +1778,7 @@ static int pcg_run(cedar_amd_solver *s, int nrhs, const real_t *b, real_t *x, co
 		}
 		if (zm == 2 && !rule.mnorm && k + 1 < p.max_iter && active) precondition_dots(); // z of the new residuals, for the next direction
 	}
+	wrap_x();
 	launch_check(who);
 	int most = 0;
 	for (int m = 0; m < nrhs; m++) {
@@ -1798,10 +1809,10 @@ int cedar_amd_solver_pcg_many(cedar_amd_solver *s, int nrhs, const real_t *b, re
 }
 
 // Flexible CG: what cedar_amd_solver_pcg refuses of the multigrid preconditioner for its lack of symmetry is served here
-static bool fcg_refused(const cedar_amd_solver *s, const cedar_amd_pcg_settings &p, const char *who)
+static bool fcg_refused(const cedar_amd_solver *s, const cedar_amd_pcg_settings &p, const char *who, bool periodic_ok = false)
 {
 	const char *why = nullptr;
-	if (s->st.ibc != 0) why = "periodic boundary conditions (ibc != 0) are not supported";
+	if (s->st.ibc != 0 && !periodic_ok) why = "periodic boundary conditions (ibc != 0) are not supported";
 	else if (p.stop_test < CEDAR_AMD_PCG_STOP_ABS_RES_L2 || p.stop_test > CEDAR_AMD_PCG_STOP_REL_RES_M2) why = "stop_test must be 0..3";
 	else if (p.precon < CEDAR_AMD_PCG_PRECON_NONE || p.precon > CEDAR_AMD_PCG_PRECON_BMG) why = "precon must be 1..3";
 	else if (p.max_iter < 0) why = "max_iter must not be negative";
@@ -1834,6 +1845,30 @@ int cedar_amd_solver_fcg_many(cedar_amd_solver *s, int nrhs, const real_t *b, re
 	const cedar_amd_pcg_settings p = pcg_settings_or_default(settings);
 	if (fcg_refused(s, p, who)) return -1;
 	return pcg_run(s, nrhs, b, x, p, hist, iters, who, p.precon == CEDAR_AMD_PCG_PRECON_BMG);
+}
+
+// Flexible CG on a periodic handle.  The periodic cycle is not a symmetric operator (its coarsest solve removes the mean,
+// its sweeps are ordered with the ghost refreshes), so only the flexible beta is offered with it; precon none / diag are
+// exactly symmetric and keep the standard beta, as in cedar_amd_solver_fcg.  Every configuration solver_create accepts
+// with ibc != 0 holds one right-hand side; a batch handle (max_rhs > 1) is refused.
+int cedar_amd_solver_fcg_periodic(cedar_amd_solver *s, const real_t *b, real_t *x, const cedar_amd_pcg_settings *settings,
+                                  real_t *hist)
+{
+	const char *who = "cedar_amd_solver_fcg_periodic";
+	if (null_handle(s, who)) return -1;
+	const char *why = nullptr;
+	if (s->nb_alloc > 1) why = "handles of cedar_amd_solver_create_many with max_rhs > 1 are not supported";
+	else if (!b || !x) why = "b and x must not be NULL";
+	if (why) {
+		char msg[256];
+		snprintf(msg, sizeof(msg), "%s: %s; nothing done", who, why);
+		print_error(msg);
+		return -1;
+	}
+	if (s->st.ibc == 0) return cedar_amd_solver_fcg(s, b, x, settings, hist);
+	const cedar_amd_pcg_settings p = pcg_settings_or_default(settings);
+	if (fcg_refused(s, p, who, true)) return -1;
+	return pcg_run(s, 1, b, x, p, hist, nullptr, who, p.precon == CEDAR_AMD_PCG_PRECON_BMG);
 }
 
 void cedar_amd_solver_precondition(cedar_amd_solver *s, real_t *z, const real_t *r)

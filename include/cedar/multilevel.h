@@ -137,6 +137,10 @@ public:
 	// flexible conjugate gradients (cedar_amd_solver_fcg): pcg with the Polak-Ribiere beta, so any cycle of the solver --
 	// V(m,n), an F-cycle, plane relaxation -- may be the preconditioner.  The same pcg.* keys, `history` as after pcg().
 	void fcg(const grid_func & b, grid_func & x) { krylov(cedar_amd_solver_fcg, "fcg", b, x); }
+	// fcg on a solver with periodic directions (grid.periodic; cedar_amd_solver_fcg_periodic): the operator pass wraps
+	// around, the ghost layers of b and x do not matter, x comes back with the periodic image in its ghosts.  A solver
+	// without periodic directions is served as by fcg().  The same pcg.* keys, `history` as after pcg().
+	void fcg_periodic(const grid_func & b, grid_func & x) { krylov(cedar_amd_solver_fcg_periodic, "fcg_periodic", b, x); }
 
 	// several right-hand sides in lockstep on the one hierarchy (cedar_amd_solver_solve_many; room for them is made with
 	// the key solver.max-rhs).  histories[m] / iterations[m]: item m's residual history cut to the cycles run and the

@@ -337,6 +337,18 @@ enum { CEDAR_AMD_PCG_RHO = 0, CEDAR_AMD_PCG_SIGMA = 1, CEDAR_AMD_PCG_ALPHA = 2, 
  * cedar_amd_relax3_prepare is read through its row-interleaved copy where it has one, as the solvers do. */
 int cedar_amd_pcg_direction(const real_t *so, const real_t *z, const real_t *p, real_t *pn, real_t *w, len_t ii, len_t jj,
                             len_t kk, int nstncl, int first, real_t *sc, real_t *partial);
+/* The same pass on a level with periodic directions, as cedar_amd_solver_fcg_periodic launches it.  ibc: the boundary code
+ * of cedar_amd_settings (2D 1 = y, 2 = x, 3 = xy; 3D also 5 = z, 6 = xz, 7 = yz, 8 = xyz).  In a periodic direction a
+ * stencil neighbour on the ghost layer is read at the opposite interior end (index 0 -> extent - 2, extent - 1 -> 1; edge
+ * and corner neighbours in every combination): w is cedar_amd_matvec2 / 3 of pn with those ghosts wrapped, bit for bit,
+ * and NO ghost cell of z or p in a periodic direction contributes to any result.  Ghosts of the other directions are read
+ * as above.  The
+ * operator is read where cedar_amd_pcg_direction reads it: its ghost layers must hold the periodic image, as the periodic
+ * cycle requires.  A 27-point operator is read from its Cedar planes (a periodic level keeps no row-interleaved copy).
+ * Everything else -- pn and w written in the interior only, the NaN-filled slab, sc, partial, the return values -- is
+ * cedar_amd_pcg_direction's; ibc = 0 forwards to it; an ibc the dimension does not define is refused (-1). */
+int cedar_amd_pcg_direction_periodic(const real_t *so, const real_t *z, const real_t *p, real_t *pn, real_t *w, len_t ii,
+                                     len_t jj, len_t kk, int nstncl, int ibc, int first, real_t *sc, real_t *partial);
 /* move != 0: x += alpha p, r -= alpha w with alpha = sc[ALPHA] (alpha = 0, the breakdown value: x and r are not touched,
  * whatever p and w hold); then r.r and r.z by zmode: 0 z = r (r.z = r.r), 1 z = r / diag written here (diag: the
  * operator's centre plane), 2 z read, 3 r.r only.  partial == NULL: sc[RR] = r.r and, unless zmode 3, sc[RZ] = r.z,
@@ -459,9 +471,27 @@ void cedar_amd_solver_precondition(cedar_amd_solver *s, real_t *z, const real_t 
  * any plane sweep counts, handles switched by cedar_amd_solver_use_fp32_operator (the recurrence keeps the FP64
  * operator).  precon = 1 | 2 (M exactly symmetric) run cedar_amd_solver_pcg itself: its results bit for bit.
  * Same settings, hist, return value, stop tests, breakdown rules and storage as cedar_amd_solver_pcg.  Refused
- * (print_error, -1, nothing written): a NULL handle, ibc != 0, stop_test or precon out of range, max_iter < 0, and with
- * precon = 3 nmg_cycles < 1 or a cycle without any relaxation sweep. */
+ * (print_error, -1, nothing written): a NULL handle, ibc != 0 (see cedar_amd_solver_fcg_periodic), stop_test or precon
+ * out of range, max_iter < 0, and with precon = 3 nmg_cycles < 1 or a cycle without any relaxation sweep. */
 int cedar_amd_solver_fcg(cedar_amd_solver *s, const real_t *b, real_t *x, const cedar_amd_pcg_settings *p, real_t *hist);
+/* Flexible CG on a periodic handle (ibc != 0): every configuration cedar_amd_solver_create accepts with periodic
+ * boundaries -- 2D point and line relaxation, 3D point relaxation, V(m,n) with m + n >= 1, F-cycles -- with precon 1, 2, 3
+ * and all four stop tests.  The periodic cycle is not a symmetric operator (its coarsest solve removes the mean, its
+ * sweeps are ordered with the ghost refreshes: |<Mu,v> - <u,Mv>| / |<Mu,v>| is a few per cent even for V(1,1), DESIGN.md
+ * section 19), so the standard beta is not offered with it: precon = 3 runs the flexible beta, precon = 1 | 2 (M exactly
+ * symmetric) the standard one, as cedar_amd_solver_fcg does.  The operator pass wraps its own reads
+ * (cedar_amd_pcg_direction_periodic); there is no ghost refresh between the Krylov passes.
+ * The ghost layers of the caller's x and b do not influence the result: x gets the periodic image in its ghost layers
+ * before the first residual, and carries it on return, like x after cedar_amd_solver_solve.  The operator given to
+ * cedar_amd_solver_create holds the periodic image in its ghost layers, as for the cycle.
+ * The operator must be definite, as for the cycle itself: a fully periodic operator with zero row sums (the pure
+ * Laplacian) is singular, the coarsest factorisation fails on it, and such problems are not served.
+ * A handle with ibc = 0 forwards to cedar_amd_solver_fcg (results bit for bit, refusals its own).  Refused (print_error,
+ * -1, nothing written): a NULL handle, b or x NULL, a handle of cedar_amd_solver_create_many that holds more than one
+ * right-hand side, and the settings cedar_amd_solver_fcg refuses.  cedar_amd_solver_pcg, _fcg, _precondition and the
+ * batch calls keep refusing ibc != 0. */
+int cedar_amd_solver_fcg_periodic(cedar_amd_solver *s, const real_t *b, real_t *x, const cedar_amd_pcg_settings *p,
+                                  real_t *hist);
 
 /* Keep the 27-point operator of the cycle in single precision (3D, Dirichlet, point relaxation).  Every smoothed
  * 27-point level (all but the coarsest) with at least min_rows rows gets a row-interleaved copy of A and 1/diag rounded
