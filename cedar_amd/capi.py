@@ -424,6 +424,55 @@ class Kernels:
                    lib.cedar_amd_interp_add3_many(n if nrhs is None else nrhs, _p(q), _p(qc), _p(so), _p(res), _p(ci), u(IIC), u(JJC), u(KKC),
                                                   u(II), u(JJ), u(KK), so.shape[0]))
 
+    # ---- the batched periodic 3D kernels (periodic_many3d.hip, krylov.hip): the arguments of the Dirichlet _many methods
+    # plus the boundary code ibc (1..3, 5..8; 0 forwards to the Dirichlet call).  Item m gets the bits of the single-vector
+    # periodic drop-in on item m alone.  RuntimeError when the library refuses (nothing written)
+    def relax3_periodic_many(self, so, qf, q, sor, updown, ibc, ghosts_consistent=0, nrhs=None):
+        """ghosts_consistent: the y ghost rows of q hold the periodic image on entry (lets a y-periodic 27-point sweep take
+        the row-class path); 0 is always correct"""
+        nst, KK, JJ, II = so.shape
+        assert qf.shape == q.shape and tuple(q.shape[1:]) == (KK, JJ, II)
+        self._many("cedar_amd_relax3_gs_periodic_many",
+                   lib.cedar_amd_relax3_gs_periodic_many(q.shape[0] if nrhs is None else nrhs, _p(so), _p(qf), _p(q), _p(sor), u(II),
+                                                         u(JJ), u(KK), nst, updown, int(ibc), int(ghosts_consistent)))
+
+    def restrict3_periodic_many(self, q, qc, ci, ibc, nrhs=None):
+        """the ghosts of the fine vectors are refreshed first: q is written too"""
+        n, KK, JJ, II = q.shape
+        nc, KKC, JJC, IIC = qc.shape
+        assert n == nc
+        self._many("cedar_amd_restrict3_periodic_many",
+                   lib.cedar_amd_restrict3_periodic_many(n if nrhs is None else nrhs, _p(q), _p(qc), _p(ci), u(II), u(JJ), u(KK),
+                                                         u(IIC), u(JJC), u(KKC), int(ibc)))
+
+    def interp_add3_periodic_many(self, q, qc, so, res, ci, ibc, nrhs=None):
+        n, KK, JJ, II = q.shape
+        nc, KKC, JJC, IIC = qc.shape
+        assert n == nc and res.shape == q.shape
+        self._many("cedar_amd_interp_add3_periodic_many",
+                   lib.cedar_amd_interp_add3_periodic_many(n if nrhs is None else nrhs, _p(q), _p(qc), _p(so), _p(res), _p(ci), u(IIC),
+                                                           u(JJC), u(KKC), u(II), u(JJ), u(KK), so.shape[0], int(ibc)))
+
+    def solve_cg3_periodic_many(self, q, qf, abd, ibc, nrhs=None):
+        """abd: the dense factor setup_cg3(so, abd, ibc) left, shared by the items; one workgroup per item"""
+        n, KK, JJ, II = q.shape
+        assert qf.shape == q.shape
+        n = n if nrhs is None else nrhs
+        bbd = np.zeros(max(n, 1) * abd.shape[0])
+        self._many("cedar_amd_solve_cg3_periodic_many",
+                   lib.cedar_amd_solve_cg3_periodic_many(n, _p(q), _p(qf), u(II), u(JJ), u(KK), _p(abd), _p(bbd), u(abd.shape[1]),
+                                                         int(ibc)))
+
+    def pcg_direction_periodic_many(self, so, z, p, pn, w, ibc, first, sc, nrhs=None, active=None):
+        """pcg_direction_many on a periodic 3D level: per item m the reads of pcg_direction_periodic"""
+        assert tuple(so.shape[1:]) == tuple(z.shape[1:]) and all(a is None or a.shape == z.shape for a in (p, pn, w))
+        n, act = self._batch(z, sc, nrhs, active)
+        grid = z.shape[1:]
+        if lib.cedar_amd_pcg_direction_periodic_many(n, act, _p(so), _p(z), _p(p), _p(pn), _p(w), u(grid[-1]), u(grid[-2]),
+                                                     u(grid[0] if len(grid) == 3 else 1), so.shape[0], int(ibc), int(first),
+                                                     _p(sc)) != 0:
+            raise RuntimeError("cedar_amd_pcg_direction_periodic_many refused")
+
     # ---- the transfers on the interpolation weights rounded to single precision (transferf.hip): a float copy of ci is built
     # for the call; arguments as the FP64 methods above (Dirichlet).  0 when served, non-zero when refused (nothing written)
     def restrict2_ci32(self, q, qc, ci):
@@ -579,6 +628,8 @@ lib.cedar_amd_solver_time_vcycles_many.restype = C.c_float
 lib.cedar_amd_solver_time_vcycles_many.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
 for _f in (lib.cedar_amd_relax3_gs_many, lib.cedar_amd_residual3_many, lib.cedar_amd_restrict3_many, lib.cedar_amd_interp_add3_many):
     _f.restype = C.c_int
+lib.cedar_amd_solver_create_many_periodic.restype = C.c_void_p
+lib.cedar_amd_solver_create_many_periodic.argtypes = lib.cedar_amd_solver_create_many.argtypes
 
 
 def _vp(a):
@@ -632,6 +683,8 @@ lib.cedar_amd_solver_fcg_many.restype = C.c_int
 lib.cedar_amd_solver_fcg_many.argtypes = lib.cedar_amd_solver_pcg_many.argtypes
 lib.cedar_amd_solver_fcg_periodic.restype = C.c_int
 lib.cedar_amd_solver_fcg_periodic.argtypes = lib.cedar_amd_solver_pcg.argtypes
+lib.cedar_amd_solver_fcg_periodic_many.restype = C.c_int
+lib.cedar_amd_solver_fcg_periodic_many.argtypes = lib.cedar_amd_solver_pcg_many.argtypes
 lib.cedar_amd_solver_use_fp32_operator.restype = C.c_int
 lib.cedar_amd_solver_use_fp32_operator.argtypes = [C.c_void_p, C.c_int]
 lib.cedar_amd_solver_use_fp32_operator_many.restype = C.c_int
@@ -657,7 +710,8 @@ class Solver:
     """cedar::cdr2::solver / cdr3::solver on the device (include/cedar_amd.h, handle API)."""
 
     def __init__(self, so, relax="point", nrelax_pre=2, nrelax_post=1, num_levels=-1,
-                 max_iter=10, tol=1e-8, min_coarse=3, share_operator=False, cycle="v", ibc=0, plane=None, max_rhs=1):
+                 max_iter=10, tol=1e-8, min_coarse=3, share_operator=False, cycle="v", ibc=0, plane=None, max_rhs=1,
+                 periodic_batch=False):
         shp = so.shape
         self.nd = len(shp) - 1
         nst = shp[0]
@@ -669,7 +723,10 @@ class Solver:
         plane_settings(st, plane)
         self.max_iter = max_iter
         self._so = so if share_operator else None  # keep the shared operator alive
-        if max_rhs == 1:
+        if periodic_batch:  # a periodic 3D handle with room for max_rhs right-hand sides (ibc = 0: as max_rhs alone)
+            self.h = lib.cedar_amd_solver_create_many_periodic(self.nd, nx, ny, nz, nst, _vp(so), int(share_operator),
+                                                               C.byref(st), int(max_rhs))
+        elif max_rhs == 1:
             self.h = lib.cedar_amd_solver_create(self.nd, nx, ny, nz, nst, _vp(so), int(share_operator), C.byref(st))
         else:  # room for max_rhs right-hand sides on every level (vcycle_many / solve_many)
             self.h = lib.cedar_amd_solver_create_many(self.nd, nx, ny, nz, nst, _vp(so), int(share_operator), C.byref(st),
@@ -795,6 +852,11 @@ class Solver:
     def fcg_many(self, b, x, max_iter=50, tol=1e-8, stop="rel_l2", precon="mg", nmg_cycles=1, hist=None):
         """fcg for the items of b, x in lockstep (cedar_amd_solver_fcg_many); same arguments and return as pcg_many"""
         return self._cg_many("cedar_amd_solver_fcg_many", b, x, max_iter, tol, stop, precon, nmg_cycles, hist)
+
+    def fcg_periodic_many(self, b, x, max_iter=50, tol=1e-8, stop="rel_l2", precon="mg", nmg_cycles=1, hist=None):
+        """fcg_periodic for the items of b, x in lockstep on a handle made with periodic_batch=True
+        (cedar_amd_solver_fcg_periodic_many); same arguments and return as fcg_many"""
+        return self._cg_many("cedar_amd_solver_fcg_periodic_many", b, x, max_iter, tol, stop, precon, nmg_cycles, hist)
 
     def precondition(self, z, r):
         """z = M^-1 r: one cycle from z = 0 (cedar_amd_solver_precondition)"""

@@ -1236,6 +1236,98 @@ int cedar_amd_interp_add3_many(int nrhs, real_t *q, real_t *qc, real_t *so, real
 	return 0;
 }
 
+// ------------------------------------------------------------------ the batched periodic 3D kernels (periodic_many3d.hip,
+// krylov.hip), one launcher each: nrhs items back to back, the operator arrays shared; ibc = 0 forwards to the Dirichlet
+// call where one exists
+static bool per_many_refused(int nrhs, bool arrays_ok, bool nst_ok, int ibc, const char *who)
+{
+	if (many_args_refused(nrhs, arrays_ok, nst_ok, who)) return true;
+	if (ibc >= 0 && periodic3_code_ok(ibc)) return false;
+	char msg[200];
+	snprintf(msg, sizeof(msg), "%s: boundary code %d is not a 3D code (0, 1..3, 5..8); nothing done", who, ibc);
+	print_error(msg);
+	return true;
+}
+
+int cedar_amd_relax3_gs_periodic_many(int nrhs, real_t *so, real_t *qf, real_t *q, real_t *sor, len_t ii, len_t jj, len_t kk,
+                                      int nstncl, int updown, int ibc, int ghosts_consistent)
+{
+	if (per_many_refused(nrhs, so && qf && q && sor, nstncl == 4 || nstncl == 14, ibc, "cedar_amd_relax3_gs_periodic_many")) return -1;
+	if (ibc == 0) return cedar_amd_relax3_gs_many(nrhs, so, qf, q, sor, ii, jj, kk, nstncl, updown);
+	const size_t P = (size_t)ii * jj * kk;
+	Staged sso(so, P * nstncl, true, false), sqf(qf, P * nrhs, true, false), sq(q, P * nrhs, true, true), ssor(sor, P * 2, true, false);
+	relax3_gs_per_many(sso.get(), sqf.get(), sq.get(), ssor.get(), (int)ii, (int)jj, (int)kk, nstncl, updown, ibc, current_stream(),
+	                   ghosts_consistent, Batch{nrhs, P});
+	return 0;
+}
+
+// the fine vectors get their ghosts refreshed first, so q is an output too
+int cedar_amd_restrict3_periodic_many(int nrhs, real_t *q, real_t *qc, real_t *ci, len_t ii, len_t jj, len_t kk, len_t iic,
+                                      len_t jjc, len_t kkc, int ibc)
+{
+	if (per_many_refused(nrhs, q && qc && ci, true, ibc, "cedar_amd_restrict3_periodic_many")) return -1;
+	if (ibc == 0) return cedar_amd_restrict3_many(nrhs, q, qc, ci, ii, jj, kk, iic, jjc, kkc);
+	const size_t P = (size_t)ii * jj * kk, PC = (size_t)iic * jjc * kkc;
+	Staged sq(q, P * nrhs, true, true), sqc(qc, PC * nrhs, true, true), sci(ci, PC * 26, true, false);
+	restrict3_per_many(sq.get(), sqc.get(), sci.get(), (int)ii, (int)jj, (int)kk, (int)iic, (int)jjc, (int)kkc, ibc,
+	                   current_stream(), Batch{nrhs, P}, Batch{nrhs, PC});
+	return 0;
+}
+
+int cedar_amd_interp_add3_periodic_many(int nrhs, real_t *q, real_t *qc, real_t *so, real_t *res, real_t *ci, len_t iic,
+                                        len_t jjc, len_t kkc, len_t iif, len_t jjf, len_t kkf, int nstncl, int ibc)
+{
+	if (per_many_refused(nrhs, q && qc && so && res && ci, nstncl == 4 || nstncl == 14, ibc, "cedar_amd_interp_add3_periodic_many"))
+		return -1;
+	if (ibc == 0) return cedar_amd_interp_add3_many(nrhs, q, qc, so, res, ci, iic, jjc, kkc, iif, jjf, kkf, nstncl);
+	const size_t P = (size_t)iif * jjf * kkf, PC = (size_t)iic * jjc * kkc;
+	Staged sq(q, P * nrhs, true, true), sqc(qc, PC * nrhs, true, false), sso(so, P * nstncl, true, false),
+	    sr(res, P * nrhs, true, true), sci(ci, PC * 26, true, false);
+	interp_add3_per_many(sq.get(), sqc.get(), sso.get(), sr.get(), sci.get(), (int)iic, (int)jjc, (int)kkc, (int)iif, (int)jjf,
+	                     (int)kkf, ibc, current_stream(), Batch{nrhs, P}, Batch{nrhs, PC});
+	return 0;
+}
+
+// abd: the dense factor of BMG3_SymStd_SETUP_cg_LU with a periodic code, nabd1 >= the number of unknowns; bbd: nrhs
+// segments of that many doubles.  There is no batched Dirichlet coarsest solve behind a kernel-level call: ibc = 0 is refused
+int cedar_amd_solve_cg3_periodic_many(int nrhs, real_t *q, real_t *qf, len_t ii, len_t jj, len_t kk, real_t *abd, real_t *bbd,
+                                      len_t nabd1, int ibc)
+{
+	const char *who = "cedar_amd_solve_cg3_periodic_many";
+	if (per_many_refused(nrhs, q && qf && abd && bbd, true, ibc, who)) return -1;
+	const size_t N = ii >= 3 && jj >= 3 && kk >= 3 ? (size_t)(ii - 2) * (jj - 2) * (kk - 2) : 0;
+	if (ibc == 0 || N == 0 || N > 2048 || (size_t)nabd1 < N) {
+		char msg[200];
+		snprintf(msg, sizeof(msg), "%s: needs a periodic code, 1 .. 2048 unknowns and the dense factor ABD(n,n); nothing done", who);
+		print_error(msg);
+		return -1;
+	}
+	const size_t P = (size_t)ii * jj * kk;
+	Staged sq(q, P * nrhs, true, true), sqf(qf, P * nrhs, true, false), sabd(abd, (size_t)nabd1 * N, true, false),
+	    sb(bbd, N * nrhs, false, true);
+	solve_cg3_per_many(sq.get(), sqf.get(), (int)ii, (int)jj, (int)kk, sabd.get(), sb.get(), (int)nabd1, ibc, current_stream(),
+	                   Batch{nrhs, P});
+	return 0;
+}
+
+// the direction pass of a periodic 3D level on nrhs items; every item's slab NaN-filled
+int cedar_amd_pcg_direction_periodic_many(int nrhs, unsigned active, const real_t *so, const real_t *z, const real_t *p,
+                                          real_t *pn, real_t *w, len_t ii, len_t jj, len_t kk, int nstncl, int ibc, int first,
+                                          real_t *sc)
+{
+	const char *who = "cedar_amd_pcg_direction_periodic_many";
+	if (per_many_refused(nrhs, so && z && pn && w && sc && (first || p), nstncl == 4 || nstncl == 14, ibc, who)) return -1;
+	if (ibc == 0) return cedar_amd_pcg_direction_many(nrhs, active, so, z, p, pn, w, ii, jj, kk, nstncl, first, sc);
+	if (kk == 1 || pcg_shape_refused(ii, jj, kk, who)) return kk == 1 ? (pcg_refuse(who, "3D only"), -1) : -1;
+	const size_t P = (size_t)ii * jj * kk, N = P * nrhs;
+	NanSlab slab(pcg_slab_doubles(3, nstncl, (int)ii, (int)jj, (int)kk) * nrhs);
+	Staged sso(so, P * nstncl, true, false), sz(z, N, true, false), sp(first ? nullptr : p, N, true, false),
+	    spn(pn, N, true, true), sw(w, N, true, true), ssc(sc, (size_t)PCG_NSC * nrhs, true, true);
+	pcg_direction_periodic_many(sso.get(), sz.get(), sp.get(), spn.get(), sw.get(), nstncl, (int)ii, (int)jj, (int)kk, ibc,
+	                            first != 0, slab.dev, ssc.get(), current_stream(), Batch{nrhs, P}, active);
+	return 0;
+}
+
 // ------------------------------------------------------------------ transfers on single-precision weights
 int cedar_amd_restrict2_ci32(real_t *q, real_t *qc, real_t *ci, int ii, int jj, int iic, int jjc)
 {

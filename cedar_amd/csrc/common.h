@@ -301,8 +301,8 @@ void solve_cg2_per(real_t *q, const real_t *qf, int II, int JJ, const real_t *ab
 // 3D periodic boundary conditions (periodic3d.hip, relax3d.hip); ipn = 1 y, 2 x, 3 xy, 5 z, 6 xz, 7 yz, 8 xyz
 bool periodic3_code_ok(int ipn);
 void wrap3(real_t *a, int II, int JJ, int KK, int narrays, int ipn, hipStream_t st);
-void wrap3_colour(real_t *q, int II, int JJ, int KK, int jb, int kb, int ipn, hipStream_t st);
-void wrap3_sweep_end(real_t *q, int II, int JJ, int KK, int ipn, hipStream_t st);
+void wrap3_colour(real_t *q, int II, int JJ, int KK, int jb, int kb, int ipn, hipStream_t st, int narrays = 1);
+void wrap3_sweep_end(real_t *q, int II, int JJ, int KK, int ipn, hipStream_t st, int narrays = 1);
 void relax3_gs_per(const real_t *so, const real_t *qf, real_t *q, const real_t *sor,
                    int II, int JJ, int KK, int nstncl, int updown, int ipn, hipStream_t st, int ghosts_consistent = 0);
 void restrict3_per(real_t *q, real_t *qc, const real_t *ci, int II, int JJ, int KK, int IIC, int JJC, int KKC, int ipn,
@@ -313,7 +313,8 @@ void setup_interp3_per(const real_t *so, real_t *ci, int IIF, int JJF, int KKF, 
                        hipStream_t st);
 void galerkin3_per(const real_t *so, real_t *soc, const real_t *ci, int IIF, int JJF, int KKF, int IIC, int JJC, int KKC,
                    int ifd, int ipn, hipStream_t st);
-void setup_cg3_per(const real_t *so, int II, int JJ, int KK, real_t *abd, int nabd1, int ipn, int *info, hipStream_t st);
+void setup_cg3_per(const real_t *so, int II, int JJ, int KK, real_t *abd, int nabd1, int ipn, int *info, hipStream_t st,
+                   int nst = 14); // nst: slots of so, 4 for a one-level seven-point handle
 void solve_cg3_per(real_t *q, const real_t *qf, int II, int JJ, int KK, const real_t *abd, real_t *bbd, int nabd1, int ipn,
                    hipStream_t st);
 // plane relaxation, the 3D side (planes.hip); dir 0 xy, 1 xz, 2 yz; stacked 2D arrays, slot q = plane beg + 2q
@@ -466,6 +467,10 @@ void pcg_update(int zmode, bool move, real_t *x, real_t *r, const real_t *p, con
 void pcg_direction_many(const real_t *so, const Op3 *op27, const real_t *z, const real_t *p, real_t *pn, real_t *w, int nd,
                         int nst, int II, int JJ, int KK, bool first, real_t *slab, real_t *sc, hipStream_t st, Batch bt,
                         unsigned active);
+// the direction pass of a periodic 3D level on a batch: pcg_direction_periodic per item, the operator fetched once
+void pcg_direction_periodic_many(const real_t *so, const real_t *z, const real_t *p, real_t *pn, real_t *w, int nst, int II,
+                                 int JJ, int KK, int ibc, bool first, real_t *slab, real_t *sc, hipStream_t st, Batch bt,
+                                 unsigned active);
 void pcg_update_many(int zmode, bool move, real_t *x, real_t *r, const real_t *p, const real_t *w, real_t *z,
                      const real_t *diag, int II, int JJ, int KK, bool first, real_t *slab, real_t *sc, hipStream_t st,
                      Batch bt, unsigned active);
@@ -506,6 +511,21 @@ void restrict3_many(const real_t *q, real_t *qc, const real_t *ci, int II, int J
                     hipStream_t st, Batch bf, Batch bc);
 void interp_add3_many(real_t *q, const real_t *qc, const real_t *so, real_t *res, const real_t *ci,
                       int IIC, int JJC, int KKC, int IIF, int JJF, int KKF, hipStream_t st, Batch bf, Batch bc);
+// one row class / one colour of the two batched sweeps (the periodic batch refreshes ghosts in between)
+void relax3_class27_many(const Op3 &A, const real_t *qf, real_t *q, int II, int JJ, int KK, int jb, int kb, bool efirst,
+                         hipStream_t st, Batch bt);
+void relax3_colour7_many(const real_t *so, const real_t *qf, real_t *q, const real_t *sor, int II, int JJ, int KK, int pts,
+                         hipStream_t st, Batch bt);
+// periodic_many3d.hip: the periodic 3D kernels on a batch stored with stride II*JJ*KK (ipn as above).  Item m of every
+// result has the bits of the single-vector periodic call on item m alone.  bbd: bt.n segments of one coarsest vector
+void relax3_gs_per_many(const real_t *so, const real_t *qf, real_t *q, const real_t *sor, int II, int JJ, int KK, int nstncl,
+                        int updown, int ipn, hipStream_t st, int ghosts_consistent, Batch bt);
+void restrict3_per_many(real_t *q, real_t *qc, const real_t *ci, int II, int JJ, int KK, int IIC, int JJC, int KKC, int ipn,
+                        hipStream_t st, Batch bf, Batch bc);
+void interp_add3_per_many(real_t *q, const real_t *qc, const real_t *so, real_t *res, const real_t *ci, int IIC, int JJC,
+                          int KKC, int IIF, int JJF, int KKF, int ipn, hipStream_t st, Batch bf, Batch bc);
+void solve_cg3_per_many(real_t *q, const real_t *qf, int II, int JJ, int KK, const real_t *abd, real_t *bbd, int nabd1, int ipn,
+                        hipStream_t st, Batch bt);
 // gallery.hip (device-side generators of the reference's gallery operators)
 void gallery_fill(int which, real_t *so, real_t *b, int nx, int ny, int nz, const double *params, hipStream_t st);
 

@@ -794,6 +794,167 @@ __global__ __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(2))) void pc
 	}
 }
 
+// ---------------------------------------------------------------- the direction pass of a periodic level on a batch
+// (cedar_amd_solver_fcg_periodic_many): the wrap rule of pcg_dir7_per / pcg_dir27_per -- a neighbour index on a periodic
+// ghost layer is read at the opposite interior end -- with the item loop of pcg_dir7_many / pcg_dir27_many.  Per item the
+// expressions, their order and the sums are those of the single-vector periodic kernels: item m's pn, w and slab have the
+// bits of pcg_direction_periodic on item m alone.
+template <bool FIRST>
+__global__ __launch_bounds__(256) void pcg_dir7_per_many(const real_t *__restrict__ so, const real_t *__restrict__ z,
+                                                         const real_t *__restrict__ p, real_t *__restrict__ pn,
+                                                         real_t *__restrict__ w, const real_t *__restrict__ sc, int II, int JJ,
+                                                         int KK, unsigned nrows, PerDirs pd, real_t *__restrict__ part, int nrhs,
+                                                         size_t stride, unsigned active)
+{
+	__shared__ real_t lds[4];
+	__shared__ real_t accl[ITEM_CHUNK][256];
+	const unsigned L = xcd_remap(blockIdx.x, nrows);
+	if (L >= nrows) return; // grid padding of xcd_grid: no slab entry
+	const int m0 = ITEM_CHUNK * (int)blockIdx.y, nitems = min(ITEM_CHUNK, nrhs - m0);
+	const int j = (int)(L % (unsigned)(JJ - 2)) + 1, k = (int)(L / (unsigned)(JJ - 2)) + 1;
+	const size_t sj = II, sk = (size_t)II * JJ, PS = sk * KK;
+	const size_t row = sj * (size_t)j + sk * (size_t)k;
+	// the four neighbour rows, wrapped (uniform over the workgroup)
+	const size_t rs = sj * (size_t)wrap_lo(j - 1, JJ, pd.y) + sk * (size_t)k, rn = sj * (size_t)wrap_hi(j + 1, JJ, pd.y) + sk * (size_t)k;
+	const size_t rb = sj * (size_t)j + sk * (size_t)wrap_lo(k - 1, KK, pd.z), rt = sj * (size_t)j + sk * (size_t)wrap_hi(k + 1, KK, pd.z);
+	for (int t = 0; t < nitems; t++) accl[t][threadIdx.x] = 0.0;
+	for (int i = threadIdx.x + 1; i <= II - 2; i += blockDim.x) {
+		const size_t x = row + (size_t)i;
+		const size_t xw = row + (size_t)wrap_lo(i - 1, II, pd.x), xe = row + (size_t)wrap_hi(i + 1, II, pd.x);
+		const real_t cp = so[KP * PS + x], cw = so[KPW * PS + x], cn = so[KPS * PS + x + sj], ce = so[KPW * PS + x + 1];
+		const real_t cs = so[KPS * PS + x], cb = so[KB * PS + x], ct = so[KB * PS + x + sk];
+#pragma unroll 1
+		for (int t = 0; t < nitems; t++) {
+			const int m = m0 + t;
+			if (!item_on(active, m)) continue;
+			const size_t off = (size_t)m * stride;
+			const real_t *__restrict__ zm = z + off, *__restrict__ pm = FIRST ? zm : p + off;
+			const real_t beta = FIRST ? 0.0 : sc[(size_t)m * PCG_NSC + PCG_BETA];
+			auto P = [&](size_t y) -> real_t { return FIRST ? zm[y] : zm[y] + beta * pm[y]; };
+			const real_t pc = P(x);
+			real_t s = cp * pc;
+			s = s - cw * P(xw);
+			s = s - cn * P(rn + (size_t)i);
+			s = s - ce * P(xe);
+			s = s - cs * P(rs + (size_t)i);
+			s = s - cb * P(rb + (size_t)i);
+			s = s - ct * P(rt + (size_t)i);
+			pn[off + x] = pc;
+			w[off + x] = s;
+			accl[t][threadIdx.x] += pc * s;
+		}
+	}
+	for (int t = 0; t < nitems; t++) {
+		const int m = m0 + t;
+		if (!item_on(active, m)) continue; // uniform over the workgroup
+		const real_t v = block_sum_k<256>(accl[t][threadIdx.x], lds);
+		if (threadIdx.x == 0) part[(size_t)m * nrows + L] = v;
+	}
+}
+
+// 27-point, rows of one trip (longer rows: pcg_dir27_per item by item, pcg_direction_periodic_many).  The 52 coefficients
+// and the diagonal pair are fetched once, from the Cedar planes (a periodic level has no row-interleaved copy), and stay
+// in registers across the items; one window set is live at a time.  Per item the nine window rows are loaded as
+// pcg_dir27_per loads them, every load before any patch; the i patch follows under the uniform `if (pd.x)`.
+template <int BS, bool FIRST>
+__global__ __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(2))) void pcg_dir27_per_many(
+    const Op3 A, const real_t *__restrict__ z, const real_t *__restrict__ p, real_t *__restrict__ pn, real_t *__restrict__ w,
+    const real_t *__restrict__ sc, int II, int JJ, int KK, unsigned nblk, TileShape ts, PerDirs pd, real_t *__restrict__ part,
+    int nrhs, size_t stride, unsigned active)
+{
+	__shared__ real_t lds[(BS + 63) / 64];
+	const unsigned L = xcd_remap(blockIdx.x, nblk);
+	if (L >= nblk) return; // grid padding: no slab entry
+	unsigned jr, kr;
+	const bool have = tile_rows(L, (unsigned)(JJ - 2), (unsigned)(KK - 2), ts, jr, kr);
+	const int q = threadIdx.x;
+	const bool mine = have && 2 * q + 1 <= II - 2;
+	const int ie = 2 * q + 1, io = 2 * q + 2;
+	const bool o_ok = io <= II - 2, two = io + 1 <= II - 1;
+	const int j = have ? (int)jr + 1 : 1, k = have ? (int)kr + 1 : 1;
+	const size_t sj = (size_t)II, sk = (size_t)II * JJ;
+	const size_t row = (size_t)j * sj + (size_t)k * sk, rowA = (size_t)j * A.SJ + (size_t)k * A.SK;
+	// the window rows (j-1, j, j+1) x (k-1, k, k+1), wrapped
+	const size_t oj[3] = {sj * (size_t)wrap_lo(j - 1, JJ, pd.y), sj * (size_t)j, sj * (size_t)wrap_hi(j + 1, JJ, pd.y)};
+	const size_t ok[3] = {sk * (size_t)wrap_lo(k - 1, KK, pd.z), sk * (size_t)k, sk * (size_t)wrap_hi(k + 1, KK, pd.z)};
+	C27 ce, co;
+	real_t de = 0.0, dn = 0.0;
+	if (mine) {
+		load_coef27<false, false, false>(A, rowA, ie, io, two, ce, co);
+		co.pw = ce.pw_e; // both are the operator entry (KPW, io): one register pair less across the item loop
+		ldpair(A.so + rowA + ie, true, de, dn); // KP plane
+	}
+#pragma unroll 1
+	for (int m = 0; m < nrhs; m++) {
+		if (!item_on(active, m)) continue; // uniform over the workgroup
+		real_t acc = 0.0;
+		if (mine) {
+			const size_t off = (size_t)m * stride;
+			const real_t *__restrict__ zm = z + off, *__restrict__ pm = FIRST ? zm : p + off;
+			const real_t beta = FIRST ? 0.0 : sc[(size_t)m * PCG_NSC + PCG_BETA];
+			real_t qe[3][3][3], qo[3][3][3];
+#pragma unroll
+			for (int dk = 0; dk < 3; dk++)
+#pragma unroll
+				for (int dj = 0; dj < 3; dj++) {
+					const size_t y = oj[dj] + ok[dk];
+					real_t w0, w1, w2, w3;
+					ldpair(zm + y + ie - 1, true, w0, w1);
+					ldpair(zm + y + io, two, w2, w3);
+					if (!FIRST) {
+						real_t p0, p1, p2, p3;
+						ldpair(pm + y + ie - 1, true, p0, p1);
+						ldpair(pm + y + io, two, p2, p3);
+						w0 = w0 + beta * p0;
+						w1 = w1 + beta * p1;
+						w2 = w2 + beta * p2;
+						w3 = w3 + beta * p3;
+					}
+					qe[dk][dj][0] = w0; qe[dk][dj][1] = w1; qe[dk][dj][2] = w2;
+					qo[dk][dj][0] = w1; qo[dk][dj][1] = w2; qo[dk][dj][2] = w3;
+				}
+			// periodic x (uniform branch): what was formed from a ghost of the row is replaced by the same expression at the
+			// wrapped address (pcg_dir27_per)
+			if (pd.x) {
+				auto P = [&](size_t y) -> real_t { return FIRST ? zm[y] : zm[y] + beta * pm[y]; };
+				if (ie == 1) {
+#pragma unroll
+					for (int dk = 0; dk < 3; dk++)
+#pragma unroll
+						for (int dj = 0; dj < 3; dj++) qe[dk][dj][0] = P(oj[dj] + ok[dk] + II - 2);
+				}
+				if (io + 1 >= II - 1) {
+#pragma unroll
+					for (int dk = 0; dk < 3; dk++)
+#pragma unroll
+						for (int dj = 0; dj < 3; dj++) {
+							const real_t v = P(oj[dj] + ok[dk] + 1);
+							if (two) qo[dk][dj][2] = v;
+							else qe[dk][dj][2] = v;
+						}
+				}
+			}
+			const real_t we = mv27(de, ce, qe);
+			const real_t pe = qe[1][1][1];
+			acc += pe * we;
+			if (o_ok) {
+				const real_t wo = mv27(dn, co, qo);
+				const real_t po = qo[1][1][1];
+				acc += po * wo;
+				d2u v; v.x = we; v.y = wo;
+				*reinterpret_cast<d2u *>(w + off + row + ie) = v;
+				v.x = pe; v.y = po;
+				*reinterpret_cast<d2u *>(pn + off + row + ie) = v;
+			} else {
+				w[off + row + ie] = we;
+				pn[off + row + ie] = pe;
+			}
+		}
+		const real_t t = block_sum_k<BS>(acc, lds);
+		if (threadIdx.x == 0) part[(size_t)m * nblk + L] = t;
+	}
+}
+
 // pcg_upd on the items m0 .. m0 + nitems-1 (m0 = ITEM_CHUNK * blockIdx.y): the same UPD_NB workgroups and row dealing, the
 // item loop inside the pair loop so that diag (ZM 1) is read once per pair.  A lane's r.r / r.z of an item run over all
 // the rows dealt to the workgroup: LDS columns (lane-private), summed per item as pcg_upd sums rr and rz.  Item m's slab:
@@ -1105,6 +1266,43 @@ void pcg_direction_many(const real_t *so, const Op3 *op27, const real_t *z, cons
 		const TileShape ts = tile_shape_resid();
 		n = tile_blocks((unsigned)(JJ - 2), (unsigned)(KK - 2), ts);
 #define L27_(BS, F) hipLaunchKernelGGL((pcg_dir27_many<BS, F>), dim3(xcd_grid(n)), dim3(BS), 0, st, A, z, p, pn, w, sc, II, JJ, KK, n, ts, slab, bt.n, bt.stride, active)
+		if (npairs <= 64) { if (first) L27_(64, true); else L27_(64, false); }
+		else if (npairs <= 128) { if (first) L27_(128, true); else L27_(128, false); }
+		else { if (first) L27_(256, true); else L27_(256, false); }
+#undef L27_
+	}
+	hipLaunchKernelGGL(pcg_alpha_many, dim3(bt.n), dim3(RED_BS), 0, st, slab, n, (size_t)n, sc, active);
+}
+
+// pcg_direction_many's launch geometry, slab layout and second stage with the wrap-around kernels (3D; a periodic level is
+// read from its Cedar planes)
+void pcg_direction_periodic_many(const real_t *so, const real_t *z, const real_t *p, real_t *pn, real_t *w, int nst, int II,
+                                 int JJ, int KK, int ibc, bool first, real_t *slab, real_t *sc, hipStream_t st, Batch bt,
+                                 unsigned active)
+{
+	const PerDirs pd = per_dirs(3, ibc);
+	const size_t ld = pcg_slab_doubles(3, nst, II, JJ, KK); // item stride of the slab
+	const unsigned chunks = (unsigned)((bt.n + ITEM_CHUNK - 1) / ITEM_CHUNK);
+	unsigned n = 0;
+	if (nst == 4) {
+		n = (unsigned)(JJ - 2) * (unsigned)(KK - 2);
+		const int bs = II - 2 >= 256 ? 256 : (II - 2 > 64 ? 128 : 64);
+		const dim3 grid(xcd_grid(n), chunks);
+		if (first) hipLaunchKernelGGL(pcg_dir7_per_many<true>, grid, dim3(bs), 0, st, so, z, p, pn, w, sc, II, JJ, KK, n, pd, slab, bt.n, bt.stride, active);
+		else hipLaunchKernelGGL(pcg_dir7_per_many<false>, grid, dim3(bs), 0, st, so, z, p, pn, w, sc, II, JJ, KK, n, pd, slab, bt.n, bt.stride, active);
+	} else {
+		const int npairs = (II - 2 + 1) / 2;
+		if (npairs > 256) { // rows of more than one trip: the single-vector pass item by item (its second stage included)
+			for (int m = 0; m < bt.n; m++)
+				if ((active >> m) & 1u)
+					pcg_direction_periodic(so, z + m * bt.stride, first ? nullptr : p + m * bt.stride, pn + m * bt.stride,
+					                       w + m * bt.stride, 3, nst, II, JJ, KK, ibc, first, slab + m * ld, sc + (size_t)m * PCG_NSC, st);
+			return;
+		}
+		const Op3 A = op3_cedar(so, nullptr, II, JJ, KK);
+		const TileShape ts = tile_shape_resid();
+		n = tile_blocks((unsigned)(JJ - 2), (unsigned)(KK - 2), ts);
+#define L27_(BS, F) hipLaunchKernelGGL((pcg_dir27_per_many<BS, F>), dim3(xcd_grid(n)), dim3(BS), 0, st, A, z, p, pn, w, sc, II, JJ, KK, n, ts, pd, slab, bt.n, bt.stride, active)
 		if (npairs <= 64) { if (first) L27_(64, true); else L27_(64, false); }
 		else if (npairs <= 128) { if (first) L27_(128, true); else L27_(128, false); }
 		else { if (first) L27_(256, true); else L27_(256, false); }

@@ -139,6 +139,18 @@ void relax3_gs27_many(const Op3 &A, const real_t *qf, real_t *q, int II, int JJ,
 	relax3_gs27_many_t(A, qf, q, II, JJ, KK, updown, st, bt);
 }
 
+// one row class (jb,kb) of that sweep on its own, rows of at most 512 pairs: the periodic batch refreshes ghosts between
+// the classes (periodic_many3d.hip)
+void relax3_class27_many(const Op3 &A, const real_t *qf, real_t *q, int II, int JJ, int KK, int jb, int kb, bool efirst,
+                         hipStream_t st, Batch bt)
+{
+	const int npairs = (II - 2 + 1) / 2;
+	if (npairs <= 64) launch_rows_many<64>(efirst, A, qf, q, II, JJ, KK, jb, kb, st, bt);
+	else if (npairs <= 128) launch_rows_many<128>(efirst, A, qf, q, II, JJ, KK, jb, kb, st, bt);
+	else if (npairs <= 256) launch_rows_many<256>(efirst, A, qf, q, II, JJ, KK, jb, kb, st, bt);
+	else launch_rows_many<512>(efirst, A, qf, q, II, JJ, KK, jb, kb, st, bt);
+}
+
 void relax3_gs27_many(const Op3f &A, const real_t *qf, real_t *q, int II, int JJ, int KK, int updown, hipStream_t st, Batch bt)
 {
 	relax3_gs27_many_t(A, qf, q, II, JJ, KK, updown, st, bt);
@@ -252,6 +264,14 @@ void relax3_gs7_many(const real_t *so, const real_t *qf, real_t *q, const real_t
 		const size_t n = (size_t)((II - 2 + 1) / 2) * (JJ - 2) * (KK - 2);
 		hipLaunchKernelGGL(relax7_colour_many, dim3(cap_grid(n, 256)), dim3(256), 0, st, so, qf, q, sor, II, JJ, KK, pts, bt.n, bt.stride);
 	}
+}
+
+// one colour of that sweep on its own (periodic_many3d.hip refreshes ghosts between the colours)
+void relax3_colour7_many(const real_t *so, const real_t *qf, real_t *q, const real_t *sor, int II, int JJ, int KK, int pts,
+                         hipStream_t st, Batch bt)
+{
+	const size_t n = (size_t)((II - 2 + 1) / 2) * (JJ - 2) * (KK - 2);
+	hipLaunchKernelGGL(relax7_colour_many, dim3(cap_grid(n, 256)), dim3(256), 0, st, so, qf, q, sor, II, JJ, KK, pts, bt.n, bt.stride);
 }
 
 __global__ __launch_bounds__(256) void residual7_many_kernel(const real_t *__restrict__ so, const real_t *__restrict__ qf,

@@ -82,7 +82,8 @@ void wrap3(real_t *a, int II, int JJ, int KK, int narrays, int ipn, hipStream_t 
 // the refreshes that follow one colour of the sweep (relax_GS.f90:266-276, :318-328): x ghosts of the rows and y
 // ghosts of the planes the colour visited.  27-point: rows j = 1 + jb + 2r, planes k = 1 + kb + 2c (0-based);
 // 7-point (jb = kb = -1): every interior row and plane.
-void wrap3_colour(real_t *q, int II, int JJ, int KK, int jb, int kb, int ipn, hipStream_t st)
+// narrays: that many arrays of II*JJ*KK doubles back to back, one launch (a batch: periodic_many3d.hip)
+void wrap3_colour(real_t *q, int II, int JJ, int KK, int jb, int kb, int ipn, hipStream_t st, int narrays)
 {
 	const int mode = (per3_y(ipn) ? 1 : 0) | (per3_x(ipn) ? 2 : 0);
 	if (!mode) return;
@@ -90,12 +91,12 @@ void wrap3_colour(real_t *q, int II, int JJ, int KK, int jb, int kb, int ipn, hi
 	const int j0 = jb < 0 ? 1 : 1 + jb, jstep = jb < 0 ? 1 : 2;
 	const int nk = (KK - 2 - (k0 - 1) + kstep - 1) / kstep;
 	if (nk <= 0) return;
-	hipLaunchKernelGGL(wrap3_xy_kernel, dim3(nk, 1), dim3(256), 0, st, q, II, JJ, KK, mode, 1, k0, kstep, j0, jstep, JJ - 1);
+	hipLaunchKernelGGL(wrap3_xy_kernel, dim3(nk, narrays), dim3(256), 0, st, q, II, JJ, KK, mode, 1, k0, kstep, j0, jstep, JJ - 1);
 }
 
-void wrap3_sweep_end(real_t *q, int II, int JJ, int KK, int ipn, hipStream_t st)
+void wrap3_sweep_end(real_t *q, int II, int JJ, int KK, int ipn, hipStream_t st, int narrays)
 {
-	if (per3_z(ipn)) wrap3_z(q, II, JJ, KK, 1, st);
+	if (per3_z(ipn)) wrap3_z(q, II, JJ, KK, narrays, st);
 }
 
 // ------------------------------------------------------------------ transfers and set-up
@@ -155,9 +156,10 @@ __device__ __forceinline__ int unknown3(int i, int j, int k, int nx, int ny, int
 // One workgroup.  The matrix is assembled by walking the stencil (every coefficient stored at an interior point
 // couples two grid points, each mapped to its unknown through the wrap), then factored with the operation order of
 // the unblocked DPOTF2 'U': column c of row j is owned by one thread, which accumulates its dot product in the
-// reference-BLAS order -- results independent of the thread count.
+// reference-BLAS order -- results independent of the thread count.  nst: the slots so holds, 14 or 4 (a one-level
+// seven-point handle: slots 1..3 are its west, south and bottom entries)
 __global__ __launch_bounds__(1024) void setup_cg3_per_kernel(const real_t *__restrict__ so, int II, int JJ, int KK,
-                                                             real_t *__restrict__ abd, int nabd1, int ipn, int *info)
+                                                             real_t *__restrict__ abd, int nabd1, int ipn, int *info, int nst)
 {
 	const int nx = II - 2, ny = JJ - 2, nz = KK - 2, N = nx * ny * nz;
 	const int tid = threadIdx.x, nt = blockDim.x;
@@ -170,7 +172,7 @@ __global__ __launch_bounds__(1024) void setup_cg3_per_kernel(const real_t *__res
 		const int i = 2 + r % nx, j = 2 + (r / nx) % ny, k = 2 + r / (nx * ny);
 		const size_t x = (size_t)(i - 1) + (size_t)II * ((size_t)(j - 1) + (size_t)JJ * (size_t)(k - 1));
 		ABD(r, r) = so[x];
-		for (int s = 1; s < 14; s++) {
+		for (int s = 1; s < nst; s++) {
 			const int X = unknown3(i + EA3[s][0], j + EA3[s][1], k + EA3[s][2], nx, ny, nz, ipn);
 			const int Y = unknown3(i + EB3[s][0], j + EB3[s][1], k + EB3[s][2], nx, ny, nz, ipn);
 			if (X < 0 || Y < 0) continue;
@@ -275,9 +277,9 @@ __global__ __launch_bounds__(1024) void solve_cg3_per_kernel(real_t *__restrict_
 }
 #undef ABD
 
-void setup_cg3_per(const real_t *so, int II, int JJ, int KK, real_t *abd, int nabd1, int ipn, int *info, hipStream_t st)
+void setup_cg3_per(const real_t *so, int II, int JJ, int KK, real_t *abd, int nabd1, int ipn, int *info, hipStream_t st, int nst)
 {
-	hipLaunchKernelGGL(setup_cg3_per_kernel, dim3(1), dim3(1024), 0, st, so, II, JJ, KK, abd, nabd1, ipn, info);
+	hipLaunchKernelGGL(setup_cg3_per_kernel, dim3(1), dim3(1024), 0, st, so, II, JJ, KK, abd, nabd1, ipn, info, nst == 4 ? 4 : 14);
 }
 
 void solve_cg3_per(real_t *q, const real_t *qf, int II, int JJ, int KK, const real_t *abd, real_t *bbd, int nabd1, int ipn,

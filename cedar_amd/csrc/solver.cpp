@@ -150,7 +150,7 @@ real_t *dalloc(size_t n)
 
 // cedar_amd_solver_create with a batch capacity (plane relaxation builds its 2D solvers with one: planes_setup)
 static cedar_amd_solver *solver_create(int nd, len_t nx, len_t ny, len_t nz, int nstencil, const real_t *so, int own_device_so,
-                                       const cedar_amd_settings *settings, int batch);
+                                       const cedar_amd_settings *settings, int batch, bool periodic_batch = false);
 
 struct cedar_amd_solver {
 	int nd = 2;
@@ -171,6 +171,9 @@ struct cedar_amd_solver {
 	// every level's vectors hold nb_alloc items, a cycle works on the first nb.  3D with nb > 1: the kernels of many3d.hip
 	// in the reference order; nb == 1: the single-vector kernels, whatever nb_alloc is
 	int nb_alloc = 1, nb = 1;
+	// a periodic 3D handle of cedar_amd_solver_create_many_periodic: its levels hold nb_alloc items too, and a batch runs
+	// the kernels of periodic_many3d.hip.  A periodic handle made any other way holds one item and the _many calls refuse it
+	bool per_batch = false;
 	// a second captured cycle: the two colours of a plane sweep may differ by one plane
 	hipGraphExec_t gexec2 = nullptr;
 	int gnb2 = 0;
@@ -467,7 +470,9 @@ void smooth(const cedar_amd_solver *s, const Level &L, real_t *x, const real_t *
 			// the ghosts of x hold the periodic image after any sweep, after interp_add, and on a coarse level (x starts
 			// from zero); the first pre-smoothing sweep on level 0 sees the caller's x and makes no such assumption
 			const bool consistent = it > 0 || updown == BMG_UP || &L != &s->lv[0];
-			relax3_gs_per(L.A, b, x, L.SOR0, L.II, L.JJ, L.KK, L.nst, updown, s->st.ibc, st, consistent);
+			if (s->nb > 1) // a batch (periodic_many3d.hip): the same rule for every item
+				relax3_gs_per_many(L.A, b, x, L.SOR0, L.II, L.JJ, L.KK, L.nst, updown, s->st.ibc, st, consistent, Batch{s->nb, L.npts});
+			else relax3_gs_per(L.A, b, x, L.SOR0, L.II, L.JJ, L.KK, L.nst, updown, s->st.ibc, st, consistent);
 			continue;
 		}
 		if (s->nd == 3 && s->nb > 1) { // a batch of right-hand sides: reference order, operator fetched once (many3d.hip)
@@ -542,6 +547,8 @@ void coarse_solve(cedar_amd_solver *s, real_t *x, const real_t *b, hipStream_t s
 	const Level &C = s->lv.back();
 	if (s->nd == 2 && s->st.ibc) solve_cg2_per(x, b, C.II, C.JJ, s->ABD, s->bbd, s->nabd1, s->st.ibc, st);
 	else if (s->nd == 2) solve_cg2(x, b, C.II, C.JJ, s->ABD, s->bbd, s->nabd1, s->nabd2, st, Batch{s->nb, C.npts});
+	else if (s->st.ibc && s->nb > 1)
+		solve_cg3_per_many(x, b, C.II, C.JJ, C.KK, s->ABD, s->bbd, s->nabd1, s->st.ibc, st, Batch{s->nb, C.npts});
 	else if (s->st.ibc) solve_cg3_per(x, b, C.II, C.JJ, C.KK, s->ABD, s->bbd, s->nabd1, s->st.ibc, st);
 	else solve_cg3(x, b, C.II, C.JJ, C.KK, s->ABD, s->bbd, s->nabd1, s->nabd2, st, Batch{s->nb, C.npts});
 }
@@ -569,6 +576,7 @@ void restrict_to(const cedar_amd_solver *s, const Level &L, const Level &K, real
 	else if (p32) restrict3_ci(ci32_view(K.P32, K.II, K.JJ, K.KK), src, K.b, L.II, L.JJ, L.KK, K.II, K.JJ, K.KK, st, bf, bc);
 	else if (s->nd == 2 && ibc) restrict2_per(src, K.b, K.P, L.II, L.JJ, K.II, K.JJ, ibc, st);
 	else if (s->nd == 2) restrict2(src, K.b, K.P, L.II, L.JJ, K.II, K.JJ, st, bf, bc);
+	else if (ibc && s->nb > 1) restrict3_per_many(src, K.b, K.P, L.II, L.JJ, L.KK, K.II, K.JJ, K.KK, ibc, st, bf, bc);
 	else if (ibc) restrict3_per(src, K.b, K.P, L.II, L.JJ, L.KK, K.II, K.JJ, K.KK, ibc, st);
 	else if (s->nb > 1) restrict3_many(src, K.b, K.P, L.II, L.JJ, L.KK, K.II, K.JJ, K.KK, st, bf, bc);
 	else restrict3(src, K.b, K.P, L.II, L.JJ, L.KK, K.II, K.JJ, K.KK, st);
@@ -584,6 +592,8 @@ void interp_add_from(const cedar_amd_solver *s, const Level &L, const Level &K, 
 		interp_add3_ci(ci32_view(K.P32, K.II, K.JJ, K.KK), x, K.x, L.A, L.res, K.II, K.JJ, K.KK, L.II, L.JJ, L.KK, st, bf, bc);
 	else if (s->nd == 2 && ibc) interp_add2_per(x, K.x, L.res, L.A, K.P, K.II, K.JJ, L.II, L.JJ, ibc, st);
 	else if (s->nd == 2) interp_add2(x, K.x, L.res, L.A, K.P, K.II, K.JJ, L.II, L.JJ, st, bf, bc);
+	else if (ibc && s->nb > 1)
+		interp_add3_per_many(x, K.x, L.A, L.res, K.P, K.II, K.JJ, K.KK, L.II, L.JJ, L.KK, ibc, st, bf, bc);
 	else if (ibc) interp_add3_per(x, K.x, L.A, L.res, K.P, K.II, K.JJ, K.KK, L.II, L.JJ, L.KK, ibc, st);
 	else if (s->nb > 1) interp_add3_many(x, K.x, L.A, L.res, K.P, K.II, K.JJ, K.KK, L.II, L.JJ, L.KK, st, bf, bc);
 	else interp_add3(x, K.x, L.A, L.res, K.P, K.II, K.JJ, K.KK, L.II, L.JJ, L.KK, st);
@@ -749,7 +759,7 @@ cedar_amd_solver *cedar_amd_solver_create(int nd, len_t nx, len_t ny, len_t nz, 
 } // extern "C"
 
 static cedar_amd_solver *solver_create(int nd, len_t nx, len_t ny, len_t nz, int nstencil, const real_t *so, int own_device_so,
-                                       const cedar_amd_settings *settings, int batch)
+                                       const cedar_amd_settings *settings, int batch, bool periodic_batch)
 {
 	hipStream_t st = current_stream();
 	cedar_amd_solver *s = new cedar_amd_solver;
@@ -802,8 +812,10 @@ static cedar_amd_solver *solver_create(int nd, len_t nx, len_t ny, len_t nz, int
 	// CEDAR_AMD_YLINES_TRANSPOSED=0 keeps the gather / solve / scatter pipeline for cross-checks
 	const char *eyt = getenv("CEDAR_AMD_YLINES_TRANSPOSED");
 	const bool lyt = ly && s->st.ibc == 0 && !(eyt && atoi(eyt) == 0);
-	// batches (see the struct): Dirichlet V-cycles; 2D with the y-lines on transposed arrays, 3D point relaxation
-	if (s->nb_alloc > 1 && (s->st.ibc != 0 || s->st.cycle != 0 || (ly && !lyt) || (nd == 3 && s->st.relaxation != CEDAR_AMD_RELAX_POINT)))
+	// batches (see the struct): Dirichlet V-cycles; 2D with the y-lines on transposed arrays, 3D point relaxation; periodic
+	// 3D only where cedar_amd_solver_create_many_periodic asked (it has checked cycle and relaxation)
+	s->per_batch = periodic_batch && nd == 3 && s->st.ibc != 0;
+	if (s->nb_alloc > 1 && ((s->st.ibc != 0 && !s->per_batch) || s->st.cycle != 0 || (ly && !lyt) || (nd == 3 && s->st.relaxation != CEDAR_AMD_RELAX_POINT)))
 		s->nb_alloc = 1;
 	level_init(s->lv[0], nd, (int)nx, (int)ny, (int)nz, nstencil, false, ly, lyt, s->nb_alloc);
 	Level &F0 = s->lv[0];
@@ -910,7 +922,7 @@ static cedar_amd_solver *solver_create(int nd, len_t nx, len_t ny, len_t nz, int
 	}
 	if (nd == 2 && s->st.ibc) setup_cg2_per(C.A, C.II, C.JJ, C.nst, s->ABD, s->nabd1, s->st.ibc, s->dinfo, st);
 	else if (nd == 2) setup_cg2(C.A, C.II, C.JJ, C.nst, s->ABD, s->nabd1, s->nabd2, s->dinfo, st);
-	else if (s->st.ibc) setup_cg3_per(C.A, C.II, C.JJ, C.KK, s->ABD, s->nabd1, s->st.ibc, s->dinfo, st);
+	else if (s->st.ibc) setup_cg3_per(C.A, C.II, C.JJ, C.KK, s->ABD, s->nabd1, s->st.ibc, s->dinfo, st, C.nst);
 	else setup_cg3(C.A, C.II, C.JJ, C.KK, C.nst, s->ABD, s->nabd1, s->nabd2, s->dinfo, st);
 	int info = 0;
 	CEDAR_HIP_CHECK(hipMemcpyAsync(&info, s->dinfo, sizeof(int), hipMemcpyDeviceToHost, st));
@@ -1519,6 +1531,34 @@ cedar_amd_solver *cedar_amd_solver_create_many(int nd, len_t nx, len_t ny, len_t
 	return solver_create(nd, nx, ny, nz, nstencil, so, own_device_so, settings, max_rhs);
 }
 
+// cedar_amd_solver_create_many for a periodic 3D handle (include/cedar_amd.h).  What solver_create would quietly turn into
+// something else -- an F-cycle or plane relaxation with a batch, 2D periodic -- is refused here instead
+cedar_amd_solver *cedar_amd_solver_create_many_periodic(int nd, len_t nx, len_t ny, len_t nz, int nstencil, const real_t *so,
+                                                        int own_device_so, const cedar_amd_settings *settings, int max_rhs)
+{
+	cedar_amd_settings st;
+	if (settings) st = *settings;
+	else cedar_amd_default_settings(&st);
+	if (st.ibc == 0) return cedar_amd_solver_create_many(nd, nx, ny, nz, nstencil, so, own_device_so, settings, max_rhs);
+	const char *why = nullptr;
+	if (max_rhs < 1 || max_rhs > CEDAR_AMD_MAX_RHS) why = "max_rhs must be 1 .. 32";
+	else if (nd != 3) why = "periodic batches are served in 3D only";
+	else if (st.cycle != 0) why = "only the V-cycle is supported";
+	else if (st.relaxation != CEDAR_AMD_RELAX_POINT) why = "only point relaxation is supported";
+	if (why) {
+		char msg[256];
+		snprintf(msg, sizeof(msg), "cedar_amd_solver_create_many_periodic: %s; no solver created", why);
+		print_error(msg);
+		return nullptr;
+	}
+	cedar_amd_solver *s = solver_create(nd, nx, ny, nz, nstencil, so, own_device_so, settings, max_rhs, true);
+	if (!s) { // what cedar_amd_solver_create refuses for a periodic handle, reported above under its name
+		char msg[] = "cedar_amd_solver_create_many_periodic: refused as cedar_amd_solver_create refuses it; no solver created";
+		print_error(msg);
+	}
+	return s;
+}
+
 int cedar_amd_solver_max_rhs(const cedar_amd_solver *s) { return null_handle(s, "cedar_amd_solver_max_rhs") ? 0 : s->nb_alloc; }
 
 // what the batched entry points cannot do: reported, nothing written
@@ -1526,7 +1566,7 @@ static bool many_refused(const cedar_amd_solver *s, int nrhs, const char *who)
 {
 	const char *why = nullptr;
 	if (nrhs < 1) why = "nrhs must be at least 1";
-	else if (s->st.ibc != 0) why = "periodic boundary conditions (ibc != 0) are not supported";
+	else if (s->st.ibc != 0 && !s->per_batch) why = "periodic boundary conditions (ibc != 0) are not supported";
 	else if (s->st.cycle != 0) why = "only the V-cycle is supported";
 	else if (s->nd == 3 && s->st.relaxation != CEDAR_AMD_RELAX_POINT) why = "3D plane relaxation is not supported";
 	else if (nrhs > s->nb_alloc) why = "nrhs exceeds the handle's max_rhs (cedar_amd_solver_create_many)";
@@ -1713,16 +1753,19 @@ static int pcg_run(cedar_amd_solver *s, int nrhs, const real_t *b, real_t *x, co
 	double sc[CEDAR_AMD_MAX_RHS * PCG_NSC], r0[CEDAR_AMD_MAX_RHS], m0[CEDAR_AMD_MAX_RHS];
 	int itm[CEDAR_AMD_MAX_RHS];
 	unsigned active = nrhs >= 32 ? ~0u : (1u << nrhs) - 1u;
-	// a periodic handle (cedar_amd_solver_fcg_periodic only, one right-hand side): x gets the periodic image in its ghost
-	// layers before the residual reads them and again on return; the direction pass wraps its own reads (krylov.hip)
+	// a periodic handle (cedar_amd_solver_fcg_periodic, one right-hand side; _fcg_periodic_many, 3D): every item's x gets
+	// the periodic image in its ghost layers before the residual reads them and again on return; the direction pass wraps
+	// its own reads (krylov.hip)
 	const int ibc = s->st.ibc;
 	auto wrap_x = [&]() {
 		if (ibc && s->nd == 2) wrap2(X, L.II, L.JJ, 1, ibc == 1 || ibc == 3, ibc == 2 || ibc == 3, st);
-		else if (ibc) wrap3(X, L.II, L.JJ, L.KK, 1, ibc, st);
+		else if (ibc) wrap3(X, L.II, L.JJ, L.KK, nrhs, ibc, st);
 	};
 	// the two passes on the active items; update: pn = nullptr leaves x and r where they are (dot products only)
 	auto direction = [&](const real_t *pold, real_t *pn, bool first) {
-		if (ibc)
+		if (ibc && nrhs > 1)
+			pcg_direction_periodic_many(L.A, Z, pold, pn, s->kw, L.nst, L.II, L.JJ, L.KK, ibc, first, s->kslab, s->ksc, st, bt, active);
+		else if (ibc)
 			pcg_direction_periodic(L.A, Z, pold, pn, s->kw, s->nd, L.nst, L.II, L.JJ, L.KK, ibc, first, s->kslab, s->ksc, st);
 		else if (nrhs == 1)
 			pcg_direction(L.A, op27, Z, pold, pn, s->kw, s->nd, L.nst, L.II, L.JJ, L.KK, first, s->kslab, s->ksc, st);
@@ -1869,6 +1912,26 @@ int cedar_amd_solver_fcg_periodic(cedar_amd_solver *s, const real_t *b, real_t *
 	const cedar_amd_pcg_settings p = pcg_settings_or_default(settings);
 	if (fcg_refused(s, p, who, true)) return -1;
 	return pcg_run(s, 1, b, x, p, hist, nullptr, who, p.precon == CEDAR_AMD_PCG_PRECON_BMG);
+}
+
+// cedar_amd_solver_fcg_periodic on the first nrhs items of a handle of cedar_amd_solver_create_many_periodic, in lockstep
+// (the contract of cedar_amd_solver_fcg_many); one right-hand side takes the single-vector path
+int cedar_amd_solver_fcg_periodic_many(cedar_amd_solver *s, int nrhs, const real_t *b, real_t *x,
+                                       const cedar_amd_pcg_settings *settings, real_t *hist, int *iters)
+{
+	const char *who = "cedar_amd_solver_fcg_periodic_many";
+	if (null_handle(s, who)) return -1;
+	if (s->st.ibc == 0) return cedar_amd_solver_fcg_many(s, nrhs, b, x, settings, hist, iters);
+	if (many_refused(s, nrhs, who)) return -1;
+	if (!b || !x) {
+		char msg[256];
+		snprintf(msg, sizeof(msg), "%s: b and x must not be NULL; nothing done", who);
+		print_error(msg);
+		return -1;
+	}
+	const cedar_amd_pcg_settings p = pcg_settings_or_default(settings);
+	if (fcg_refused(s, p, who, true)) return -1;
+	return pcg_run(s, nrhs, b, x, p, hist, iters, who, p.precon == CEDAR_AMD_PCG_PRECON_BMG);
 }
 
 void cedar_amd_solver_precondition(cedar_amd_solver *s, real_t *z, const real_t *r)

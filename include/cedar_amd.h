@@ -770,6 +770,64 @@ int cedar_amd_restrict3_many(int nrhs, real_t *q, real_t *qc, real_t *ci, len_t 
 int cedar_amd_interp_add3_many(int nrhs, real_t *q, real_t *qc, real_t *so, real_t *res, real_t *ci, len_t iic, len_t jjc,
                                len_t kkc, len_t iif, len_t jjf, len_t kkf, int nstncl);
 
+/* Several right-hand sides at once on a PERIODIC 3D handle (periodic_many3d.hip, krylov.hip *_per_many).
+ * cedar_amd_solver_create_many_periodic is cedar_amd_solver_create_many for a periodic 3D handle: every level, the
+ * coarsest right-hand-side workspace and later the Krylov storage have room for max_rhs items, and
+ * cedar_amd_solver_max_rhs reports max_rhs.  cedar_amd_solver_create_many itself is unchanged: a periodic handle asked for
+ * through it still holds one item, and the _many calls keep refusing it.
+ *  - Served: 3D, ibc 1..3 and 5..8, 7- and 27-point, point relaxation, V(m,n), max_rhs 1 .. 32.  On such a handle
+ *    cedar_amd_solver_vcycle_many, _solve_many and _time_vcycles_many work with the contracts they have above; every item's
+ *    x comes back with the periodic image in its ghost layers.  Every single-vector entry point (_solve, _vcycle, _get,
+ *    _set, _time_*) still works on item 0 with the single-vector kernels, unchanged.
+ *  - Forwarded: ibc == 0 goes to cedar_amd_solver_create_many; cedar_amd_solver_fcg_periodic_many on a Dirichlet batch
+ *    handle goes to cedar_amd_solver_fcg_many; the kernel-level calls below with ibc = 0 go to their Dirichlet _many twin.
+ *  - Refused by the creation call (print_error, NULL): nd == 2 with ibc != 0, an F-cycle, plane (any non-point)
+ *    relaxation, max_rhs outside 1 .. 32, and everything cedar_amd_solver_create refuses for a periodic handle (a boundary
+ *    code 3D does not define, an odd periodic extent on a coarsened level, more than 2048 coarsest unknowns).
+ *  - Refused on the handle (print_error, -1, nothing written): nrhs < 1 or nrhs > max_rhs; cedar_amd_solver_pcg_many and
+ *    cedar_amd_solver_fcg_many (periodic boundaries, as before); cedar_amd_solver_fcg_periodic when max_rhs > 1 (use
+ *    cedar_amd_solver_fcg_periodic_many with nrhs == 1); the single-precision switches.
+ *  - Bits: item m of every result -- x, rel rows, iters -- has the bits of the single-vector periodic call on item m alone
+ *    on a handle of cedar_amd_solver_create with the same settings.  The single-vector periodic path has no partial-sum
+ *    sweep, so this holds at every size with no environment switch.
+ *  - Out of scope: 2D periodic batches, periodic F-cycles on a batch, singular fully periodic operators, the rank-grid
+ *    solvers. */
+cedar_amd_solver *cedar_amd_solver_create_many_periodic(int nd, len_t nx, len_t ny, len_t nz, int nstencil,
+                                                        const real_t *so, int own_device_so,
+                                                        const cedar_amd_settings *settings, int max_rhs);
+/* cedar_amd_solver_fcg_periodic on the first nrhs items in lockstep, with the contract of cedar_amd_solver_fcg_many (hist
+ * rows, iters, freezing of stopped or broken-down items, storage for max_rhs items): flexible beta with precon 3, the
+ * standard recurrence with precon 1 / 2, all four stop tests; every item's x is wrapped before the first residual and on
+ * return, the ghosts of b are never read.  Item m's x, hist row and iters[m] equal those of cedar_amd_solver_fcg_periodic
+ * on item m alone, bit for bit; nrhs == 1 runs the single-vector path itself.  A Dirichlet batch handle is forwarded to
+ * cedar_amd_solver_fcg_many; a periodic handle not made by cedar_amd_solver_create_many_periodic is refused as the other
+ * _many calls refuse it. */
+int cedar_amd_solver_fcg_periodic_many(cedar_amd_solver *s, int nrhs, const real_t *b, real_t *x,
+                                       const cedar_amd_pcg_settings *p, real_t *hist, int *iters);
+/* The batched periodic 3D kernels one by one on caller arrays (host or device; nrhs items back to back, operator arrays
+ * shared; argument order of the Dirichlet _many calls, then the boundary code).  Item m has the bits of the single-vector
+ * periodic drop-in (BMG3_SymStd_relax_GS / _restrict / _interp_add / _SOLVE_cg, cedar_amd_pcg_direction_periodic) on item
+ * m alone.  0, or -1 (print_error, nothing written) for nrhs outside 1 .. 32, a NULL array, an nstncl other than 4 | 14 or
+ * a boundary code 3D does not define.  ibc = 0 forwards to the Dirichlet _many call (cedar_amd_solve_cg3_periodic_many has
+ * none and refuses it).
+ *  - relax3_gs: ghosts_consistent != 0 tells the sweep that the y ghost rows of q hold the periodic image on entry (the
+ *    row-class path needs it when y is periodic); 0 is always correct.
+ *  - restrict3 refreshes the ghosts of the nrhs fine vectors first (q is written); interp_add3 keeps res /= so(kp).
+ *  - solve_cg3: abd = the dense factor of BMG3_SymStd_SETUP_cg_LU with the same code (shared), bbd = nrhs segments of
+ *    (ii-2)(jj-2)(kk-2) doubles; one workgroup per item.
+ *  - pcg_direction: as cedar_amd_pcg_direction_many, reads wrapped; a masked item is neither read nor written. */
+int cedar_amd_relax3_gs_periodic_many(int nrhs, real_t *so, real_t *qf, real_t *q, real_t *sor, len_t ii, len_t jj, len_t kk,
+                                      int nstncl, int updown, int ibc, int ghosts_consistent);
+int cedar_amd_restrict3_periodic_many(int nrhs, real_t *q, real_t *qc, real_t *ci, len_t ii, len_t jj, len_t kk, len_t iic,
+                                      len_t jjc, len_t kkc, int ibc);
+int cedar_amd_interp_add3_periodic_many(int nrhs, real_t *q, real_t *qc, real_t *so, real_t *res, real_t *ci, len_t iic,
+                                        len_t jjc, len_t kkc, len_t iif, len_t jjf, len_t kkf, int nstncl, int ibc);
+int cedar_amd_solve_cg3_periodic_many(int nrhs, real_t *q, real_t *qf, len_t ii, len_t jj, len_t kk, real_t *abd, real_t *bbd,
+                                      len_t nabd1, int ibc);
+int cedar_amd_pcg_direction_periodic_many(int nrhs, unsigned active, const real_t *so, const real_t *z, const real_t *p,
+                                          real_t *pn, real_t *w, len_t ii, len_t jj, len_t kk, int nstncl, int ibc, int first,
+                                          real_t *sc);
+
 /* plane relaxation as a kernel of its own -- kernels::plane_relax<stypes, rdir>::setup(so) / run(so, x, b, dir)
  * (include/cedar/kernels/plane_relax.h:10-33; include/cedar/3d/relax_planes.h:164-246, src/3d/relax_planes.cc).
  * dir 0 = xy planes, 1 = xz, 2 = yz; plane_settings = the 2D solvers' configuration (NULL: the reference's default
