@@ -25,6 +25,7 @@
 #include "common.h"
 #include "relax27_dev.h"
 #include <algorithm>
+#include <type_traits>
 
 namespace cedar_amd {
 
@@ -82,11 +83,60 @@ __device__ __forceinline__ real_t mv27(real_t d, const C27 &c, const real_t (&qq
 }
 
 // ---------------------------------------------------------------- p' = z + beta p, w = A p', partial p'.w
+// Where the 2D and 7-point bodies read z / p at the neighbours of point x = (i, j, k) -- the one thing in which a level
+// with periodic directions (pcg_direction_periodic) differs.  There a neighbour index on the ghost layer of a periodic
+// direction becomes the opposite interior end: 0 -> extent - 2, extent - 1 -> 1.  Only the ADDRESS of z / p changes --
+// the expression z + beta p, the operator entries (read at the same places; their ghost layers hold the periodic image)
+// and the term order are the same, so w has the bits of matvec2 / matvec3 on a vector whose ghosts were wrapped first.
+// pd is uniform over the launch.  2D: k = 0, KK = 1 (B and T unused).
+// Both policies have the same methods on a point q = (address, column): W / E give the neighbour in the row, again as a
+// point, so that a 2D corner is S(W(q)); S / N / B / T give an address.  AdjPlain's are literally x - 1, x + 1, x -+ sj,
+// x -+ sk; AdjPer's are row + wrapped column and wrapped row + column.  The bodies below write the stencil terms out
+// where they are used: passed through a shared seven-term helper, pcg_dir7<first> needs two VGPRs more.
+__device__ __forceinline__ int wrap_lo(int i, int n, int per) { return per && i == 0 ? n - 2 : i; }     // i - 1 of a point
+__device__ __forceinline__ int wrap_hi(int i, int n, int per) { return per && i == n - 1 ? 1 : i; }     // i + 1 of a point
+
+struct Pt {
+	size_t x; // address
+	int i;    // column
+};
+
+struct AdjPlain {
+	size_t sj, sk;
+	__device__ __forceinline__ AdjPlain(PerDirs, int, int, int II, int JJ, int) : sj(II), sk((size_t)II * JJ) {}
+	__device__ __forceinline__ Pt W(Pt q) const { return Pt{q.x - 1, q.i - 1}; }
+	__device__ __forceinline__ Pt E(Pt q) const { return Pt{q.x + 1, q.i + 1}; }
+	__device__ __forceinline__ size_t S(Pt q) const { return q.x - sj; }
+	__device__ __forceinline__ size_t N(Pt q) const { return q.x + sj; }
+	__device__ __forceinline__ size_t B(Pt q) const { return q.x - sk; }
+	__device__ __forceinline__ size_t T(Pt q) const { return q.x + sk; }
+};
+
+struct AdjPer {
+	size_t row, rs, rn, rb, rt; // the row of the point and its four neighbour rows, wrapped (uniform over the workgroup)
+	int II, px;
+	__device__ __forceinline__ AdjPer(PerDirs pd, int j, int k, int II_, int JJ, int KK) : II(II_), px(pd.x)
+	{
+		const size_t sj = II, sk = (size_t)II * JJ;
+		row = sj * (size_t)j + sk * (size_t)k;
+		rs = sj * (size_t)wrap_lo(j - 1, JJ, pd.y) + sk * (size_t)k, rn = sj * (size_t)wrap_hi(j + 1, JJ, pd.y) + sk * (size_t)k;
+		rb = sj * (size_t)j + sk * (size_t)wrap_lo(k - 1, KK, pd.z), rt = sj * (size_t)j + sk * (size_t)wrap_hi(k + 1, KK, pd.z);
+	}
+	__device__ __forceinline__ Pt at(int c) const { return Pt{row + (size_t)c, c}; }
+	__device__ __forceinline__ Pt W(Pt q) const { return at(wrap_lo(q.i - 1, II, px)); }
+	__device__ __forceinline__ Pt E(Pt q) const { return at(wrap_hi(q.i + 1, II, px)); }
+	__device__ __forceinline__ size_t S(Pt q) const { return rs + (size_t)q.i; }
+	__device__ __forceinline__ size_t N(Pt q) const { return rn + (size_t)q.i; }
+	__device__ __forceinline__ size_t B(Pt q) const { return rb + (size_t)q.i; }
+	__device__ __forceinline__ size_t T(Pt q) const { return rt + (size_t)q.i; }
+};
+
 // 2D: one lane per point, one workgroup per 256-point segment of a row (residual2_kernel's layout)
-template <bool NINE, bool FIRST>
+template <bool NINE, bool FIRST, class ADJ>
 __device__ __forceinline__ void dir2_segment(const real_t *__restrict__ so, const real_t *__restrict__ z,
                                              const real_t *__restrict__ p, real_t *__restrict__ pn, real_t *__restrict__ w,
-                                             const real_t *__restrict__ sc, int II, int JJ, real_t *__restrict__ part)
+                                             const real_t *__restrict__ sc, int II, int JJ, PerDirs pd,
+                                             real_t *__restrict__ part)
 {
 	__shared__ real_t lds[4];
 	const int i = blockIdx.x * blockDim.x + threadIdx.x + 1;
@@ -95,19 +145,21 @@ __device__ __forceinline__ void dir2_segment(const real_t *__restrict__ so, cons
 	real_t acc = 0.0;
 	if (i <= II - 2) {
 		const size_t sj = II, PS = (size_t)II * JJ;
+		const ADJ a(pd, j, 0, II, JJ, 1);
 		const size_t x = (size_t)i + sj * (size_t)j;
 		auto P = [&](size_t y) -> real_t { return FIRST ? z[y] : z[y] + beta * p[y]; };
+		const Pt q{x, i};
 		const real_t pc = P(x);
 		real_t s = so[KO * PS + x] * pc;
-		s = s - so[KW * PS + x] * P(x - 1);
-		s = s - so[KW * PS + x + 1] * P(x + 1);
-		s = s - so[KS * PS + x] * P(x - sj);
-		s = s - so[KS * PS + x + sj] * P(x + sj);
+		s = s - so[KW * PS + x] * P(a.W(q).x);
+		s = s - so[KW * PS + x + 1] * P(a.E(q).x);
+		s = s - so[KS * PS + x] * P(a.S(q));
+		s = s - so[KS * PS + x + sj] * P(a.N(q));
 		if (NINE) {
-			s = s - so[KSW * PS + x] * P(x - 1 - sj);
-			s = s - so[KNW * PS + x + 1] * P(x + 1 - sj);
-			s = s - so[KNW * PS + x + sj] * P(x - 1 + sj);
-			s = s - so[KSW * PS + x + 1 + sj] * P(x + 1 + sj);
+			s = s - so[KSW * PS + x] * P(a.S(a.W(q)));
+			s = s - so[KNW * PS + x + 1] * P(a.S(a.E(q)));
+			s = s - so[KNW * PS + x + sj] * P(a.N(a.W(q)));
+			s = s - so[KSW * PS + x + 1 + sj] * P(a.N(a.E(q)));
 		}
 		pn[x] = pc;
 		w[x] = s;
@@ -123,16 +175,8 @@ __global__ __launch_bounds__(256) void pcg_dir2(const real_t *__restrict__ so, c
                                                 real_t *__restrict__ w, const real_t *__restrict__ sc, int II, int JJ,
                                                 real_t *__restrict__ part)
 {
-	dir2_segment<NINE, FIRST>(so, z, p, pn, w, sc, II, JJ, part);
+	dir2_segment<NINE, FIRST, AdjPlain>(so, z, p, pn, w, sc, II, JJ, PerDirs{}, part);
 }
-
-// ---------------------------------------------------------------- the same on a level with periodic directions
-// (pcg_direction_periodic).  A neighbour index on the ghost layer of a periodic direction becomes the opposite interior end:
-// 0 -> extent - 2, extent - 1 -> 1.  Only the ADDRESS of z / p changes -- the expression z + beta p, the operator entries
-// (read where the kernels above read them; their ghost layers hold the periodic image) and the term order are the same, so
-// w has the bits of matvec2 / matvec3 on a vector whose ghosts were wrapped first.  pd is uniform over the launch.
-__device__ __forceinline__ int wrap_lo(int i, int n, int per) { return per && i == 0 ? n - 2 : i; }     // i - 1 of a point
-__device__ __forceinline__ int wrap_hi(int i, int n, int per) { return per && i == n - 1 ? 1 : i; }     // i + 1 of a point
 
 template <bool NINE, bool FIRST>
 __global__ __launch_bounds__(256) void pcg_dir2_per(const real_t *__restrict__ so, const real_t *__restrict__ z,
@@ -140,35 +184,51 @@ __global__ __launch_bounds__(256) void pcg_dir2_per(const real_t *__restrict__ s
                                                     real_t *__restrict__ w, const real_t *__restrict__ sc, int II, int JJ,
                                                     PerDirs pd, real_t *__restrict__ part)
 {
+	dir2_segment<NINE, FIRST, AdjPer>(so, z, p, pn, w, sc, II, JJ, pd, part);
+}
+
+// 3D 7-point: one workgroup per grid row (residual3_kernel's layout); partial of logical row L at part[L]
+template <bool FIRST, class ADJ>
+__device__ __forceinline__ void dir7_row(const real_t *__restrict__ so, const real_t *__restrict__ z,
+                                         const real_t *__restrict__ p, real_t *__restrict__ pn, real_t *__restrict__ w,
+                                         const real_t *__restrict__ sc, int II, int JJ, int KK, unsigned nrows, PerDirs pd,
+                                         real_t *__restrict__ part)
+{
 	__shared__ real_t lds[4];
-	const int i = blockIdx.x * blockDim.x + threadIdx.x + 1;
-	const int j = blockIdx.y + 1;
+	const unsigned L = xcd_remap(blockIdx.x, nrows);
+	if (L >= nrows) return; // grid padding of xcd_grid: no slab entry
+	const int j = (int)(L % (unsigned)(JJ - 2)) + 1, k = (int)(L / (unsigned)(JJ - 2)) + 1;
+	const size_t sj = II, sk = (size_t)II * JJ, PS = sk * KK;
+	const ADJ a(pd, j, k, II, JJ, KK);
 	const real_t beta = FIRST ? 0.0 : sc[PCG_BETA];
+	auto P = [&](size_t y) -> real_t { return FIRST ? z[y] : z[y] + beta * p[y]; };
 	real_t acc = 0.0;
-	if (i <= II - 2) {
-		const size_t sj = II, PS = (size_t)II * JJ;
-		const size_t x = (size_t)i + sj * (size_t)j;
-		const size_t iw = wrap_lo(i - 1, II, pd.x), ie = wrap_hi(i + 1, II, pd.x);
-		const size_t rs = sj * (size_t)wrap_lo(j - 1, JJ, pd.y), rc = sj * (size_t)j, rn = sj * (size_t)wrap_hi(j + 1, JJ, pd.y);
-		auto P = [&](size_t y) -> real_t { return FIRST ? z[y] : z[y] + beta * p[y]; };
+	for (int i = threadIdx.x + 1; i <= II - 2; i += blockDim.x) {
+		const size_t x = (size_t)i + sj * (size_t)j + sk * (size_t)k;
 		const real_t pc = P(x);
-		real_t s = so[KO * PS + x] * pc;
-		s = s - so[KW * PS + x] * P(rc + iw);
-		s = s - so[KW * PS + x + 1] * P(rc + ie);
-		s = s - so[KS * PS + x] * P(rs + i);
-		s = s - so[KS * PS + x + sj] * P(rn + i);
-		if (NINE) {
-			s = s - so[KSW * PS + x] * P(rs + iw);
-			s = s - so[KNW * PS + x + 1] * P(rs + ie);
-			s = s - so[KNW * PS + x + sj] * P(rn + iw);
-			s = s - so[KSW * PS + x + 1 + sj] * P(rn + ie);
-		}
+		const Pt q{x, i};
+		real_t s = so[KP * PS + x] * pc;
+		s = s - so[KPW * PS + x] * P(a.W(q).x);
+		s = s - so[KPS * PS + x + sj] * P(a.N(q));
+		s = s - so[KPW * PS + x + 1] * P(a.E(q).x);
+		s = s - so[KPS * PS + x] * P(a.S(q));
+		s = s - so[KB * PS + x] * P(a.B(q));
+		s = s - so[KB * PS + x + sk] * P(a.T(q));
 		pn[x] = pc;
 		w[x] = s;
-		acc = pc * s;
+		acc += pc * s;
 	}
 	const real_t t = block_sum_k<256>(acc, lds);
-	if (threadIdx.x == 0) part[blockIdx.x + (size_t)gridDim.x * blockIdx.y] = t;
+	if (threadIdx.x == 0) part[L] = t;
+}
+
+template <bool FIRST>
+__global__ __launch_bounds__(256) void pcg_dir7(const real_t *__restrict__ so, const real_t *__restrict__ z,
+                                                const real_t *__restrict__ p, real_t *__restrict__ pn,
+                                                real_t *__restrict__ w, const real_t *__restrict__ sc, int II, int JJ,
+                                                int KK, unsigned nrows, real_t *__restrict__ part)
+{
+	dir7_row<FIRST, AdjPlain>(so, z, p, pn, w, sc, II, JJ, KK, nrows, PerDirs{}, part);
 }
 
 template <bool FIRST>
@@ -177,67 +237,32 @@ __global__ __launch_bounds__(256) void pcg_dir7_per(const real_t *__restrict__ s
                                                     real_t *__restrict__ w, const real_t *__restrict__ sc, int II, int JJ,
                                                     int KK, unsigned nrows, PerDirs pd, real_t *__restrict__ part)
 {
-	__shared__ real_t lds[4];
-	const unsigned L = xcd_remap(blockIdx.x, nrows);
-	if (L >= nrows) return; // grid padding of xcd_grid: no slab entry
-	const int j = (int)(L % (unsigned)(JJ - 2)) + 1, k = (int)(L / (unsigned)(JJ - 2)) + 1;
-	const size_t sj = II, sk = (size_t)II * JJ, PS = sk * KK;
-	const size_t row = sj * (size_t)j + sk * (size_t)k;
-	// the four neighbour rows, wrapped (uniform over the workgroup)
-	const size_t rs = sj * (size_t)wrap_lo(j - 1, JJ, pd.y) + sk * (size_t)k, rn = sj * (size_t)wrap_hi(j + 1, JJ, pd.y) + sk * (size_t)k;
-	const size_t rb = sj * (size_t)j + sk * (size_t)wrap_lo(k - 1, KK, pd.z), rt = sj * (size_t)j + sk * (size_t)wrap_hi(k + 1, KK, pd.z);
-	const real_t beta = FIRST ? 0.0 : sc[PCG_BETA];
-	auto P = [&](size_t y) -> real_t { return FIRST ? z[y] : z[y] + beta * p[y]; };
-	real_t acc = 0.0;
-	for (int i = threadIdx.x + 1; i <= II - 2; i += blockDim.x) {
-		const size_t x = row + (size_t)i;
-		const real_t pc = P(x);
-		real_t s = so[KP * PS + x] * pc;
-		s = s - so[KPW * PS + x] * P(row + (size_t)wrap_lo(i - 1, II, pd.x));
-		s = s - so[KPS * PS + x + sj] * P(rn + (size_t)i);
-		s = s - so[KPW * PS + x + 1] * P(row + (size_t)wrap_hi(i + 1, II, pd.x));
-		s = s - so[KPS * PS + x] * P(rs + (size_t)i);
-		s = s - so[KB * PS + x] * P(rb + (size_t)i);
-		s = s - so[KB * PS + x + sk] * P(rt + (size_t)i);
-		pn[x] = pc;
-		w[x] = s;
-		acc += pc * s;
-	}
-	const real_t t = block_sum_k<256>(acc, lds);
-	if (threadIdx.x == 0) part[L] = t;
+	dir7_row<FIRST, AdjPer>(so, z, p, pn, w, sc, II, JJ, KK, nrows, pd, part);
 }
 
-// 3D 7-point: one workgroup per grid row (residual3_kernel's layout); partial of logical row L at part[L]
-template <bool FIRST>
-__global__ __launch_bounds__(256) void pcg_dir7(const real_t *__restrict__ so, const real_t *__restrict__ z,
-                                                const real_t *__restrict__ p, real_t *__restrict__ pn,
-                                                real_t *__restrict__ w, const real_t *__restrict__ sc, int II, int JJ,
-                                                int KK, unsigned nrows, real_t *__restrict__ part)
+// The end of a 27-point task: w = A p' at the even and the odd point of the pair (mv27 on the finished windows), their
+// share of p'.w added to acc, and w and p' stored at off + row + ie (off: the item's offset; 16-byte stores, or a row's
+// last half pair).  Used by pcg_dir27, pcg_dir27_many and pcg_dir27_per_many, which compile to the code they had with the
+// text in place.  pcg_dir27_per keeps its own copy: with this call the allocator, at 256 VGPRs, spills four VGPRs more.
+__device__ __forceinline__ void dir27_emit(real_t de, real_t dn, const C27 &ce, const C27 &co, const real_t (&qe)[3][3][3],
+                                           const real_t (&qo)[3][3][3], bool o_ok, real_t *__restrict__ w,
+                                           real_t *__restrict__ pn, size_t off, size_t row, int ie, real_t &acc)
 {
-	__shared__ real_t lds[4];
-	const unsigned L = xcd_remap(blockIdx.x, nrows);
-	if (L >= nrows) return; // grid padding of xcd_grid: no slab entry
-	const int j = (int)(L % (unsigned)(JJ - 2)) + 1, k = (int)(L / (unsigned)(JJ - 2)) + 1;
-	const size_t sj = II, sk = (size_t)II * JJ, PS = sk * KK;
-	const real_t beta = FIRST ? 0.0 : sc[PCG_BETA];
-	auto P = [&](size_t y) -> real_t { return FIRST ? z[y] : z[y] + beta * p[y]; };
-	real_t acc = 0.0;
-	for (int i = threadIdx.x + 1; i <= II - 2; i += blockDim.x) {
-		const size_t x = (size_t)i + sj * (size_t)j + sk * (size_t)k;
-		const real_t pc = P(x);
-		real_t s = so[KP * PS + x] * pc;
-		s = s - so[KPW * PS + x] * P(x - 1);
-		s = s - so[KPS * PS + x + sj] * P(x + sj);
-		s = s - so[KPW * PS + x + 1] * P(x + 1);
-		s = s - so[KPS * PS + x] * P(x - sj);
-		s = s - so[KB * PS + x] * P(x - sk);
-		s = s - so[KB * PS + x + sk] * P(x + sk);
-		pn[x] = pc;
-		w[x] = s;
-		acc += pc * s;
+	const real_t we = mv27(de, ce, qe);
+	const real_t pe = qe[1][1][1];
+	acc += pe * we;
+	if (o_ok) {
+		const real_t wo = mv27(dn, co, qo);
+		const real_t po = qo[1][1][1];
+		acc += po * wo;
+		d2u v; v.x = we; v.y = wo;
+		*reinterpret_cast<d2u *>(w + off + row + ie) = v;
+		v.x = pe; v.y = po;
+		*reinterpret_cast<d2u *>(pn + off + row + ie) = v;
+	} else {
+		w[off + row + ie] = we;
+		pn[off + row + ie] = pe;
 	}
-	const real_t t = block_sum_k<256>(acc, lds);
-	if (threadIdx.x == 0) part[L] = t;
 }
 
 // 3D 27-point: residual27_rows' layout -- lane p owns the pair (2p+1, 2p+2) of its row, 16-byte loads and stores,
@@ -283,21 +308,7 @@ __global__ __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(2))) void pc
 						qo[dk][dj][2] = w3 + beta * qo[dk][dj][2];
 					}
 			}
-			const real_t we = mv27(de, ce, qe);
-			const real_t pe = qe[1][1][1];
-			acc += pe * we;
-			if (o_ok) {
-				const real_t wo = mv27(dn, co, qo);
-				const real_t po = qo[1][1][1];
-				acc += po * wo;
-				d2u v; v.x = we; v.y = wo;
-				*reinterpret_cast<d2u *>(w + row + ie) = v;
-				v.x = pe; v.y = po;
-				*reinterpret_cast<d2u *>(pn + row + ie) = v;
-			} else {
-				w[row + ie] = we;
-				pn[row + ie] = pe;
-			}
+			dir27_emit(de, dn, ce, co, qe, qo, o_ok, w, pn, 0, row, ie, acc);
 		}
 	}
 	const real_t t = block_sum_k<BS>(acc, lds);
@@ -309,7 +320,7 @@ __global__ __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(2))) void pc
 // and the right element of the lane that owns the last point (an odd nx ends in a half pair: its right neighbour, the
 // element ldpair read at io, is the wrap) -- those are replaced by z + beta p at the wrapped address after the pair loads,
 // so nothing formed from a ghost value reaches w, pn or the sum.  The coefficients: load_coef27 on the Cedar planes, as
-// pcg_dir27 (a periodic level has no row-interleaved copy).
+// pcg_dir27 (a periodic level has no row-interleaved copy).  The tail is dir27_emit's text (see there).
 template <int BS, bool FIRST>
 __global__ __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(2))) void pcg_dir27_per(
     const Op3 A, const real_t *__restrict__ z, const real_t *__restrict__ p, real_t *__restrict__ pn, real_t *__restrict__ w,
@@ -658,19 +669,20 @@ __global__ __launch_bounds__(256) void pcg_dir2_many(const real_t *__restrict__ 
 	const int m = blockIdx.z;
 	if (!item_on(active, m)) return;
 	const size_t off = (size_t)m * stride;
-	dir2_segment<NINE, FIRST>(so, z + off, FIRST ? z : p + off, pn + off, w + off, sc + (size_t)m * PCG_NSC, II, JJ,
-	                          part + (size_t)m * gridDim.x * gridDim.y);
+	dir2_segment<NINE, FIRST, AdjPlain>(so, z + off, FIRST ? z : p + off, pn + off, w + off, sc + (size_t)m * PCG_NSC, II, JJ,
+	                                    PerDirs{}, part + (size_t)m * gridDim.x * gridDim.y);
 }
 
-// 3D 7-point: pcg_dir7 with the seven operator entries a point reads in registers across the items m0 .. m0 + nitems-1
+// 3D 7-point: dir7_row with the seven operator entries a point reads in registers across the items m0 .. m0 + nitems-1
 // (m0 = ITEM_CHUNK * blockIdx.y).  A lane's sum runs over the trips of a row longer than the workgroup, per item: one
-// LDS column per lane (accl[item][lane], lane-private, so no barrier), summed per item exactly as pcg_dir7 sums acc.
-template <bool FIRST>
-__global__ __launch_bounds__(256) void pcg_dir7_many(const real_t *__restrict__ so, const real_t *__restrict__ z,
-                                                     const real_t *__restrict__ p, real_t *__restrict__ pn,
-                                                     real_t *__restrict__ w, const real_t *__restrict__ sc, int II, int JJ,
-                                                     int KK, unsigned nrows, real_t *__restrict__ part, int nrhs,
-                                                     size_t stride, unsigned active)
+// LDS column per lane (accl[item][lane], lane-private, so no barrier), summed per item exactly as dir7_row sums acc.
+// With AdjPer: the direction pass of a periodic level on a batch (cedar_amd_solver_fcg_periodic_many); item m's pn, w and
+// slab have the bits of pcg_direction_periodic on item m alone.
+template <bool FIRST, class ADJ>
+__device__ __forceinline__ void dir7_items(const real_t *__restrict__ so, const real_t *__restrict__ z,
+                                           const real_t *__restrict__ p, real_t *__restrict__ pn, real_t *__restrict__ w,
+                                           const real_t *__restrict__ sc, int II, int JJ, int KK, unsigned nrows, PerDirs pd,
+                                           real_t *__restrict__ part, int nrhs, size_t stride, unsigned active)
 {
 	__shared__ real_t lds[4];
 	__shared__ real_t accl[ITEM_CHUNK][256];
@@ -679,9 +691,11 @@ __global__ __launch_bounds__(256) void pcg_dir7_many(const real_t *__restrict__ 
 	const int m0 = ITEM_CHUNK * (int)blockIdx.y, nitems = min(ITEM_CHUNK, nrhs - m0);
 	const int j = (int)(L % (unsigned)(JJ - 2)) + 1, k = (int)(L / (unsigned)(JJ - 2)) + 1;
 	const size_t sj = II, sk = (size_t)II * JJ, PS = sk * KK;
+	const ADJ a(pd, j, k, II, JJ, KK);
 	for (int t = 0; t < nitems; t++) accl[t][threadIdx.x] = 0.0;
 	for (int i = threadIdx.x + 1; i <= II - 2; i += blockDim.x) {
 		const size_t x = (size_t)i + sj * (size_t)j + sk * (size_t)k;
+		const Pt q{x, i};
 		const real_t cp = so[KP * PS + x], cw = so[KPW * PS + x], cn = so[KPS * PS + x + sj], ce = so[KPW * PS + x + 1];
 		const real_t cs = so[KPS * PS + x], cb = so[KB * PS + x], ct = so[KB * PS + x + sk];
 #pragma unroll 1
@@ -694,12 +708,12 @@ __global__ __launch_bounds__(256) void pcg_dir7_many(const real_t *__restrict__ 
 			auto P = [&](size_t y) -> real_t { return FIRST ? zm[y] : zm[y] + beta * pm[y]; };
 			const real_t pc = P(x);
 			real_t s = cp * pc;
-			s = s - cw * P(x - 1);
-			s = s - cn * P(x + sj);
-			s = s - ce * P(x + 1);
-			s = s - cs * P(x - sj);
-			s = s - cb * P(x - sk);
-			s = s - ct * P(x + sk);
+			s = s - cw * P(a.W(q).x);
+			s = s - cn * P(a.N(q));
+			s = s - ce * P(a.E(q).x);
+			s = s - cs * P(a.S(q));
+			s = s - cb * P(a.B(q));
+			s = s - ct * P(a.T(q));
 			pn[off + x] = pc;
 			w[off + x] = s;
 			accl[t][threadIdx.x] += pc * s;
@@ -711,6 +725,26 @@ __global__ __launch_bounds__(256) void pcg_dir7_many(const real_t *__restrict__ 
 		const real_t v = block_sum_k<256>(accl[t][threadIdx.x], lds);
 		if (threadIdx.x == 0) part[(size_t)m * nrows + L] = v;
 	}
+}
+
+template <bool FIRST>
+__global__ __launch_bounds__(256) void pcg_dir7_many(const real_t *__restrict__ so, const real_t *__restrict__ z,
+                                                     const real_t *__restrict__ p, real_t *__restrict__ pn,
+                                                     real_t *__restrict__ w, const real_t *__restrict__ sc, int II, int JJ,
+                                                     int KK, unsigned nrows, real_t *__restrict__ part, int nrhs,
+                                                     size_t stride, unsigned active)
+{
+	dir7_items<FIRST, AdjPlain>(so, z, p, pn, w, sc, II, JJ, KK, nrows, PerDirs{}, part, nrhs, stride, active);
+}
+
+template <bool FIRST>
+__global__ __launch_bounds__(256) void pcg_dir7_per_many(const real_t *__restrict__ so, const real_t *__restrict__ z,
+                                                         const real_t *__restrict__ p, real_t *__restrict__ pn,
+                                                         real_t *__restrict__ w, const real_t *__restrict__ sc, int II, int JJ,
+                                                         int KK, unsigned nrows, PerDirs pd, real_t *__restrict__ part, int nrhs,
+                                                         size_t stride, unsigned active)
+{
+	dir7_items<FIRST, AdjPer>(so, z, p, pn, w, sc, II, JJ, KK, nrows, pd, part, nrhs, stride, active);
 }
 
 // 3D 27-point: pcg_dir27 for rows of one trip (at most 2 BS points; longer rows go through pcg_dir27 item by item, see
@@ -773,86 +807,16 @@ __global__ __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(2))) void pc
 						qo[dk][dj][2] = w3 + beta * p3;
 					}
 			}
-			const real_t we = mv27(de, ce, qe);
-			const real_t pe = qe[1][1][1];
-			acc += pe * we;
-			if (o_ok) {
-				const real_t wo = mv27(dn, co, qo);
-				const real_t po = qo[1][1][1];
-				acc += po * wo;
-				d2u v; v.x = we; v.y = wo;
-				*reinterpret_cast<d2u *>(w + off + row + ie) = v;
-				v.x = pe; v.y = po;
-				*reinterpret_cast<d2u *>(pn + off + row + ie) = v;
-			} else {
-				w[off + row + ie] = we;
-				pn[off + row + ie] = pe;
-			}
+			dir27_emit(de, dn, ce, co, qe, qo, o_ok, w, pn, off, row, ie, acc);
 		}
 		const real_t t = block_sum_k<BS>(acc, lds);
 		if (threadIdx.x == 0) part[(size_t)m * nblk + L] = t;
 	}
 }
 
-// ---------------------------------------------------------------- the direction pass of a periodic level on a batch
-// (cedar_amd_solver_fcg_periodic_many): the wrap rule of pcg_dir7_per / pcg_dir27_per -- a neighbour index on a periodic
-// ghost layer is read at the opposite interior end -- with the item loop of pcg_dir7_many / pcg_dir27_many.  Per item the
-// expressions, their order and the sums are those of the single-vector periodic kernels: item m's pn, w and slab have the
-// bits of pcg_direction_periodic on item m alone.
-template <bool FIRST>
-__global__ __launch_bounds__(256) void pcg_dir7_per_many(const real_t *__restrict__ so, const real_t *__restrict__ z,
-                                                         const real_t *__restrict__ p, real_t *__restrict__ pn,
-                                                         real_t *__restrict__ w, const real_t *__restrict__ sc, int II, int JJ,
-                                                         int KK, unsigned nrows, PerDirs pd, real_t *__restrict__ part, int nrhs,
-                                                         size_t stride, unsigned active)
-{
-	__shared__ real_t lds[4];
-	__shared__ real_t accl[ITEM_CHUNK][256];
-	const unsigned L = xcd_remap(blockIdx.x, nrows);
-	if (L >= nrows) return; // grid padding of xcd_grid: no slab entry
-	const int m0 = ITEM_CHUNK * (int)blockIdx.y, nitems = min(ITEM_CHUNK, nrhs - m0);
-	const int j = (int)(L % (unsigned)(JJ - 2)) + 1, k = (int)(L / (unsigned)(JJ - 2)) + 1;
-	const size_t sj = II, sk = (size_t)II * JJ, PS = sk * KK;
-	const size_t row = sj * (size_t)j + sk * (size_t)k;
-	// the four neighbour rows, wrapped (uniform over the workgroup)
-	const size_t rs = sj * (size_t)wrap_lo(j - 1, JJ, pd.y) + sk * (size_t)k, rn = sj * (size_t)wrap_hi(j + 1, JJ, pd.y) + sk * (size_t)k;
-	const size_t rb = sj * (size_t)j + sk * (size_t)wrap_lo(k - 1, KK, pd.z), rt = sj * (size_t)j + sk * (size_t)wrap_hi(k + 1, KK, pd.z);
-	for (int t = 0; t < nitems; t++) accl[t][threadIdx.x] = 0.0;
-	for (int i = threadIdx.x + 1; i <= II - 2; i += blockDim.x) {
-		const size_t x = row + (size_t)i;
-		const size_t xw = row + (size_t)wrap_lo(i - 1, II, pd.x), xe = row + (size_t)wrap_hi(i + 1, II, pd.x);
-		const real_t cp = so[KP * PS + x], cw = so[KPW * PS + x], cn = so[KPS * PS + x + sj], ce = so[KPW * PS + x + 1];
-		const real_t cs = so[KPS * PS + x], cb = so[KB * PS + x], ct = so[KB * PS + x + sk];
-#pragma unroll 1
-		for (int t = 0; t < nitems; t++) {
-			const int m = m0 + t;
-			if (!item_on(active, m)) continue;
-			const size_t off = (size_t)m * stride;
-			const real_t *__restrict__ zm = z + off, *__restrict__ pm = FIRST ? zm : p + off;
-			const real_t beta = FIRST ? 0.0 : sc[(size_t)m * PCG_NSC + PCG_BETA];
-			auto P = [&](size_t y) -> real_t { return FIRST ? zm[y] : zm[y] + beta * pm[y]; };
-			const real_t pc = P(x);
-			real_t s = cp * pc;
-			s = s - cw * P(xw);
-			s = s - cn * P(rn + (size_t)i);
-			s = s - ce * P(xe);
-			s = s - cs * P(rs + (size_t)i);
-			s = s - cb * P(rb + (size_t)i);
-			s = s - ct * P(rt + (size_t)i);
-			pn[off + x] = pc;
-			w[off + x] = s;
-			accl[t][threadIdx.x] += pc * s;
-		}
-	}
-	for (int t = 0; t < nitems; t++) {
-		const int m = m0 + t;
-		if (!item_on(active, m)) continue; // uniform over the workgroup
-		const real_t v = block_sum_k<256>(accl[t][threadIdx.x], lds);
-		if (threadIdx.x == 0) part[(size_t)m * nrows + L] = v;
-	}
-}
-
-// 27-point, rows of one trip (longer rows: pcg_dir27_per item by item, pcg_direction_periodic_many).  The 52 coefficients
+// 27-point on a batch of a periodic level (cedar_amd_solver_fcg_periodic_many): pcg_dir27_per's wrap rule with
+// pcg_dir27_many's item loop; per item the expressions, their order and the sums are pcg_dir27_per's.  Rows of one trip
+// (longer rows: pcg_dir27_per item by item, pcg_direction_periodic_many).  The 52 coefficients
 // and the diagonal pair are fetched once, from the Cedar planes (a periodic level has no row-interleaved copy), and stay
 // in registers across the items; one window set is live at a time.  Per item the nine window rows are loaded as
 // pcg_dir27_per loads them, every load before any patch; the i patch follows under the uniform `if (pd.x)`.
@@ -934,21 +898,7 @@ __global__ __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(2))) void pc
 						}
 				}
 			}
-			const real_t we = mv27(de, ce, qe);
-			const real_t pe = qe[1][1][1];
-			acc += pe * we;
-			if (o_ok) {
-				const real_t wo = mv27(dn, co, qo);
-				const real_t po = qo[1][1][1];
-				acc += po * wo;
-				d2u v; v.x = we; v.y = wo;
-				*reinterpret_cast<d2u *>(w + off + row + ie) = v;
-				v.x = pe; v.y = po;
-				*reinterpret_cast<d2u *>(pn + off + row + ie) = v;
-			} else {
-				w[off + row + ie] = we;
-				pn[off + row + ie] = pe;
-			}
+			dir27_emit(de, dn, ce, co, qe, qo, o_ok, w, pn, off, row, ie, acc);
 		}
 		const real_t t = block_sum_k<BS>(acc, lds);
 		if (threadIdx.x == 0) part[(size_t)m * nblk + L] = t;
@@ -1134,211 +1084,196 @@ __global__ __launch_bounds__(RED_BS) void pcg_rho_flex_many(const real_t *__rest
 	if (threadIdx.x == 0) set_rho_flex(rr, rz, wz, first, sc + (size_t)m * PCG_NSC);
 }
 
+// ---------------------------------------------------------------- launchers
+// a run-time switch as a compile-time constant: f(std::bool_constant<b>), f(std::integral_constant<int, V>) for the V
+// that v equals (none: the last)
+template <class F>
+void with_bool(bool b, F &&f) { b ? f(std::true_type{}) : f(std::false_type{}); }
+
+template <int V, int... Vs, class F>
+void with_int(int v, F &&f)
+{
+	if constexpr (sizeof...(Vs) > 0) {
+		if (v != V) return with_int<Vs...>(v, f);
+	}
+	f(std::integral_constant<int, V>{});
+}
+
+unsigned item_chunks(int nrhs) { return (unsigned)((nrhs + ITEM_CHUNK - 1) / ITEM_CHUNK); }
+
+// The launch geometry of a direction pass on nrhs items (the single pass: 1) and its slab layout: one partial per
+// workgroup task, n per item.  2D: the item in grid.z; 7-point: the item chunk in grid.y; 27-point: the items are walked
+// inside the workgroup, which is as wide as the row's pairs need.
+struct DirGeom {
+	int nd, nst;
+	dim3 grid;
+	int bs;     // workgroup width
+	unsigned n; // slab entries of one item
+	Op3 A;      // 27-point: the operator view, the tile walk and the pairs of a row
+	TileShape ts;
+	int npairs;
+};
+
+DirGeom dir_geom(const real_t *so, const Op3 *op27, int nd, int nst, int II, int JJ, int KK, int nrhs)
+{
+	DirGeom g{};
+	g.nd = nd, g.nst = nst;
+	if (nd == 2) {
+		g.grid = dim3((II - 2 + 255) / 256, JJ - 2, nrhs);
+		g.bs = 256;
+		g.n = g.grid.x * g.grid.y;
+	} else if (nst == 4) {
+		g.n = (unsigned)(JJ - 2) * (unsigned)(KK - 2);
+		g.bs = II - 2 >= 256 ? 256 : (II - 2 > 64 ? 128 : 64);
+		g.grid = dim3(xcd_grid(g.n), item_chunks(nrhs));
+	} else {
+		g.A = op27 ? *op27 : op3_cedar(so, nullptr, II, JJ, KK);
+		g.ts = tile_shape_resid();
+		g.n = tile_blocks((unsigned)(JJ - 2), (unsigned)(KK - 2), g.ts);
+		g.npairs = (II - 2 + 1) / 2;
+		g.bs = g.npairs <= 64 ? 64 : g.npairs <= 128 ? 128 : 256;
+		g.grid = dim3(xcd_grid(g.n));
+	}
+	return g;
+}
+
+// launches the direction kernel of g: k2(NINE, FIRST), k7(FIRST) or k27(BS, FIRST) launches its instantiation
+template <class K2, class K7, class K27>
+void dir_launch(const DirGeom &g, bool first, K2 &&k2, K7 &&k7, K27 &&k27)
+{
+	with_bool(first, [&](auto F) {
+		if (g.nd == 2) with_bool(g.nst == 5, [&](auto NINE) { k2(NINE, F); });
+		else if (g.nst == 4) k7(F);
+		else with_int<64, 128, 256>(g.bs, [&](auto BS) { k27(BS, F); });
+	});
+}
+
+// A batched pass and its second stage.  The batched 27-point kernels take rows of one trip; longer rows go through the
+// single pass item by item (its second stage included): one(m, slab_m, sc_m).
+template <class ONE, class K2, class K7, class K27>
+void dir_launch_many(const DirGeom &g, bool first, size_t ld, real_t *slab, real_t *sc, hipStream_t st, Batch bt, unsigned active,
+                     ONE &&one, K2 &&k2, K7 &&k7, K27 &&k27)
+{
+	if (g.npairs > 256) {
+		for (int m = 0; m < bt.n; m++)
+			if ((active >> m) & 1u) one(m, slab + m * ld, sc + (size_t)m * PCG_NSC);
+		return;
+	}
+	dir_launch(g, first, k2, k7, k27);
+	hipLaunchKernelGGL(pcg_alpha_many, dim3(bt.n), dim3(RED_BS), 0, st, slab, g.n, (size_t)g.n, sc, active);
+}
+
+// the workgroups of pcg_upd / pcg_dwz and their batched forms: one per row up to UPD_NB
+unsigned upd_blocks(int JJ, int KK)
+{
+	const size_t nrows = (size_t)(JJ - 2) * (KK == 1 ? 1 : KK - 2);
+	return (unsigned)std::min<size_t>(UPD_NB, nrows);
+}
+
+// the rho stages' has_rz of a zmode: 0 r.r only (zmode 3), 1 r.z in the second slab section, 2 r.z = r.r (zmode 0)
+int has_rz(int zmode) { return zmode == 3 ? 0 : zmode == 0 ? 2 : 1; }
+
 } // namespace
 
 size_t pcg_slab_doubles(int nd, int nst, int II, int JJ, int KK)
 {
-	size_t n = 3 * (size_t)UPD_NB; // pcg_dots_wz: three sections
-	if (nd == 2) n = std::max(n, (size_t)((II - 2 + 255) / 256) * (size_t)(JJ - 2));
-	else if (nst == 14) n = std::max(n, (size_t)tile_blocks((unsigned)(JJ - 2), (unsigned)(KK - 2), tile_shape_resid()));
-	else n = std::max(n, (size_t)(JJ - 2) * (size_t)(KK - 2));
-	return n;
+	return std::max(3 * (size_t)UPD_NB, (size_t)dir_geom(nullptr, nullptr, nd, nst, II, JJ, KK, 1).n); // pcg_dots_wz: three sections
 }
 
 void pcg_direction(const real_t *so, const Op3 *op27, const real_t *z, const real_t *p, real_t *pn, real_t *w, int nd,
                    int nst, int II, int JJ, int KK, bool first, real_t *slab, real_t *sc, hipStream_t st,
                    real_t *partial)
 {
-	unsigned n = 0;
-	if (nd == 2) {
-		dim3 grid((II - 2 + 255) / 256, JJ - 2);
-		n = grid.x * grid.y;
-#define L2_(NINE, F) hipLaunchKernelGGL((pcg_dir2<NINE, F>), grid, dim3(256), 0, st, so, z, p, pn, w, sc, II, JJ, slab)
-		if (nst == 5) { if (first) L2_(true, true); else L2_(true, false); }
-		else { if (first) L2_(false, true); else L2_(false, false); }
-#undef L2_
-	} else if (nst == 4) {
-		n = (unsigned)(JJ - 2) * (unsigned)(KK - 2);
-		const int bs = II - 2 >= 256 ? 256 : (II - 2 > 64 ? 128 : 64);
-		if (first) hipLaunchKernelGGL(pcg_dir7<true>, dim3(xcd_grid(n)), dim3(bs), 0, st, so, z, p, pn, w, sc, II, JJ, KK, n, slab);
-		else hipLaunchKernelGGL(pcg_dir7<false>, dim3(xcd_grid(n)), dim3(bs), 0, st, so, z, p, pn, w, sc, II, JJ, KK, n, slab);
-	} else {
-		const Op3 A = op27 ? *op27 : op3_cedar(so, nullptr, II, JJ, KK);
-		const TileShape ts = tile_shape_resid();
-		n = tile_blocks((unsigned)(JJ - 2), (unsigned)(KK - 2), ts);
-		const int npairs = (II - 2 + 1) / 2;
-#define L27_(BS, F) hipLaunchKernelGGL((pcg_dir27<BS, F>), dim3(xcd_grid(n)), dim3(BS), 0, st, A, z, p, pn, w, sc, II, JJ, KK, n, ts, slab)
-		if (npairs <= 64) { if (first) L27_(64, true); else L27_(64, false); }
-		else if (npairs <= 128) { if (first) L27_(128, true); else L27_(128, false); }
-		else { if (first) L27_(256, true); else L27_(256, false); }
-#undef L27_
-	}
-	if (partial) hipLaunchKernelGGL(pcg_partial, dim3(1), dim3(RED_BS), 0, st, slab, n, 1, partial);
-	else hipLaunchKernelGGL(pcg_alpha, dim3(1), dim3(RED_BS), 0, st, slab, n, sc);
+	const DirGeom g = dir_geom(so, op27, nd, nst, II, JJ, KK, 1);
+	dir_launch(
+	    g, first,
+	    [&](auto NINE, auto F) { hipLaunchKernelGGL((pcg_dir2<NINE(), F()>), g.grid, dim3(g.bs), 0, st, so, z, p, pn, w, sc, II, JJ, slab); },
+	    [&](auto F) { hipLaunchKernelGGL(pcg_dir7<F()>, g.grid, dim3(g.bs), 0, st, so, z, p, pn, w, sc, II, JJ, KK, g.n, slab); },
+	    [&](auto BS, auto F) { hipLaunchKernelGGL((pcg_dir27<BS(), F()>), g.grid, dim3(g.bs), 0, st, g.A, z, p, pn, w, sc, II, JJ, KK, g.n, g.ts, slab); });
+	if (partial) hipLaunchKernelGGL(pcg_partial, dim3(1), dim3(RED_BS), 0, st, slab, g.n, 1, partial);
+	else hipLaunchKernelGGL(pcg_alpha, dim3(1), dim3(RED_BS), 0, st, slab, g.n, sc);
 }
 
-// pcg_direction's launch geometry (grid, workgroup width, slab layout) and second stage with the wrap-around kernels
 void pcg_direction_periodic(const real_t *so, const real_t *z, const real_t *p, real_t *pn, real_t *w, int nd, int nst, int II,
                             int JJ, int KK, int ibc, bool first, real_t *slab, real_t *sc, hipStream_t st, real_t *partial)
 {
 	const PerDirs pd = per_dirs(nd, ibc);
-	unsigned n = 0;
-	if (nd == 2) {
-		dim3 grid((II - 2 + 255) / 256, JJ - 2);
-		n = grid.x * grid.y;
-#define L2_(NINE, F) hipLaunchKernelGGL((pcg_dir2_per<NINE, F>), grid, dim3(256), 0, st, so, z, p, pn, w, sc, II, JJ, pd, slab)
-		if (nst == 5) { if (first) L2_(true, true); else L2_(true, false); }
-		else { if (first) L2_(false, true); else L2_(false, false); }
-#undef L2_
-	} else if (nst == 4) {
-		n = (unsigned)(JJ - 2) * (unsigned)(KK - 2);
-		const int bs = II - 2 >= 256 ? 256 : (II - 2 > 64 ? 128 : 64);
-		if (first) hipLaunchKernelGGL(pcg_dir7_per<true>, dim3(xcd_grid(n)), dim3(bs), 0, st, so, z, p, pn, w, sc, II, JJ, KK, n, pd, slab);
-		else hipLaunchKernelGGL(pcg_dir7_per<false>, dim3(xcd_grid(n)), dim3(bs), 0, st, so, z, p, pn, w, sc, II, JJ, KK, n, pd, slab);
-	} else {
-		const Op3 A = op3_cedar(so, nullptr, II, JJ, KK);
-		const TileShape ts = tile_shape_resid();
-		n = tile_blocks((unsigned)(JJ - 2), (unsigned)(KK - 2), ts);
-		const int npairs = (II - 2 + 1) / 2;
-#define L27_(BS, F) hipLaunchKernelGGL((pcg_dir27_per<BS, F>), dim3(xcd_grid(n)), dim3(BS), 0, st, A, z, p, pn, w, sc, II, JJ, KK, n, ts, pd, slab)
-		if (npairs <= 64) { if (first) L27_(64, true); else L27_(64, false); }
-		else if (npairs <= 128) { if (first) L27_(128, true); else L27_(128, false); }
-		else { if (first) L27_(256, true); else L27_(256, false); }
-#undef L27_
-	}
-	if (partial) hipLaunchKernelGGL(pcg_partial, dim3(1), dim3(RED_BS), 0, st, slab, n, 1, partial);
-	else hipLaunchKernelGGL(pcg_alpha, dim3(1), dim3(RED_BS), 0, st, slab, n, sc);
+	const DirGeom g = dir_geom(so, nullptr, nd, nst, II, JJ, KK, 1); // a periodic level is read from its Cedar planes
+	dir_launch(
+	    g, first,
+	    [&](auto NINE, auto F) { hipLaunchKernelGGL((pcg_dir2_per<NINE(), F()>), g.grid, dim3(g.bs), 0, st, so, z, p, pn, w, sc, II, JJ, pd, slab); },
+	    [&](auto F) { hipLaunchKernelGGL(pcg_dir7_per<F()>, g.grid, dim3(g.bs), 0, st, so, z, p, pn, w, sc, II, JJ, KK, g.n, pd, slab); },
+	    [&](auto BS, auto F) { hipLaunchKernelGGL((pcg_dir27_per<BS(), F()>), g.grid, dim3(g.bs), 0, st, g.A, z, p, pn, w, sc, II, JJ, KK, g.n, g.ts, pd, slab); });
+	if (partial) hipLaunchKernelGGL(pcg_partial, dim3(1), dim3(RED_BS), 0, st, slab, g.n, 1, partial);
+	else hipLaunchKernelGGL(pcg_alpha, dim3(1), dim3(RED_BS), 0, st, slab, g.n, sc);
 }
 
 void pcg_update(int zmode, bool move, real_t *x, real_t *r, const real_t *p, const real_t *w, real_t *z,
                 const real_t *diag, int II, int JJ, int KK, bool first, real_t *slab, real_t *sc, hipStream_t st,
                 real_t *partial)
 {
-	const size_t nrows = (size_t)(JJ - 2) * (KK == 1 ? 1 : KK - 2);
-	const unsigned nb = (unsigned)std::min<size_t>(UPD_NB, nrows);
-#define LU_(ZM, MV) hipLaunchKernelGGL((pcg_upd<ZM, MV>), dim3(nb), dim3(256), 0, st, x, r, p, w, z, diag, sc, II, JJ, KK, slab)
-	switch (zmode * 2 + (move ? 1 : 0)) {
-	case 0: LU_(0, false); break;
-	case 1: LU_(0, true); break;
-	case 2: LU_(1, false); break;
-	case 3: LU_(1, true); break;
-	case 4: LU_(2, false); break;
-	case 5: LU_(2, true); break;
-	case 6: LU_(3, false); break;
-	default: LU_(3, true); break;
-	}
-#undef LU_
-	const int has_rz = zmode == 3 ? 0 : zmode == 0 ? 2 : 1; // 2: r.z = r.r
-	if (!partial) hipLaunchKernelGGL(pcg_rho, dim3(1), dim3(RED_BS), 0, st, slab, nb, has_rz, first ? 1 : 0, sc);
-	else if (zmode != 3) hipLaunchKernelGGL(pcg_partial, dim3(1), dim3(RED_BS), 0, st, slab, nb, has_rz == 1 ? 2 : 1, partial);
+	const unsigned nb = upd_blocks(JJ, KK);
+	with_int<0, 1, 2, 3>(zmode, [&](auto ZM) {
+		with_bool(move, [&](auto MV) {
+			hipLaunchKernelGGL((pcg_upd<ZM(), MV()>), dim3(nb), dim3(256), 0, st, x, r, p, w, z, diag, sc, II, JJ, KK, slab);
+		});
+	});
+	if (!partial) hipLaunchKernelGGL(pcg_rho, dim3(1), dim3(RED_BS), 0, st, slab, nb, has_rz(zmode), first ? 1 : 0, sc);
+	else if (zmode != 3) hipLaunchKernelGGL(pcg_partial, dim3(1), dim3(RED_BS), 0, st, slab, nb, has_rz(zmode) == 1 ? 2 : 1, partial);
 }
 
 void pcg_direction_many(const real_t *so, const Op3 *op27, const real_t *z, const real_t *p, real_t *pn, real_t *w, int nd,
                         int nst, int II, int JJ, int KK, bool first, real_t *slab, real_t *sc, hipStream_t st, Batch bt,
                         unsigned active)
 {
-	const size_t ld = pcg_slab_doubles(nd, nst, II, JJ, KK); // item stride of the slab
-	const unsigned chunks = (unsigned)((bt.n + ITEM_CHUNK - 1) / ITEM_CHUNK);
-	unsigned n = 0;
-	if (nd == 2) {
-		dim3 grid((II - 2 + 255) / 256, JJ - 2, bt.n);
-		n = grid.x * grid.y;
-#define L2_(NINE, F) hipLaunchKernelGGL((pcg_dir2_many<NINE, F>), grid, dim3(256), 0, st, so, z, p, pn, w, sc, II, JJ, slab, bt.stride, active)
-		if (nst == 5) { if (first) L2_(true, true); else L2_(true, false); }
-		else { if (first) L2_(false, true); else L2_(false, false); }
-#undef L2_
-	} else if (nst == 4) {
-		n = (unsigned)(JJ - 2) * (unsigned)(KK - 2);
-		const int bs = II - 2 >= 256 ? 256 : (II - 2 > 64 ? 128 : 64);
-		const dim3 grid(xcd_grid(n), chunks);
-		if (first) hipLaunchKernelGGL(pcg_dir7_many<true>, grid, dim3(bs), 0, st, so, z, p, pn, w, sc, II, JJ, KK, n, slab, bt.n, bt.stride, active);
-		else hipLaunchKernelGGL(pcg_dir7_many<false>, grid, dim3(bs), 0, st, so, z, p, pn, w, sc, II, JJ, KK, n, slab, bt.n, bt.stride, active);
-	} else {
-		const int npairs = (II - 2 + 1) / 2;
-		if (npairs > 256) { // rows of more than one trip: the single-vector pass item by item (its second stage included)
-			for (int m = 0; m < bt.n; m++)
-				if ((active >> m) & 1u)
-					pcg_direction(so, op27, z + m * bt.stride, first ? nullptr : p + m * bt.stride, pn + m * bt.stride,
-					              w + m * bt.stride, nd, nst, II, JJ, KK, first, slab + m * ld, sc + (size_t)m * PCG_NSC, st);
-			return;
-		}
-		const Op3 A = op27 ? *op27 : op3_cedar(so, nullptr, II, JJ, KK);
-		const TileShape ts = tile_shape_resid();
-		n = tile_blocks((unsigned)(JJ - 2), (unsigned)(KK - 2), ts);
-#define L27_(BS, F) hipLaunchKernelGGL((pcg_dir27_many<BS, F>), dim3(xcd_grid(n)), dim3(BS), 0, st, A, z, p, pn, w, sc, II, JJ, KK, n, ts, slab, bt.n, bt.stride, active)
-		if (npairs <= 64) { if (first) L27_(64, true); else L27_(64, false); }
-		else if (npairs <= 128) { if (first) L27_(128, true); else L27_(128, false); }
-		else { if (first) L27_(256, true); else L27_(256, false); }
-#undef L27_
-	}
-	hipLaunchKernelGGL(pcg_alpha_many, dim3(bt.n), dim3(RED_BS), 0, st, slab, n, (size_t)n, sc, active);
+	const DirGeom g = dir_geom(so, op27, nd, nst, II, JJ, KK, bt.n);
+	dir_launch_many(
+	    g, first, pcg_slab_doubles(nd, nst, II, JJ, KK), slab, sc, st, bt, active,
+	    [&](int m, real_t *slab_m, real_t *sc_m) {
+		    pcg_direction(so, op27, z + m * bt.stride, first ? nullptr : p + m * bt.stride, pn + m * bt.stride, w + m * bt.stride, nd,
+		                  nst, II, JJ, KK, first, slab_m, sc_m, st);
+	    },
+	    [&](auto NINE, auto F) { hipLaunchKernelGGL((pcg_dir2_many<NINE(), F()>), g.grid, dim3(g.bs), 0, st, so, z, p, pn, w, sc, II, JJ, slab, bt.stride, active); },
+	    [&](auto F) { hipLaunchKernelGGL(pcg_dir7_many<F()>, g.grid, dim3(g.bs), 0, st, so, z, p, pn, w, sc, II, JJ, KK, g.n, slab, bt.n, bt.stride, active); },
+	    [&](auto BS, auto F) { hipLaunchKernelGGL((pcg_dir27_many<BS(), F()>), g.grid, dim3(g.bs), 0, st, g.A, z, p, pn, w, sc, II, JJ, KK, g.n, g.ts, slab, bt.n, bt.stride, active); });
 }
 
-// pcg_direction_many's launch geometry, slab layout and second stage with the wrap-around kernels (3D; a periodic level is
-// read from its Cedar planes)
+// 3D; a periodic level is read from its Cedar planes
 void pcg_direction_periodic_many(const real_t *so, const real_t *z, const real_t *p, real_t *pn, real_t *w, int nst, int II,
                                  int JJ, int KK, int ibc, bool first, real_t *slab, real_t *sc, hipStream_t st, Batch bt,
                                  unsigned active)
 {
 	const PerDirs pd = per_dirs(3, ibc);
-	const size_t ld = pcg_slab_doubles(3, nst, II, JJ, KK); // item stride of the slab
-	const unsigned chunks = (unsigned)((bt.n + ITEM_CHUNK - 1) / ITEM_CHUNK);
-	unsigned n = 0;
-	if (nst == 4) {
-		n = (unsigned)(JJ - 2) * (unsigned)(KK - 2);
-		const int bs = II - 2 >= 256 ? 256 : (II - 2 > 64 ? 128 : 64);
-		const dim3 grid(xcd_grid(n), chunks);
-		if (first) hipLaunchKernelGGL(pcg_dir7_per_many<true>, grid, dim3(bs), 0, st, so, z, p, pn, w, sc, II, JJ, KK, n, pd, slab, bt.n, bt.stride, active);
-		else hipLaunchKernelGGL(pcg_dir7_per_many<false>, grid, dim3(bs), 0, st, so, z, p, pn, w, sc, II, JJ, KK, n, pd, slab, bt.n, bt.stride, active);
-	} else {
-		const int npairs = (II - 2 + 1) / 2;
-		if (npairs > 256) { // rows of more than one trip: the single-vector pass item by item (its second stage included)
-			for (int m = 0; m < bt.n; m++)
-				if ((active >> m) & 1u)
-					pcg_direction_periodic(so, z + m * bt.stride, first ? nullptr : p + m * bt.stride, pn + m * bt.stride,
-					                       w + m * bt.stride, 3, nst, II, JJ, KK, ibc, first, slab + m * ld, sc + (size_t)m * PCG_NSC, st);
-			return;
-		}
-		const Op3 A = op3_cedar(so, nullptr, II, JJ, KK);
-		const TileShape ts = tile_shape_resid();
-		n = tile_blocks((unsigned)(JJ - 2), (unsigned)(KK - 2), ts);
-#define L27_(BS, F) hipLaunchKernelGGL((pcg_dir27_per_many<BS, F>), dim3(xcd_grid(n)), dim3(BS), 0, st, A, z, p, pn, w, sc, II, JJ, KK, n, ts, pd, slab, bt.n, bt.stride, active)
-		if (npairs <= 64) { if (first) L27_(64, true); else L27_(64, false); }
-		else if (npairs <= 128) { if (first) L27_(128, true); else L27_(128, false); }
-		else { if (first) L27_(256, true); else L27_(256, false); }
-#undef L27_
-	}
-	hipLaunchKernelGGL(pcg_alpha_many, dim3(bt.n), dim3(RED_BS), 0, st, slab, n, (size_t)n, sc, active);
+	const DirGeom g = dir_geom(so, nullptr, 3, nst, II, JJ, KK, bt.n);
+	dir_launch_many(
+	    g, first, pcg_slab_doubles(3, nst, II, JJ, KK), slab, sc, st, bt, active,
+	    [&](int m, real_t *slab_m, real_t *sc_m) {
+		    pcg_direction_periodic(so, z + m * bt.stride, first ? nullptr : p + m * bt.stride, pn + m * bt.stride, w + m * bt.stride, 3,
+		                           nst, II, JJ, KK, ibc, first, slab_m, sc_m, st);
+	    },
+	    [](auto, auto) {}, // no 2D level here
+	    [&](auto F) { hipLaunchKernelGGL(pcg_dir7_per_many<F()>, g.grid, dim3(g.bs), 0, st, so, z, p, pn, w, sc, II, JJ, KK, g.n, pd, slab, bt.n, bt.stride, active); },
+	    [&](auto BS, auto F) { hipLaunchKernelGGL((pcg_dir27_per_many<BS(), F()>), g.grid, dim3(g.bs), 0, st, g.A, z, p, pn, w, sc, II, JJ, KK, g.n, g.ts, pd, slab, bt.n, bt.stride, active); });
 }
 
 void pcg_update_many(int zmode, bool move, real_t *x, real_t *r, const real_t *p, const real_t *w, real_t *z,
                      const real_t *diag, int II, int JJ, int KK, bool first, real_t *slab, real_t *sc, hipStream_t st,
                      Batch bt, unsigned active)
 {
-	const size_t nrows = (size_t)(JJ - 2) * (KK == 1 ? 1 : KK - 2);
-	const unsigned nb = (unsigned)std::min<size_t>(UPD_NB, nrows);
-	const dim3 grid(nb, (unsigned)((bt.n + ITEM_CHUNK - 1) / ITEM_CHUNK));
-#define LU_(ZM, MV) hipLaunchKernelGGL((pcg_upd_many<ZM, MV>), grid, dim3(256), 0, st, x, r, p, w, z, diag, sc, II, JJ, KK, slab, bt.n, bt.stride, active)
-	switch (zmode * 2 + (move ? 1 : 0)) {
-	case 0: LU_(0, false); break;
-	case 1: LU_(0, true); break;
-	case 2: LU_(1, false); break;
-	case 3: LU_(1, true); break;
-	case 4: LU_(2, false); break;
-	case 5: LU_(2, true); break;
-	case 6: LU_(3, false); break;
-	default: LU_(3, true); break;
-	}
-#undef LU_
-	const int has_rz = zmode == 3 ? 0 : zmode == 0 ? 2 : 1; // 2: r.z = r.r
-	hipLaunchKernelGGL(pcg_rho_many, dim3(bt.n), dim3(RED_BS), 0, st, slab, nb, (size_t)2 * nb, has_rz, first ? 1 : 0, sc, active);
+	const unsigned nb = upd_blocks(JJ, KK);
+	const dim3 grid(nb, item_chunks(bt.n));
+	with_int<0, 1, 2, 3>(zmode, [&](auto ZM) {
+		with_bool(move, [&](auto MV) {
+			hipLaunchKernelGGL((pcg_upd_many<ZM(), MV()>), grid, dim3(256), 0, st, x, r, p, w, z, diag, sc, II, JJ, KK, slab, bt.n, bt.stride, active);
+		});
+	});
+	hipLaunchKernelGGL(pcg_rho_many, dim3(bt.n), dim3(RED_BS), 0, st, slab, nb, (size_t)2 * nb, has_rz(zmode), first ? 1 : 0, sc, active);
 }
 
 void pcg_dots_wz(const real_t *r, const real_t *z, const real_t *w, int II, int JJ, int KK, bool first, real_t *slab,
                  real_t *sc, hipStream_t st)
 {
-	const size_t nrows = (size_t)(JJ - 2) * (KK == 1 ? 1 : KK - 2);
-	const unsigned nb = (unsigned)std::min<size_t>(UPD_NB, nrows);
+	const unsigned nb = upd_blocks(JJ, KK);
 	hipLaunchKernelGGL(pcg_dwz, dim3(nb), dim3(256), 0, st, r, z, w, II, JJ, KK, slab);
 	hipLaunchKernelGGL(pcg_rho_flex, dim3(1), dim3(RED_BS), 0, st, slab, nb, first ? 1 : 0, sc);
 }
@@ -1346,9 +1281,8 @@ void pcg_dots_wz(const real_t *r, const real_t *z, const real_t *w, int II, int 
 void pcg_dots_wz_many(const real_t *r, const real_t *z, const real_t *w, int II, int JJ, int KK, bool first, real_t *slab,
                       real_t *sc, hipStream_t st, Batch bt, unsigned active)
 {
-	const size_t nrows = (size_t)(JJ - 2) * (KK == 1 ? 1 : KK - 2);
-	const unsigned nb = (unsigned)std::min<size_t>(UPD_NB, nrows);
-	const dim3 grid(nb, (unsigned)((bt.n + ITEM_CHUNK - 1) / ITEM_CHUNK));
+	const unsigned nb = upd_blocks(JJ, KK);
+	const dim3 grid(nb, item_chunks(bt.n));
 	hipLaunchKernelGGL(pcg_dwz_many, grid, dim3(256), 0, st, r, z, w, II, JJ, KK, slab, bt.n, bt.stride, active);
 	hipLaunchKernelGGL(pcg_rho_flex_many, dim3(bt.n), dim3(RED_BS), 0, st, slab, nb, (size_t)3 * nb, first ? 1 : 0, sc, active);
 }
@@ -1360,8 +1294,7 @@ void pcg_ranks_alpha(const real_t *gathered, int world, int stride, real_t *sc, 
 
 void pcg_ranks_rho(int zmode, const real_t *gathered, int world, int stride, bool first, real_t *sc, hipStream_t st)
 {
-	const int has_rz = zmode == 3 ? 0 : zmode == 0 ? 2 : 1;
-	hipLaunchKernelGGL(pcg_rho_ranks, dim3(1), dim3(64), 0, st, gathered, world, stride, has_rz, first ? 1 : 0, sc);
+	hipLaunchKernelGGL(pcg_rho_ranks, dim3(1), dim3(64), 0, st, gathered, world, stride, has_rz(zmode), first ? 1 : 0, sc);
 }
 
 void pcg_ghost_shell(const real_t *z, const real_t *p, real_t *pn, const real_t *sc, const ShellBoxes &bx, int II, int JJ,
