@@ -473,6 +473,52 @@ class Kernels:
                                                      _p(sc)) != 0:
             raise RuntimeError("cedar_amd_pcg_direction_periodic_many refused")
 
+    # ---- the batched periodic 2D kernels (periodic_many2d.hip, krylov.hip): the arguments of the single-vector 2D methods
+    # on vectors of shape (nrhs,) + grid, plus the boundary code ibc (1..3; 0 is refused except by the direction pass, which
+    # forwards to pcg_direction_many).  Item m gets the bits of the single-vector periodic method on item m alone.
+    # RuntimeError when the library refuses (nothing written)
+    def relax2_periodic_many(self, so, qf, q, sor, updown, ibc, nrhs=None):
+        nst, JJ, II = so.shape
+        assert qf.shape == q.shape and tuple(q.shape[1:]) == (JJ, II)
+        self._many("cedar_amd_relax2_gs_periodic_many",
+                   lib.cedar_amd_relax2_gs_periodic_many(q.shape[0] if nrhs is None else nrhs, _p(so), _p(qf), _p(q), _p(sor), u(II),
+                                                         u(JJ), nst, updown, int(ibc)))
+
+    def restrict2_periodic_many(self, q, qc, ci, ibc, nrhs=None):
+        """the ghosts of the fine vectors are refreshed first: q is written too"""
+        n, JJ, II = q.shape
+        nc, JJC, IIC = qc.shape
+        assert n == nc
+        self._many("cedar_amd_restrict2_periodic_many",
+                   lib.cedar_amd_restrict2_periodic_many(n if nrhs is None else nrhs, _p(q), _p(qc), _p(ci), u(II), u(JJ), u(IIC),
+                                                         u(JJC), int(ibc)))
+
+    def interp_add2_periodic_many(self, q, qc, res, so, ci, ibc, nrhs=None):
+        n, JJ, II = q.shape
+        nc, JJC, IIC = qc.shape
+        assert n == nc and res.shape == q.shape
+        self._many("cedar_amd_interp_add2_periodic_many",
+                   lib.cedar_amd_interp_add2_periodic_many(n if nrhs is None else nrhs, _p(q), _p(qc), _p(res), _p(so), _p(ci), u(IIC),
+                                                           u(JJC), u(II), u(JJ), so.shape[0], int(ibc)))
+
+    def solve_cg2_periodic_many(self, q, qf, abd, ibc, nrhs=None):
+        """abd: the dense factor setup_cg2(so, abd, ibc) left, shared by the items; one lane per item"""
+        n, JJ, II = q.shape
+        assert qf.shape == q.shape
+        n = n if nrhs is None else nrhs
+        bbd = np.zeros(max(n, 1) * abd.shape[0])
+        self._many("cedar_amd_solve_cg2_periodic_many",
+                   lib.cedar_amd_solve_cg2_periodic_many(n, _p(q), _p(qf), u(II), u(JJ), _p(abd), _p(bbd), u(abd.shape[1]), int(ibc)))
+
+    def pcg_direction2_periodic_many(self, so, z, p, pn, w, ibc, first, sc, nrhs=None, active=None):
+        """pcg_direction_many on a periodic 2D level: per item m the reads of pcg_direction_periodic"""
+        assert tuple(so.shape[1:]) == tuple(z.shape[1:]) and all(a is None or a.shape == z.shape for a in (p, pn, w))
+        n, act = self._batch(z, sc, nrhs, active)
+        JJ, II = z.shape[1:]
+        if lib.cedar_amd_pcg_direction2_periodic_many(n, act, _p(so), _p(z), _p(p), _p(pn), _p(w), u(II), u(JJ), so.shape[0],
+                                                      int(ibc), int(first), _p(sc)) != 0:
+            raise RuntimeError("cedar_amd_pcg_direction2_periodic_many refused")
+
     # ---- the transfers on the interpolation weights rounded to single precision (transferf.hip): a float copy of ci is built
     # for the call; arguments as the FP64 methods above (Dirichlet).  0 when served, non-zero when refused (nothing written)
     def restrict2_ci32(self, q, qc, ci):
@@ -630,6 +676,11 @@ for _f in (lib.cedar_amd_relax3_gs_many, lib.cedar_amd_residual3_many, lib.cedar
     _f.restype = C.c_int
 lib.cedar_amd_solver_create_many_periodic.restype = C.c_void_p
 lib.cedar_amd_solver_create_many_periodic.argtypes = lib.cedar_amd_solver_create_many.argtypes
+lib.cedar_amd_solver_create_many_periodic2.restype = C.c_void_p
+lib.cedar_amd_solver_create_many_periodic2.argtypes = [u, u, C.c_int, C.c_void_p, C.c_int, C.POINTER(Settings), C.c_int]
+for _f in (lib.cedar_amd_relax2_gs_periodic_many, lib.cedar_amd_restrict2_periodic_many, lib.cedar_amd_interp_add2_periodic_many,
+           lib.cedar_amd_solve_cg2_periodic_many, lib.cedar_amd_pcg_direction2_periodic_many):
+    _f.restype = C.c_int
 
 
 def _vp(a):
@@ -711,7 +762,7 @@ class Solver:
 
     def __init__(self, so, relax="point", nrelax_pre=2, nrelax_post=1, num_levels=-1,
                  max_iter=10, tol=1e-8, min_coarse=3, share_operator=False, cycle="v", ibc=0, plane=None, max_rhs=1,
-                 periodic_batch=False):
+                 periodic_batch=False, periodic_batch2d=False):
         shp = so.shape
         self.nd = len(shp) - 1
         nst = shp[0]
@@ -723,7 +774,12 @@ class Solver:
         plane_settings(st, plane)
         self.max_iter = max_iter
         self._so = so if share_operator else None  # keep the shared operator alive
-        if periodic_batch:  # a periodic 3D handle with room for max_rhs right-hand sides (ibc = 0: as max_rhs alone)
+        if periodic_batch2d:  # a periodic 2D handle with room for max_rhs right-hand sides (ibc = 0: as max_rhs alone)
+            if self.nd != 2:
+                raise ValueError("periodic_batch2d is for 2D operators; periodic_batch serves 3D")
+            self.h = lib.cedar_amd_solver_create_many_periodic2(nx, ny, nst, _vp(so), int(share_operator), C.byref(st),
+                                                                int(max_rhs))
+        elif periodic_batch:  # a periodic 3D handle with room for max_rhs right-hand sides (ibc = 0: as max_rhs alone)
             self.h = lib.cedar_amd_solver_create_many_periodic(self.nd, nx, ny, nz, nst, _vp(so), int(share_operator),
                                                                C.byref(st), int(max_rhs))
         elif max_rhs == 1:
@@ -854,7 +910,8 @@ class Solver:
         return self._cg_many("cedar_amd_solver_fcg_many", b, x, max_iter, tol, stop, precon, nmg_cycles, hist)
 
     def fcg_periodic_many(self, b, x, max_iter=50, tol=1e-8, stop="rel_l2", precon="mg", nmg_cycles=1, hist=None):
-        """fcg_periodic for the items of b, x in lockstep on a handle made with periodic_batch=True
+        """fcg_periodic for the items of b, x in lockstep on a handle made with periodic_batch=True (3D) or
+        periodic_batch2d=True (2D)
         (cedar_amd_solver_fcg_periodic_many); same arguments and return as fcg_many"""
         return self._cg_many("cedar_amd_solver_fcg_periodic_many", b, x, max_iter, tol, stop, precon, nmg_cycles, hist)
 

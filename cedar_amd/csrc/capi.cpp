@@ -1323,8 +1323,104 @@ int cedar_amd_pcg_direction_periodic_many(int nrhs, unsigned active, const real_
 	NanSlab slab(pcg_slab_doubles(3, nstncl, (int)ii, (int)jj, (int)kk) * nrhs);
 	Staged sso(so, P * nstncl, true, false), sz(z, N, true, false), sp(first ? nullptr : p, N, true, false),
 	    spn(pn, N, true, true), sw(w, N, true, true), ssc(sc, (size_t)PCG_NSC * nrhs, true, true);
-	pcg_direction_periodic_many(sso.get(), sz.get(), sp.get(), spn.get(), sw.get(), nstncl, (int)ii, (int)jj, (int)kk, ibc,
+	pcg_direction_periodic_many(sso.get(), sz.get(), sp.get(), spn.get(), sw.get(), 3, nstncl, (int)ii, (int)jj, (int)kk, ibc,
 	                            first != 0, slab.dev, ssc.get(), current_stream(), Batch{nrhs, P}, active);
+	return 0;
+}
+
+// ------------------------------------------------------------------ the batched periodic 2D kernels (periodic_many2d.hip,
+// krylov.hip), one launcher each: nrhs items back to back with stride ii*jj, the operator arrays shared.  Only the
+// direction pass has a Dirichlet batched twin behind a kernel-level call: the other four refuse ibc = 0
+static bool per_many2_refused(int nrhs, bool arrays_ok, bool nst_ok, int ibc, bool dirichlet_twin, const char *who)
+{
+	const char *why = nrhs < 1 || nrhs > CEDAR_AMD_MAX_RHS ? "nrhs must be 1 .. 32" : !nst_ok ? "nstncl must be 3 or 5"
+	                  : !arrays_ok ? "a required array is NULL" : ibc < 0 || ibc > 3 ? "the 2D boundary codes are 0 .. 3"
+	                  : ibc == 0 && !dirichlet_twin ? "ibc = 0 has no batched Dirichlet kernel-level call to go to" : nullptr;
+	if (!why) return false;
+	char msg[200];
+	snprintf(msg, sizeof(msg), "%s: %s; nothing done", who, why);
+	print_error(msg);
+	return true;
+}
+
+int cedar_amd_relax2_gs_periodic_many(int nrhs, real_t *so, real_t *qf, real_t *q, real_t *sor, len_t ii, len_t jj, int nstncl,
+                                      int updown, int ibc)
+{
+	const char *who = "cedar_amd_relax2_gs_periodic_many";
+	if (per_many2_refused(nrhs, so && qf && q && sor, nstncl == 3 || nstncl == 5, ibc, false, who)) return -1;
+	if ((size_t)ii * sizeof(real_t) > 64 * 1024) {
+		char msg[200];
+		snprintf(msg, sizeof(msg), "%s: periodic rows longer than 8192 points are not supported; nothing done", who);
+		print_error(msg);
+		return -1;
+	}
+	const size_t P = (size_t)ii * jj;
+	Staged sso(so, P * nstncl, true, false), sqf(qf, P * nrhs, true, false), sq(q, P * nrhs, true, true), ssor(sor, P * 2, true, false);
+	relax2_gs_per_many(sso.get(), sqf.get(), sq.get(), ssor.get(), (int)ii, (int)jj, nstncl, updown, ibc, current_stream(),
+	                   Batch{nrhs, P});
+	return 0;
+}
+
+// the fine vectors get their ghosts refreshed first, so q is an output too
+int cedar_amd_restrict2_periodic_many(int nrhs, real_t *q, real_t *qc, real_t *ci, len_t ii, len_t jj, len_t iic, len_t jjc, int ibc)
+{
+	if (per_many2_refused(nrhs, q && qc && ci, true, ibc, false, "cedar_amd_restrict2_periodic_many")) return -1;
+	const size_t P = (size_t)ii * jj, PC = (size_t)iic * jjc;
+	Staged sq(q, P * nrhs, true, true), sqc(qc, PC * nrhs, true, true), sci(ci, PC * 8, true, false);
+	restrict2_per_many(sq.get(), sqc.get(), sci.get(), (int)ii, (int)jj, (int)iic, (int)jjc, ibc, current_stream(), Batch{nrhs, P},
+	                   Batch{nrhs, PC});
+	return 0;
+}
+
+int cedar_amd_interp_add2_periodic_many(int nrhs, real_t *q, real_t *qc, real_t *res, real_t *so, real_t *ci, len_t iic, len_t jjc,
+                                        len_t ii, len_t jj, int nstncl, int ibc)
+{
+	const char *who = "cedar_amd_interp_add2_periodic_many";
+	if (per_many2_refused(nrhs, q && qc && res && so && ci, nstncl == 3 || nstncl == 5, ibc, false, who)) return -1;
+	const size_t P = (size_t)ii * jj, PC = (size_t)iic * jjc;
+	Staged sq(q, P * nrhs, true, true), sqc(qc, PC * nrhs, true, false), sr(res, P * nrhs, true, true),
+	    sso(so, P * nstncl, true, false), sci(ci, PC * 8, true, false);
+	interp_add2_per_many(sq.get(), sqc.get(), sr.get(), sso.get(), sci.get(), (int)iic, (int)jjc, (int)ii, (int)jj, ibc,
+	                     current_stream(), Batch{nrhs, P}, Batch{nrhs, PC});
+	return 0;
+}
+
+// abd: the dense factor of BMG2_SymStd_SETUP_cg_LU with a periodic code, nabd1 >= the number of unknowns; bbd: nrhs segments
+// of that many doubles
+int cedar_amd_solve_cg2_periodic_many(int nrhs, real_t *q, real_t *qf, len_t ii, len_t jj, real_t *abd, real_t *bbd, len_t nabd1,
+                                      int ibc)
+{
+	const char *who = "cedar_amd_solve_cg2_periodic_many";
+	if (per_many2_refused(nrhs, q && qf && abd && bbd, true, ibc, false, who)) return -1;
+	const size_t N = ii >= 3 && jj >= 3 ? (size_t)(ii - 2) * (jj - 2) : 0;
+	if (N == 0 || (size_t)nabd1 < N) {
+		char msg[200];
+		snprintf(msg, sizeof(msg), "%s: needs at least one unknown and the dense factor ABD(n,n); nothing done", who);
+		print_error(msg);
+		return -1;
+	}
+	const size_t P = (size_t)ii * jj;
+	Staged sq(q, P * nrhs, true, true), sqf(qf, P * nrhs, true, false), sabd(abd, (size_t)nabd1 * N, true, false),
+	    sb(bbd, N * nrhs, false, true);
+	solve_cg2_per_many(sq.get(), sqf.get(), (int)ii, (int)jj, sabd.get(), sb.get(), (int)nabd1, ibc, current_stream(),
+	                   Batch{nrhs, P});
+	return 0;
+}
+
+// the direction pass of a periodic 2D level on nrhs items; every item's slab NaN-filled
+int cedar_amd_pcg_direction2_periodic_many(int nrhs, unsigned active, const real_t *so, const real_t *z, const real_t *p,
+                                           real_t *pn, real_t *w, len_t ii, len_t jj, int nstncl, int ibc, int first, real_t *sc)
+{
+	const char *who = "cedar_amd_pcg_direction2_periodic_many";
+	if (per_many2_refused(nrhs, so && z && pn && w && sc && (first || p), nstncl == 3 || nstncl == 5, ibc, true, who)) return -1;
+	if (ibc == 0) return cedar_amd_pcg_direction_many(nrhs, active, so, z, p, pn, w, ii, jj, 1, nstncl, first, sc);
+	if (pcg_shape_refused(ii, jj, 1, who)) return -1;
+	const size_t P = (size_t)ii * jj, N = P * nrhs;
+	NanSlab slab(pcg_slab_doubles(2, nstncl, (int)ii, (int)jj, 1) * nrhs);
+	Staged sso(so, P * nstncl, true, false), sz(z, N, true, false), sp(first ? nullptr : p, N, true, false),
+	    spn(pn, N, true, true), sw(w, N, true, true), ssc(sc, (size_t)PCG_NSC * nrhs, true, true);
+	pcg_direction_periodic_many(sso.get(), sz.get(), sp.get(), spn.get(), sw.get(), 2, nstncl, (int)ii, (int)jj, 1, ibc, first != 0,
+	                            slab.dev, ssc.get(), current_stream(), Batch{nrhs, P}, active);
 	return 0;
 }
 

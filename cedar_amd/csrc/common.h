@@ -371,7 +371,7 @@ void setup_lines_x(const real_t *so, real_t *sor, int II, int JJ, hipStream_t st
 void setup_lines_y(const real_t *so, real_t *sor, int II, int JJ, hipStream_t st, int fold = 0);
 void relax_lines_x(const real_t *so, const real_t *qf, real_t *q, const real_t *sor,
                    int II, int JJ, int nstncl, int updown, hipStream_t st, int ipn = 0, const real_t *pf = nullptr,
-                   Batch bt = Batch()); // batches: Dirichlet lines only
+                   Batch bt = Batch()); // batches: stride II*JJ when ipn != 0 (the wraps take the items as planes)
 // scan-ordered copy of the line factors for the resident solver (lines.hip line_pttrs_pf); 0 doubles = not used
 size_t lines_permuted_doubles(int n, int nlines);
 void lines_permute(const real_t *sor, real_t *pf, int n, int ld, int nlines, size_t PS, hipStream_t st);
@@ -467,8 +467,8 @@ void pcg_update(int zmode, bool move, real_t *x, real_t *r, const real_t *p, con
 void pcg_direction_many(const real_t *so, const Op3 *op27, const real_t *z, const real_t *p, real_t *pn, real_t *w, int nd,
                         int nst, int II, int JJ, int KK, bool first, real_t *slab, real_t *sc, hipStream_t st, Batch bt,
                         unsigned active);
-// the direction pass of a periodic 3D level on a batch: pcg_direction_periodic per item, the operator fetched once
-void pcg_direction_periodic_many(const real_t *so, const real_t *z, const real_t *p, real_t *pn, real_t *w, int nst, int II,
+// the direction pass of a periodic level (2D or 3D) on a batch: pcg_direction_periodic per item, the operator fetched once
+void pcg_direction_periodic_many(const real_t *so, const real_t *z, const real_t *p, real_t *pn, real_t *w, int nd, int nst, int II,
                                  int JJ, int KK, int ibc, bool first, real_t *slab, real_t *sc, hipStream_t st, Batch bt,
                                  unsigned active);
 void pcg_update_many(int zmode, bool move, real_t *x, real_t *r, const real_t *p, const real_t *w, real_t *z,
@@ -525,6 +525,17 @@ void restrict3_per_many(real_t *q, real_t *qc, const real_t *ci, int II, int JJ,
 void interp_add3_per_many(real_t *q, const real_t *qc, const real_t *so, real_t *res, const real_t *ci, int IIC, int JJC,
                           int KKC, int IIF, int JJF, int KKF, int ipn, hipStream_t st, Batch bf, Batch bc);
 void solve_cg3_per_many(real_t *q, const real_t *qf, int II, int JJ, int KK, const real_t *abd, real_t *bbd, int nabd1, int ipn,
+                        hipStream_t st, Batch bt);
+// periodic_many2d.hip: the periodic 2D kernels on a batch stored with stride II*JJ (ipn = 1 per_y, 2 per_x, 3 per_xy), bit
+// for bit the single-vector periodic calls per item.  relax2_gs_per_many: 1 = rows too long; a batch with another stride
+// walks its items through relax2_gs_per.  bbd: bt.n segments of (II-2)(JJ-2) doubles
+int relax2_gs_per_many(const real_t *so, const real_t *qf, real_t *q, const real_t *sor, int II, int JJ, int nstncl, int updown,
+                       int ipn, hipStream_t st, Batch bt);
+void restrict2_per_many(real_t *q, real_t *qc, const real_t *ci, int Nx, int Ny, int Nxc, int Nyc, int ipn, hipStream_t st, Batch bf,
+                        Batch bc);
+void interp_add2_per_many(real_t *q, const real_t *qc, real_t *res, const real_t *so, const real_t *ci, int IIC, int JJC, int IIF,
+                          int JJF, int ipn, hipStream_t st, Batch bf, Batch bc);
+void solve_cg2_per_many(real_t *q, const real_t *qf, int II, int JJ, const real_t *abd, real_t *bbd, int nabd1, int ipn,
                         hipStream_t st, Batch bt);
 // gallery.hip (device-side generators of the reference's gallery operators)
 void gallery_fill(int which, real_t *so, real_t *b, int nx, int ny, int nz, const double *params, hipStream_t st);

@@ -654,6 +654,7 @@ constexpr unsigned UPD_NB = 2048;
 // Algorithmic bytes per interior point for n items:
 //   pcg_dir27_many  operator once 112 (interleaved copy 120) + n x (z, p read 16 + p', w written 16)  = 120 + 32 n
 //   pcg_dir7_many   4 x 8 + 32 n;   pcg_dir2_many  as pcg_dir2 per item (the item comes from the launch grid)
+//   pcg_dir2_per_many (periodic 2D levels: the items walked inside the workgroup)  5 x 8 (five-point: 3 x 8) + 32 n
 //   pcg_upd_many    48 n; precon = diag: 8 + 56 n
 constexpr int ITEM_CHUNK = 8; // items of one workgroup of pcg_dir7_many / pcg_upd_many (their per-lane sums live in LDS)
 
@@ -671,6 +672,74 @@ __global__ __launch_bounds__(256) void pcg_dir2_many(const real_t *__restrict__ 
 	const size_t off = (size_t)m * stride;
 	dir2_segment<NINE, FIRST, AdjPlain>(so, z + off, FIRST ? z : p + off, pn + off, w + off, sc + (size_t)m * PCG_NSC, II, JJ,
 	                                    PerDirs{}, part + (size_t)m * gridDim.x * gridDim.y);
+}
+
+// 2D on a level with periodic directions (cedar_amd_solver_fcg_periodic_many on a 2D handle): dir2_segment's task -- one
+// lane per point, one workgroup per 256-point segment of a row -- with all items walked inside it: the point's five or
+// nine operator entries and its (wrapped) neighbour addresses are formed once and applied to every active item, whose
+// sum is taken by block_sum_k as dir2_segment takes it.  Item m's pn, w and slab have the bits of pcg_direction_periodic
+// on item m alone; a masked item is neither read nor written.
+template <bool NINE, bool FIRST, class ADJ>
+__device__ __forceinline__ void dir2_items(const real_t *__restrict__ so, const real_t *__restrict__ z,
+                                           const real_t *__restrict__ p, real_t *__restrict__ pn, real_t *__restrict__ w,
+                                           const real_t *__restrict__ sc, int II, int JJ, PerDirs pd, real_t *__restrict__ part,
+                                           int nrhs, size_t stride, unsigned active)
+{
+	__shared__ real_t lds[4];
+	const int i = blockIdx.x * blockDim.x + threadIdx.x + 1;
+	const int j = blockIdx.y + 1;
+	const bool on = i <= II - 2;
+	const size_t sj = II, PS = (size_t)II * JJ;
+	const size_t n = (size_t)gridDim.x * gridDim.y; // slab entries of one item
+	const ADJ a(pd, j, 0, II, JJ, 1);
+	const int ic = on ? i : 1; // (a lane past the row forms the addresses of the first point and uses none)
+	const size_t x = (size_t)ic + sj * (size_t)j;
+	const Pt q{x, ic};
+	const size_t xw = a.W(q).x, xe = a.E(q).x, xs = a.S(q), xn = a.N(q);
+	const size_t xsw = NINE ? a.S(a.W(q)) : x, xse = NINE ? a.S(a.E(q)) : x, xnw = NINE ? a.N(a.W(q)) : x, xne = NINE ? a.N(a.E(q)) : x;
+	real_t co = 0, cw = 0, ce = 0, cs = 0, cn = 0, csw = 0, cse = 0, cnw = 0, cne = 0;
+	if (on) {
+		co = so[KO * PS + x], cw = so[KW * PS + x], ce = so[KW * PS + x + 1], cs = so[KS * PS + x], cn = so[KS * PS + x + sj];
+		if (NINE) csw = so[KSW * PS + x], cse = so[KNW * PS + x + 1], cnw = so[KNW * PS + x + sj], cne = so[KSW * PS + x + 1 + sj];
+	}
+#pragma unroll 1
+	for (int m = 0; m < nrhs; m++) {
+		if (!item_on(active, m)) continue; // uniform over the workgroup
+		const size_t off = (size_t)m * stride;
+		const real_t *__restrict__ zm = z + off, *__restrict__ pm = FIRST ? zm : p + off;
+		const real_t beta = FIRST ? 0.0 : sc[(size_t)m * PCG_NSC + PCG_BETA];
+		auto P = [&](size_t y) -> real_t { return FIRST ? zm[y] : zm[y] + beta * pm[y]; };
+		real_t acc = 0.0;
+		if (on) {
+			const real_t pc = P(x);
+			real_t s = co * pc;
+			s = s - cw * P(xw);
+			s = s - ce * P(xe);
+			s = s - cs * P(xs);
+			s = s - cn * P(xn);
+			if (NINE) {
+				s = s - csw * P(xsw);
+				s = s - cse * P(xse);
+				s = s - cnw * P(xnw);
+				s = s - cne * P(xne);
+			}
+			pn[off + x] = pc;
+			w[off + x] = s;
+			acc = pc * s;
+		}
+		const real_t t = block_sum_k<256>(acc, lds);
+		if (threadIdx.x == 0) part[(size_t)m * n + blockIdx.x + (size_t)gridDim.x * blockIdx.y] = t;
+	}
+}
+
+template <bool NINE, bool FIRST>
+__global__ __launch_bounds__(256) void pcg_dir2_per_many(const real_t *__restrict__ so, const real_t *__restrict__ z,
+                                                         const real_t *__restrict__ p, real_t *__restrict__ pn,
+                                                         real_t *__restrict__ w, const real_t *__restrict__ sc, int II, int JJ,
+                                                         PerDirs pd, real_t *__restrict__ part, int nrhs, size_t stride,
+                                                         unsigned active)
+{
+	dir2_items<NINE, FIRST, AdjPer>(so, z, p, pn, w, sc, II, JJ, pd, part, nrhs, stride, active);
 }
 
 // 3D 7-point: dir7_row with the seven operator entries a point reads in registers across the items m0 .. m0 + nitems-1
@@ -1238,20 +1307,21 @@ void pcg_direction_many(const real_t *so, const Op3 *op27, const real_t *z, cons
 	    [&](auto BS, auto F) { hipLaunchKernelGGL((pcg_dir27_many<BS(), F()>), g.grid, dim3(g.bs), 0, st, g.A, z, p, pn, w, sc, II, JJ, KK, g.n, g.ts, slab, bt.n, bt.stride, active); });
 }
 
-// 3D; a periodic level is read from its Cedar planes
-void pcg_direction_periodic_many(const real_t *so, const real_t *z, const real_t *p, real_t *pn, real_t *w, int nst, int II,
+// a periodic level is read from its Cedar planes.  2D: the items are walked inside the workgroup (pcg_dir2_per_many), so the
+// launch grid is the single pass' own
+void pcg_direction_periodic_many(const real_t *so, const real_t *z, const real_t *p, real_t *pn, real_t *w, int nd, int nst, int II,
                                  int JJ, int KK, int ibc, bool first, real_t *slab, real_t *sc, hipStream_t st, Batch bt,
                                  unsigned active)
 {
-	const PerDirs pd = per_dirs(3, ibc);
-	const DirGeom g = dir_geom(so, nullptr, 3, nst, II, JJ, KK, bt.n);
+	const PerDirs pd = per_dirs(nd, ibc);
+	const DirGeom g = dir_geom(so, nullptr, nd, nst, II, JJ, KK, nd == 2 ? 1 : bt.n);
 	dir_launch_many(
-	    g, first, pcg_slab_doubles(3, nst, II, JJ, KK), slab, sc, st, bt, active,
+	    g, first, pcg_slab_doubles(nd, nst, II, JJ, KK), slab, sc, st, bt, active,
 	    [&](int m, real_t *slab_m, real_t *sc_m) {
-		    pcg_direction_periodic(so, z + m * bt.stride, first ? nullptr : p + m * bt.stride, pn + m * bt.stride, w + m * bt.stride, 3,
+		    pcg_direction_periodic(so, z + m * bt.stride, first ? nullptr : p + m * bt.stride, pn + m * bt.stride, w + m * bt.stride, nd,
 		                           nst, II, JJ, KK, ibc, first, slab_m, sc_m, st);
 	    },
-	    [](auto, auto) {}, // no 2D level here
+	    [&](auto NINE, auto F) { hipLaunchKernelGGL((pcg_dir2_per_many<NINE(), F()>), g.grid, dim3(g.bs), 0, st, so, z, p, pn, w, sc, II, JJ, pd, slab, bt.n, bt.stride, active); },
 	    [&](auto F) { hipLaunchKernelGGL(pcg_dir7_per_many<F()>, g.grid, dim3(g.bs), 0, st, so, z, p, pn, w, sc, II, JJ, KK, g.n, pd, slab, bt.n, bt.stride, active); },
 	    [&](auto BS, auto F) { hipLaunchKernelGGL((pcg_dir27_per_many<BS(), F()>), g.grid, dim3(g.bs), 0, st, g.A, z, p, pn, w, sc, II, JJ, KK, g.n, g.ts, pd, slab, bt.n, bt.stride, active); });
 }

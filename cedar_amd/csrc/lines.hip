@@ -189,9 +189,9 @@ void relax_lines_x(const real_t *so, const real_t *qf, real_t *q, const real_t *
 		// DOWN: lines J = 3,5,.. first (0-based rows 2,4,.. => jb = 1), then J = 2,4,..
 		int jb = (updown == BMG_DOWN) ? 1 - c : c;
 		launch_x(op2_cedar(so, nullptr, II, JJ), qf, q, sor, II, JJ, nstncl, jb, st, sm, false, sm ? nullptr : pf, bt);
-		if (sm) wrap2(q, II, JJ, 1, ipn == 3, 1, st);
+		if (sm) wrap2(q, II, JJ, bt.n, ipn == 3, 1, st); // (a batch: every item is a plane of the wrap)
 	}
-	if (ipn == 1) wrap2(q, II, JJ, 1, 1, 0, st);
+	if (ipn == 1) wrap2(q, II, JJ, bt.n, 1, 0, st);
 }
 
 // ------------------------------------------------------------------ y-lines

@@ -171,8 +171,10 @@ struct cedar_amd_solver {
 	// every level's vectors hold nb_alloc items, a cycle works on the first nb.  3D with nb > 1: the kernels of many3d.hip
 	// in the reference order; nb == 1: the single-vector kernels, whatever nb_alloc is
 	int nb_alloc = 1, nb = 1;
-	// a periodic 3D handle of cedar_amd_solver_create_many_periodic: its levels hold nb_alloc items too, and a batch runs
-	// the kernels of periodic_many3d.hip.  A periodic handle made any other way holds one item and the _many calls refuse it
+	// a periodic 3D handle of cedar_amd_solver_create_many_periodic or a periodic 2D handle of
+	// cedar_amd_solver_create_many_periodic2: its levels hold nb_alloc items too, and a batch runs the kernels of
+	// periodic_many3d.hip / periodic_many2d.hip.  A periodic handle made any other way holds one item and the _many calls
+	// refuse it
 	bool per_batch = false;
 	// a second captured cycle: the two colours of a plane sweep may differ by one plane
 	hipGraphExec_t gexec2 = nullptr;
@@ -279,8 +281,11 @@ void residual_true(const cedar_amd_solver *s, const Level &L, const real_t *x, c
 // one y-line sweep: on the transposed arrays when the level keeps them
 void lines_y(const Level &L, real_t *x, const real_t *b, const real_t *sor, int updown, int ipn, hipStream_t st, Batch bt = Batch())
 {
-	if (!L.At) { // (batches always keep the transposed arrays: cedar_amd_solver_create)
-		relax_lines_y(L.A, b, x, sor, L.yscr, L.II, L.JJ, L.nst, updown, st, ipn);
+	if (!L.At) {
+		// Dirichlet batches always keep the transposed arrays (cedar_amd_solver_create); a periodic 2D batch walks its items
+		// through the gather / solve / scatter pipeline on the level's one scratch, in stream order
+		for (int m = 0; m < bt.n; m++)
+			relax_lines_y(L.A, b + m * bt.stride, x + m * bt.stride, sor, L.yscr, L.II, L.JJ, L.nst, updown, st, ipn);
 		return;
 	}
 	if (!L.bt_fresh) {
@@ -494,8 +499,9 @@ void smooth(const cedar_amd_solver *s, const Level &L, real_t *x, const real_t *
 			continue;
 		}
 		const int ipn = s->st.ibc;
-		if (ipn && s->st.relaxation == CEDAR_AMD_RELAX_POINT) { // periodic point relaxation
-			relax2_gs_per(L.A, b, x, L.SOR0, L.II, L.JJ, L.nst, updown, ipn, st);
+		if (ipn && s->st.relaxation == CEDAR_AMD_RELAX_POINT) { // periodic point relaxation; a batch: periodic_many2d.hip
+			if (s->nb > 1) relax2_gs_per_many(L.A, b, x, L.SOR0, L.II, L.JJ, L.nst, updown, ipn, st, Batch{s->nb, L.npts});
+			else relax2_gs_per(L.A, b, x, L.SOR0, L.II, L.JJ, L.nst, updown, ipn, st);
 			continue;
 		}
 		const Batch bt{s->nb, L.npts};
@@ -545,7 +551,9 @@ void plane_streams_create(cedar_amd_solver *s)
 void coarse_solve(cedar_amd_solver *s, real_t *x, const real_t *b, hipStream_t st)
 {
 	const Level &C = s->lv.back();
-	if (s->nd == 2 && s->st.ibc) solve_cg2_per(x, b, C.II, C.JJ, s->ABD, s->bbd, s->nabd1, s->st.ibc, st);
+	if (s->nd == 2 && s->st.ibc && s->nb > 1)
+		solve_cg2_per_many(x, b, C.II, C.JJ, s->ABD, s->bbd, s->nabd1, s->st.ibc, st, Batch{s->nb, C.npts});
+	else if (s->nd == 2 && s->st.ibc) solve_cg2_per(x, b, C.II, C.JJ, s->ABD, s->bbd, s->nabd1, s->st.ibc, st);
 	else if (s->nd == 2) solve_cg2(x, b, C.II, C.JJ, s->ABD, s->bbd, s->nabd1, s->nabd2, st, Batch{s->nb, C.npts});
 	else if (s->st.ibc && s->nb > 1)
 		solve_cg3_per_many(x, b, C.II, C.JJ, C.KK, s->ABD, s->bbd, s->nabd1, s->st.ibc, st, Batch{s->nb, C.npts});
@@ -574,6 +582,7 @@ void restrict_to(const cedar_amd_solver *s, const Level &L, const Level &K, real
 	const bool p32 = K.P32 && !visit_fused(s, L);
 	if (p32 && s->nd == 2) restrict2_ci(ci32_view(K.P32, K.II, K.JJ), src, K.b, L.II, L.JJ, K.II, K.JJ, st, bf, bc);
 	else if (p32) restrict3_ci(ci32_view(K.P32, K.II, K.JJ, K.KK), src, K.b, L.II, L.JJ, L.KK, K.II, K.JJ, K.KK, st, bf, bc);
+	else if (s->nd == 2 && ibc && s->nb > 1) restrict2_per_many(src, K.b, K.P, L.II, L.JJ, K.II, K.JJ, ibc, st, bf, bc);
 	else if (s->nd == 2 && ibc) restrict2_per(src, K.b, K.P, L.II, L.JJ, K.II, K.JJ, ibc, st);
 	else if (s->nd == 2) restrict2(src, K.b, K.P, L.II, L.JJ, K.II, K.JJ, st, bf, bc);
 	else if (ibc && s->nb > 1) restrict3_per_many(src, K.b, K.P, L.II, L.JJ, L.KK, K.II, K.JJ, K.KK, ibc, st, bf, bc);
@@ -590,6 +599,7 @@ void interp_add_from(const cedar_amd_solver *s, const Level &L, const Level &K, 
 	if (p32 && s->nd == 2) interp_add2_ci(ci32_view(K.P32, K.II, K.JJ), x, K.x, L.res, L.A, K.II, K.JJ, L.II, L.JJ, st, bf, bc);
 	else if (p32)
 		interp_add3_ci(ci32_view(K.P32, K.II, K.JJ, K.KK), x, K.x, L.A, L.res, K.II, K.JJ, K.KK, L.II, L.JJ, L.KK, st, bf, bc);
+	else if (s->nd == 2 && ibc && s->nb > 1) interp_add2_per_many(x, K.x, L.res, L.A, K.P, K.II, K.JJ, L.II, L.JJ, ibc, st, bf, bc);
 	else if (s->nd == 2 && ibc) interp_add2_per(x, K.x, L.res, L.A, K.P, K.II, K.JJ, L.II, L.JJ, ibc, st);
 	else if (s->nd == 2) interp_add2(x, K.x, L.res, L.A, K.P, K.II, K.JJ, L.II, L.JJ, st, bf, bc);
 	else if (ibc && s->nb > 1)
@@ -813,9 +823,10 @@ static cedar_amd_solver *solver_create(int nd, len_t nx, len_t ny, len_t nz, int
 	const char *eyt = getenv("CEDAR_AMD_YLINES_TRANSPOSED");
 	const bool lyt = ly && s->st.ibc == 0 && !(eyt && atoi(eyt) == 0);
 	// batches (see the struct): Dirichlet V-cycles; 2D with the y-lines on transposed arrays, 3D point relaxation; periodic
-	// 3D only where cedar_amd_solver_create_many_periodic asked (it has checked cycle and relaxation)
-	s->per_batch = periodic_batch && nd == 3 && s->st.ibc != 0;
-	if (s->nb_alloc > 1 && ((s->st.ibc != 0 && !s->per_batch) || s->st.cycle != 0 || (ly && !lyt) || (nd == 3 && s->st.relaxation != CEDAR_AMD_RELAX_POINT)))
+	// only where cedar_amd_solver_create_many_periodic (3D) or _periodic2 (2D) asked (they have checked cycle and
+	// relaxation); a periodic 2D batch keeps its y-lines on relax_lines_y and walks the items through it
+	s->per_batch = periodic_batch && s->st.ibc != 0;
+	if (s->nb_alloc > 1 && ((s->st.ibc != 0 && !s->per_batch) || s->st.cycle != 0 || (ly && !lyt && !s->per_batch) || (nd == 3 && s->st.relaxation != CEDAR_AMD_RELAX_POINT)))
 		s->nb_alloc = 1;
 	level_init(s->lv[0], nd, (int)nx, (int)ny, (int)nz, nstencil, false, ly, lyt, s->nb_alloc);
 	Level &F0 = s->lv[0];
@@ -1559,6 +1570,32 @@ cedar_amd_solver *cedar_amd_solver_create_many_periodic(int nd, len_t nx, len_t 
 	return s;
 }
 
+// cedar_amd_solver_create_many for a periodic 2D handle (include/cedar_amd.h): point and line relaxation, V-cycle
+cedar_amd_solver *cedar_amd_solver_create_many_periodic2(len_t nx, len_t ny, int nstencil, const real_t *so, int own_device_so,
+                                                         const cedar_amd_settings *settings, int max_rhs)
+{
+	cedar_amd_settings st;
+	if (settings) st = *settings;
+	else cedar_amd_default_settings(&st);
+	if (st.ibc == 0) return cedar_amd_solver_create_many(2, nx, ny, 1, nstencil, so, own_device_so, settings, max_rhs);
+	const char *why = nullptr;
+	if (max_rhs < 1 || max_rhs > CEDAR_AMD_MAX_RHS) why = "max_rhs must be 1 .. 32";
+	else if (st.ibc < 1 || st.ibc > 3) why = "the 2D boundary codes are 0 and 1 .. 3";
+	else if (st.cycle != 0) why = "only the V-cycle is supported";
+	if (why) {
+		char msg[256];
+		snprintf(msg, sizeof(msg), "cedar_amd_solver_create_many_periodic2: %s; no solver created", why);
+		print_error(msg);
+		return nullptr;
+	}
+	cedar_amd_solver *s = solver_create(2, nx, ny, 1, nstencil, so, own_device_so, settings, max_rhs, true);
+	if (!s) { // what cedar_amd_solver_create refuses for a periodic handle, reported above under its name
+		char msg[] = "cedar_amd_solver_create_many_periodic2: refused as cedar_amd_solver_create refuses it; no solver created";
+		print_error(msg);
+	}
+	return s;
+}
+
 int cedar_amd_solver_max_rhs(const cedar_amd_solver *s) { return null_handle(s, "cedar_amd_solver_max_rhs") ? 0 : s->nb_alloc; }
 
 // what the batched entry points cannot do: reported, nothing written
@@ -1753,18 +1790,18 @@ static int pcg_run(cedar_amd_solver *s, int nrhs, const real_t *b, real_t *x, co
 	double sc[CEDAR_AMD_MAX_RHS * PCG_NSC], r0[CEDAR_AMD_MAX_RHS], m0[CEDAR_AMD_MAX_RHS];
 	int itm[CEDAR_AMD_MAX_RHS];
 	unsigned active = nrhs >= 32 ? ~0u : (1u << nrhs) - 1u;
-	// a periodic handle (cedar_amd_solver_fcg_periodic, one right-hand side; _fcg_periodic_many, 3D): every item's x gets
+	// a periodic handle (cedar_amd_solver_fcg_periodic, one right-hand side; _fcg_periodic_many, a batch): every item's x gets
 	// the periodic image in its ghost layers before the residual reads them and again on return; the direction pass wraps
 	// its own reads (krylov.hip)
 	const int ibc = s->st.ibc;
 	auto wrap_x = [&]() {
-		if (ibc && s->nd == 2) wrap2(X, L.II, L.JJ, 1, ibc == 1 || ibc == 3, ibc == 2 || ibc == 3, st);
+		if (ibc && s->nd == 2) wrap2(X, L.II, L.JJ, nrhs, ibc == 1 || ibc == 3, ibc == 2 || ibc == 3, st);
 		else if (ibc) wrap3(X, L.II, L.JJ, L.KK, nrhs, ibc, st);
 	};
 	// the two passes on the active items; update: pn = nullptr leaves x and r where they are (dot products only)
 	auto direction = [&](const real_t *pold, real_t *pn, bool first) {
 		if (ibc && nrhs > 1)
-			pcg_direction_periodic_many(L.A, Z, pold, pn, s->kw, L.nst, L.II, L.JJ, L.KK, ibc, first, s->kslab, s->ksc, st, bt, active);
+			pcg_direction_periodic_many(L.A, Z, pold, pn, s->kw, s->nd, L.nst, L.II, L.JJ, L.KK, ibc, first, s->kslab, s->ksc, st, bt, active);
 		else if (ibc)
 			pcg_direction_periodic(L.A, Z, pold, pn, s->kw, s->nd, L.nst, L.II, L.JJ, L.KK, ibc, first, s->kslab, s->ksc, st);
 		else if (nrhs == 1)
@@ -1914,7 +1951,8 @@ int cedar_amd_solver_fcg_periodic(cedar_amd_solver *s, const real_t *b, real_t *
 	return pcg_run(s, 1, b, x, p, hist, nullptr, who, p.precon == CEDAR_AMD_PCG_PRECON_BMG);
 }
 
-// cedar_amd_solver_fcg_periodic on the first nrhs items of a handle of cedar_amd_solver_create_many_periodic, in lockstep
+// cedar_amd_solver_fcg_periodic on the first nrhs items of a handle of cedar_amd_solver_create_many_periodic (3D) or
+// cedar_amd_solver_create_many_periodic2 (2D), in lockstep
 // (the contract of cedar_amd_solver_fcg_many); one right-hand side takes the single-vector path
 int cedar_amd_solver_fcg_periodic_many(cedar_amd_solver *s, int nrhs, const real_t *b, real_t *x,
                                        const cedar_amd_pcg_settings *settings, real_t *hist, int *iters)

@@ -148,7 +148,12 @@ protected:
 		BMG_get_bc(this->kman->get_params()->per_mask(), &st.ibc); // grid.periodic -> boundary code, as every reference binding does
 		// solver.max-rhs (default 1): room for that many right-hand sides on every level (multilevel::solve_many)
 		const int max_rhs = this->conf->template get<int>("solver.max-rhs", 1);
-		if (max_rhs == 1) this->h = cedar_amd_solver_create(2, fop.shape(0), fop.shape(1), 1, stencil_ndirs<fsten>::value, fop.data(), 0, &st);
+		// solver.periodic-batch (default false): with periodic directions, keep that room on a periodic handle too
+		// (cedar_amd_solver_create_many_periodic2); without the key a periodic solver holds one right-hand side
+		const bool periodic_batch = this->conf->template get<bool>("solver.periodic-batch", false);
+		if (st.ibc != 0 && max_rhs > 1 && periodic_batch)
+			this->h = cedar_amd_solver_create_many_periodic2(fop.shape(0), fop.shape(1), stencil_ndirs<fsten>::value, fop.data(), 0, &st, max_rhs);
+		else if (max_rhs == 1) this->h = cedar_amd_solver_create(2, fop.shape(0), fop.shape(1), 1, stencil_ndirs<fsten>::value, fop.data(), 0, &st);
 		else this->h = cedar_amd_solver_create_many(2, fop.shape(0), fop.shape(1), 1, stencil_ndirs<fsten>::value, fop.data(), 0, &st, max_rhs);
 		if (!this->h)
 			log::error << "cdr2::solver: the device-resident solver could not be created for these settings (reported above); "

@@ -193,8 +193,8 @@ public:
 	{
 		krylov_many(cedar_amd_solver_fcg_many, "fcg_many", b, x);
 	}
-	// fcg_periodic on several right-hand sides in lockstep (cedar_amd_solver_fcg_periodic_many): a 3D solver with periodic
-	// directions made with solver.max-rhs and solver.periodic-batch: true; results as after pcg_many()
+	// fcg_periodic on several right-hand sides in lockstep (cedar_amd_solver_fcg_periodic_many): a 2D or 3D solver with
+	// periodic directions made with solver.max-rhs and solver.periodic-batch: true; results as after pcg_many()
 	void fcg_periodic_many(const std::vector<grid_func> & b, std::vector<grid_func> & x)
 	{
 		krylov_many(cedar_amd_solver_fcg_periodic_many, "fcg_periodic_many", b, x);

@@ -828,6 +828,68 @@ int cedar_amd_pcg_direction_periodic_many(int nrhs, unsigned active, const real_
                                           real_t *pn, real_t *w, len_t ii, len_t jj, len_t kk, int nstncl, int ibc, int first,
                                           real_t *sc);
 
+/* Several right-hand sides at once on a PERIODIC 2D handle (periodic_many2d.hip, krylov.hip pcg_dir2_per_many): the 2D
+ * case the block above leaves out is served by a call of its own, cedar_amd_solver_create_many_periodic2.  It is
+ * cedar_amd_solver_create_many for a periodic 2D handle: every level, the coarsest right-hand-side workspace and later the
+ * Krylov storage have room for max_rhs items, and cedar_amd_solver_max_rhs reports max_rhs.  cedar_amd_solver_create_many
+ * and cedar_amd_solver_create_many_periodic are unchanged: a periodic 2D handle asked for through the first still holds one
+ * item and the _many calls keep refusing it, the second keeps refusing nd == 2.
+ *  - Served: 2D, ibc 1..3, 5- and 9-point, V(m,n), max_rhs 1 .. 32; point relaxation (rows up to the 8190 points the
+ *    single-vector handle serves) and line-x, line-y, line-xy relaxation.  On such a handle cedar_amd_solver_vcycle_many,
+ *    _solve_many and _time_vcycles_many work with the contracts they have above, and cedar_amd_solver_fcg_periodic_many
+ *    runs flexible CG on the items in lockstep (all nrhs items of x are wrapped before the first residual and on return,
+ *    the ghosts of b are never read, nrhs == 1 runs the single-vector path itself).  Every single-vector entry point
+ *    (_solve, _vcycle, _get, _set, _time_*) still works on item 0 with exactly the launches it takes on a handle of
+ *    cedar_amd_solver_create.
+ *  - How a batch runs: the point sweep, the transfers, the coarsest solve, the x-line sweep and every Krylov pass take all
+ *    items in one launch; the point sweep and the direction pass fetch the operator once per task and apply it to every
+ *    item.  Periodic y-lines stay on the gather / solve / scatter pipeline, which the items walk one after the other (a
+ *    batched periodic y-line pipeline is out of scope).
+ *  - Forwarded: ibc == 0 goes to cedar_amd_solver_create_many(2, ...); cedar_amd_solver_fcg_periodic_many on a Dirichlet
+ *    batch handle goes to cedar_amd_solver_fcg_many.
+ *  - Refused by the creation call (print_error, NULL, the message names cedar_amd_solver_create_many_periodic2): an
+ *    F-cycle, max_rhs outside 1 .. 32, a boundary code 2D does not define, and everything cedar_amd_solver_create refuses
+ *    for a periodic 2D handle (point relaxation with rows longer than 8190 points): its message first, then a line that
+ *    names this call.
+ *  - Refused on the handle (print_error, -1, nothing written): nrhs < 1 or nrhs > max_rhs; cedar_amd_solver_pcg_many and
+ *    cedar_amd_solver_fcg_many (periodic boundaries, as before); cedar_amd_solver_fcg_periodic when max_rhs > 1 (use
+ *    cedar_amd_solver_fcg_periodic_many with nrhs == 1); every single-precision switch.
+ *  - Bits: item m of every result -- x, rel / hist rows, iters -- has the bits of the single-vector periodic call on item m
+ *    alone on a handle of cedar_amd_solver_create with the same settings.  The 2D periodic single-vector path has no
+ *    partial-sum sweep and no float view, so this holds at every size with no environment switch.
+ *  - Out of scope: periodic F-cycles on a batch, a batched periodic y-line pipeline, the single-precision switches on
+ *    periodic handles, singular fully periodic operators, the rank-grid solvers. */
+cedar_amd_solver *cedar_amd_solver_create_many_periodic2(len_t nx, len_t ny, int nstencil, const real_t *so,
+                                                         int own_device_so, const cedar_amd_settings *settings, int max_rhs);
+/* The batched periodic 2D kernels one at a time on caller arrays (host or device; the nrhs items lie back to back with
+ * stride ii*jj, the operator arrays are shared; argument order of the single-vector 2D calls, then the boundary code).
+ * Item m has the bits of the single-vector periodic drop-in (BMG2_SymStd_relax_GS / _restrict / _interp_add / _SOLVE_cg,
+ * cedar_amd_pcg_direction_periodic) on item m alone.  0, or -1 (print_error, nothing written) for nrhs outside 1 .. 32, a
+ * NULL array, an nstncl other than 3 | 5 or ibc outside 0 .. 3.  ibc = 0: cedar_amd_pcg_direction2_periodic_many forwards
+ * to cedar_amd_pcg_direction_many, its Dirichlet batched twin; relax2_gs, restrict2, interp_add2 and solve_cg2 have no
+ * Dirichlet batched kernel-level call to go to and refuse it.
+ *  - relax2_gs: nstncl 3 = the five-point sweep, 5 = the nine-point one; updown as BMG2_SymStd_relax_GS; rows of more than
+ *    8192 points (ghosts included) are refused.  Up to 512 interior points one workgroup per grid row serves all items;
+ *    longer rows take one launch per i-colour with a lane per point.  Either way a lane keeps the coefficients of its
+ *    points in registers across the items.
+ *  - restrict2 refreshes the ghosts of the nrhs fine vectors first (q is written) under the single call's conditions;
+ *    interp_add2 keeps its side effect on res per item and wraps every item's q.
+ *  - solve_cg2: abd = the dense factor of BMG2_SymStd_SETUP_cg_LU with the same code (shared), nabd1 >= (ii-2)(jj-2);
+ *    bbd = nrhs segments of (ii-2)(jj-2) doubles; one lane per item.
+ *  - pcg_direction2: as cedar_amd_pcg_direction_many on a 2D level, reads wrapped; a masked item is neither read nor
+ *    written.  cedar_amd_pcg_direction_periodic_many keeps refusing nstncl 3 | 5. */
+int cedar_amd_relax2_gs_periodic_many(int nrhs, real_t *so, real_t *qf, real_t *q, real_t *sor, len_t ii, len_t jj, int nstncl,
+                                      int updown, int ibc);
+int cedar_amd_restrict2_periodic_many(int nrhs, real_t *q, real_t *qc, real_t *ci, len_t ii, len_t jj, len_t iic, len_t jjc,
+                                      int ibc);
+int cedar_amd_interp_add2_periodic_many(int nrhs, real_t *q, real_t *qc, real_t *res, real_t *so, real_t *ci, len_t iic,
+                                        len_t jjc, len_t ii, len_t jj, int nstncl, int ibc);
+int cedar_amd_solve_cg2_periodic_many(int nrhs, real_t *q, real_t *qf, len_t ii, len_t jj, real_t *abd, real_t *bbd,
+                                      len_t nabd1, int ibc);
+int cedar_amd_pcg_direction2_periodic_many(int nrhs, unsigned active, const real_t *so, const real_t *z, const real_t *p,
+                                           real_t *pn, real_t *w, len_t ii, len_t jj, int nstncl, int ibc, int first,
+                                           real_t *sc);
+
 /* plane relaxation as a kernel of its own -- kernels::plane_relax<stypes, rdir>::setup(so) / run(so, x, b, dir)
  * (include/cedar/kernels/plane_relax.h:10-33; include/cedar/3d/relax_planes.h:164-246, src/3d/relax_planes.cc).
  * dir 0 = xy planes, 1 = xz, 2 = yz; plane_settings = the 2D solvers' configuration (NULL: the reference's default
