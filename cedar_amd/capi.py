@@ -642,6 +642,20 @@ class Kernels:
                                          bx.ctypes.data_as(C.POINTER(C.c_int)), len(bx)) != 0:
             raise RuntimeError("cedar_amd_pcg_ghost_shell refused")
 
+    def project_mean(self, v, nrhs=None, active=None):
+        """v := v - mean_interior(v) (cedar_amd_project_mean).  nrhs None: v is one level vector; else v has shape
+        (items,) + grid and the items of the bit mask active (default: all nrhs) are projected.  Returns the means
+        (0 for an item outside active)"""
+        grid = v.shape if nrhs is None else v.shape[1:]
+        n = 1 if nrhs is None else int(nrhs)
+        assert nrhs is None or v.shape[0] >= n
+        mean = np.zeros(n)
+        act = u((1 << n) - 1 if active is None else int(active))
+        if lib.cedar_amd_project_mean(n, act, _p(v), u(grid[-1]), u(grid[-2]), u(grid[0] if len(grid) == 3 else 1),
+                                      mean.ctypes.data) != 0:
+            raise RuntimeError("cedar_amd_project_mean refused")
+        return mean
+
     def l2(self, v):
         return l2norm(v)
 
@@ -678,6 +692,10 @@ lib.cedar_amd_solver_create_many_periodic.restype = C.c_void_p
 lib.cedar_amd_solver_create_many_periodic.argtypes = lib.cedar_amd_solver_create_many.argtypes
 lib.cedar_amd_solver_create_many_periodic2.restype = C.c_void_p
 lib.cedar_amd_solver_create_many_periodic2.argtypes = [u, u, C.c_int, C.c_void_p, C.c_int, C.POINTER(Settings), C.c_int]
+lib.cedar_amd_solver_create_semidefinite.restype = C.c_void_p
+lib.cedar_amd_solver_create_semidefinite.argtypes = lib.cedar_amd_solver_create_many.argtypes
+lib.cedar_amd_project_mean.restype = C.c_int
+lib.cedar_amd_project_mean.argtypes = [C.c_int, C.c_uint, C.c_void_p, u, u, u, C.c_void_p]
 for _f in (lib.cedar_amd_relax2_gs_periodic_many, lib.cedar_amd_restrict2_periodic_many, lib.cedar_amd_interp_add2_periodic_many,
            lib.cedar_amd_solve_cg2_periodic_many, lib.cedar_amd_pcg_direction2_periodic_many):
     _f.restype = C.c_int
@@ -736,6 +754,10 @@ lib.cedar_amd_solver_fcg_periodic.restype = C.c_int
 lib.cedar_amd_solver_fcg_periodic.argtypes = lib.cedar_amd_solver_pcg.argtypes
 lib.cedar_amd_solver_fcg_periodic_many.restype = C.c_int
 lib.cedar_amd_solver_fcg_periodic_many.argtypes = lib.cedar_amd_solver_pcg_many.argtypes
+lib.cedar_amd_solver_fcg_semidefinite.restype = C.c_int
+lib.cedar_amd_solver_fcg_semidefinite.argtypes = lib.cedar_amd_solver_pcg.argtypes
+lib.cedar_amd_solver_fcg_semidefinite_many.restype = C.c_int
+lib.cedar_amd_solver_fcg_semidefinite_many.argtypes = lib.cedar_amd_solver_pcg_many.argtypes
 lib.cedar_amd_solver_use_fp32_operator.restype = C.c_int
 lib.cedar_amd_solver_use_fp32_operator.argtypes = [C.c_void_p, C.c_int]
 lib.cedar_amd_solver_use_fp32_operator_many.restype = C.c_int
@@ -762,7 +784,7 @@ class Solver:
 
     def __init__(self, so, relax="point", nrelax_pre=2, nrelax_post=1, num_levels=-1,
                  max_iter=10, tol=1e-8, min_coarse=3, share_operator=False, cycle="v", ibc=0, plane=None, max_rhs=1,
-                 periodic_batch=False, periodic_batch2d=False):
+                 periodic_batch=False, periodic_batch2d=False, semidefinite=False):
         shp = so.shape
         self.nd = len(shp) - 1
         nst = shp[0]
@@ -774,7 +796,12 @@ class Solver:
         plane_settings(st, plane)
         self.max_iter = max_iter
         self._so = so if share_operator else None  # keep the shared operator alive
-        if periodic_batch2d:  # a periodic 2D handle with room for max_rhs right-hand sides (ibc = 0: as max_rhs alone)
+        if semidefinite:
+            # a singular operator whose null space is the constants -- pure Neumann, fully periodic; ibc keeps its meaning
+            # (cedar_amd_solver_create_semidefinite); max_rhs > 1: a batch handle of the kind nd and ibc call for
+            self.h = lib.cedar_amd_solver_create_semidefinite(self.nd, nx, ny, nz, nst, _vp(so), int(share_operator),
+                                                              C.byref(st), int(max_rhs))
+        elif periodic_batch2d:  # a periodic 2D handle with room for max_rhs right-hand sides (ibc = 0: as max_rhs alone)
             if self.nd != 2:
                 raise ValueError("periodic_batch2d is for 2D operators; periodic_batch serves 3D")
             self.h = lib.cedar_amd_solver_create_many_periodic2(nx, ny, nst, _vp(so), int(share_operator), C.byref(st),
@@ -914,6 +941,17 @@ class Solver:
         periodic_batch2d=True (2D)
         (cedar_amd_solver_fcg_periodic_many); same arguments and return as fcg_many"""
         return self._cg_many("cedar_amd_solver_fcg_periodic_many", b, x, max_iter, tol, stop, precon, nmg_cycles, hist)
+
+    def fcg_semidefinite(self, b, x, max_iter=50, tol=1e-8, stop="rel_l2", precon="mg", nmg_cycles=1):
+        """flexible conjugate gradients on a handle made with semidefinite=True (cedar_amd_solver_fcg_semidefinite):
+        solves A x = P b with mean(x) = 0, P v = v - mean_interior(v); b need not be compatible and is not written,
+        hist[0] = |P (b - A x0)|; the cycle is applied as P M P.  Same arguments and return as pcg"""
+        return self._cg("cedar_amd_solver_fcg_semidefinite", b, x, max_iter, tol, stop, precon, nmg_cycles)
+
+    def fcg_semidefinite_many(self, b, x, max_iter=50, tol=1e-8, stop="rel_l2", precon="mg", nmg_cycles=1, hist=None):
+        """fcg_semidefinite for the items of b, x in lockstep on a handle made with semidefinite=True and max_rhs > 1
+        (cedar_amd_solver_fcg_semidefinite_many); same arguments and return as fcg_many"""
+        return self._cg_many("cedar_amd_solver_fcg_semidefinite_many", b, x, max_iter, tol, stop, precon, nmg_cycles, hist)
 
     def precondition(self, z, r):
         """z = M^-1 r: one cycle from z = 0 (cedar_amd_solver_precondition)"""

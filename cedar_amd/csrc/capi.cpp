@@ -1407,6 +1407,26 @@ int cedar_amd_solve_cg2_periodic_many(int nrhs, real_t *q, real_t *qf, len_t ii,
 	return 0;
 }
 
+// v := v - mean_interior(v) on the items of `active` (util.hip project_mean_many); kk = 1: a 2D level
+int cedar_amd_project_mean(int nrhs, unsigned active, real_t *v, len_t ii, len_t jj, len_t kk, real_t *mean)
+{
+	if (nrhs < 1 || nrhs > CEDAR_AMD_MAX_RHS || !v || ii < 3 || jj < 3 || (kk != 1 && kk < 3)) {
+		char msg[] = "cedar_amd_project_mean: nrhs must be 1 .. 32, v not NULL and every extent at least 3 (kk = 1: 2D); nothing done";
+		print_error(msg);
+		return -1;
+	}
+	const size_t P = (size_t)ii * jj * kk;
+	Staged sv(v, P * nrhs, true, true);
+	ScratchLoan scratch(nullptr, project_mean_doubles(nrhs));
+	hipStream_t st = current_stream();
+	project_mean_many(sv.get(), (int)ii, (int)jj, (int)kk, scratch.p, st, Batch{nrhs, P}, active);
+	if (mean) {
+		CEDAR_HIP_CHECK(hipMemcpyAsync(mean, scratch.p + 2 * (size_t)nrhs * PROJECT_MEAN_NB, nrhs * sizeof(real_t), hipMemcpyDefault, st));
+		CEDAR_HIP_CHECK(hipStreamSynchronize(st));
+	}
+	return 0;
+}
+
 // the direction pass of a periodic 2D level on nrhs items; every item's slab NaN-filled
 int cedar_amd_pcg_direction2_periodic_many(int nrhs, unsigned active, const real_t *so, const real_t *z, const real_t *p,
                                            real_t *pn, real_t *w, len_t ii, len_t jj, int nstncl, int ibc, int first, real_t *sc)

@@ -113,9 +113,28 @@ __device__ void band_solve(int n, int kd, const real_t *__restrict__ abd, int ld
 	}
 }
 
+// The mean removal of SOLVE_cg (BMG3_SymStd_SOLVE_cg.f90:150-172) on a semidefinite handle: minus the mean of the n
+// unknowns, which lie in bbd in the reference's loop order (i fastest, then j, then k).  One lane sums sequentially, as
+// the periodic solves do (periodic2d.hip, periodic3d.hip), so an item's bits do not depend on the batch.  Every lane of
+// the wavefront must call it.
+__device__ real_t mean_shift(const real_t *bbd, int n)
+{
+	__shared__ real_t cshift;
+	if (threadIdx.x == 0) {
+		real_t cint = 0.0, qint = 0.0;
+		for (int r = 0; r < n; r++) {
+			qint = qint + bbd[r];
+			cint = cint + 1;
+		}
+		cshift = -qint / cint;
+	}
+	__syncthreads();
+	return cshift;
+}
+
 // ------------------------------------------------------------------ 2D
 __global__ __launch_bounds__(256) void setup_cg2_kernel(const real_t *__restrict__ so, int II, int JJ, int nstncl,
-                                                         real_t *__restrict__ abd, int nabd1, int nabd2, int *info)
+                                                         real_t *__restrict__ abd, int nabd1, int nabd2, int *info, int semidef)
 {
 	const int I1 = II - 1, J1 = JJ - 1, I2 = I1 - 1;
 	const int n = I2 * (J1 - 1);
@@ -130,6 +149,10 @@ __global__ __launch_bounds__(256) void setup_cg2_kernel(const real_t *__restrict
 		ABD(1, kk) = nstncl == 5 ? -so[KSW * PS + x] : 0.0;
 	}
 	__syncthreads();
+	// a semidefinite operator (null space: the constants): the last unknown's diagonal entry is added to itself, as
+	// BMG2_SymStd_SETUP_cg_LU.f90 does for the indefinite boundary codes
+	if (semidef && threadIdx.x == 0) ABD(II, n) = ABD(II, n) + ABD(II, n);
+	__syncthreads();
 	__shared__ int flag;
 	const int rc = dpbtf2_upper_wg(n, I1, abd, nabd1, &flag);
 	if (threadIdx.x == 0) *info = rc;
@@ -137,7 +160,7 @@ __global__ __launch_bounds__(256) void setup_cg2_kernel(const real_t *__restrict
 
 __global__ __launch_bounds__(64) void solve_cg2_kernel(real_t *__restrict__ q, const real_t *__restrict__ qf, int II, int JJ,
                                                         const real_t *__restrict__ abd, real_t *__restrict__ bbd, int nabd1, int use_lds,
-                                                        size_t bstride, int nabd2)
+                                                        size_t bstride, int nabd2, int semidef)
 {
 	extern __shared__ __attribute__((aligned(16))) real_t lds[];
 	const int I1 = II - 1, J1 = JJ - 1, I2 = I1 - 1;
@@ -150,29 +173,31 @@ __global__ __launch_bounds__(64) void solve_cg2_kernel(real_t *__restrict__ q, c
 	__syncthreads();
 	band_solve(n, I1, abd, nabd1, bbd, lds, use_lds);
 	__syncthreads();
+	const real_t c = semidef ? mean_shift(bbd, n) : 0.0;
 	for (int kk = threadIdx.x; kk < n; kk += blockDim.x) {
 		const int i = kk % I2 + 1, j = kk / I2 + 1;
-		q[(size_t)i + (size_t)II * j] = bbd[kk];
+		q[(size_t)i + (size_t)II * j] = semidef ? bbd[kk] + c : bbd[kk];
 	}
 }
 
-void setup_cg2(const real_t *so, int II, int JJ, int nstncl, real_t *abd, int nabd1, int nabd2, int *info, hipStream_t st)
+void setup_cg2(const real_t *so, int II, int JJ, int nstncl, real_t *abd, int nabd1, int nabd2, int *info, hipStream_t st,
+               int semidef)
 {
-	hipLaunchKernelGGL(setup_cg2_kernel, dim3(1), dim3(256), 0, st, so, II, JJ, nstncl, abd, nabd1, nabd2, info);
+	hipLaunchKernelGGL(setup_cg2_kernel, dim3(1), dim3(256), 0, st, so, II, JJ, nstncl, abd, nabd1, nabd2, info, semidef);
 }
 
 void solve_cg2(real_t *q, const real_t *qf, int II, int JJ, const real_t *abd, real_t *bbd, int nabd1, int nabd2, hipStream_t st,
-               Batch bt)
+               Batch bt, int semidef)
 {
 	size_t shm = ((size_t)nabd1 * nabd2 + nabd2 + 2) * sizeof(real_t);
 	int use_lds = shm <= 60 * 1024;
 	hipLaunchKernelGGL(solve_cg2_kernel, dim3(bt.n), dim3(64), use_lds ? shm : 0, st, q, qf, II, JJ, abd, bbd, nabd1, use_lds,
-	                   bt.stride, nabd2);
+	                   bt.stride, nabd2, semidef);
 }
 
 // ------------------------------------------------------------------ 3D
 __global__ __launch_bounds__(256) void setup_cg3_kernel(const real_t *__restrict__ so, int II, int JJ, int KK, int nstncl,
-                                                         real_t *__restrict__ abd, int nabd1, int nabd2, int *info)
+                                                         real_t *__restrict__ abd, int nabd1, int nabd2, int *info, int semidef)
 {
 	const int i1 = II - 1, j1 = JJ - 1, k1 = KK - 1, i2 = i1 - 1;
 	const int ibw = i2 * j1 + 1;
@@ -199,6 +224,9 @@ __global__ __launch_bounds__(256) void setup_cg3_kernel(const real_t *__restrict
 		ABD(1, kl) = full ? -so[KBSW * PS + x] : 0.0;
 	}
 	__syncthreads();
+	// semidefinite: BMG3_SymStd_SETUP_cg_LU.f90:143-145 (see setup_cg2_kernel)
+	if (semidef && threadIdx.x == 0) ABD(ibw + 1, n) = ABD(ibw + 1, n) + ABD(ibw + 1, n);
+	__syncthreads();
 	__shared__ int flag;
 	const int rc = dpbtf2_upper_wg(n, ibw, abd, nabd1, &flag);
 	if (threadIdx.x == 0) *info = rc;
@@ -206,7 +234,7 @@ __global__ __launch_bounds__(256) void setup_cg3_kernel(const real_t *__restrict
 
 __global__ __launch_bounds__(64) void solve_cg3_kernel(real_t *__restrict__ q, const real_t *__restrict__ qf, int II, int JJ, int KK,
                                                         const real_t *__restrict__ abd, real_t *__restrict__ bbd, int nabd1, int use_lds,
-                                                        size_t bstride, int nabd2)
+                                                        size_t bstride, int nabd2, int semidef)
 {
 	extern __shared__ __attribute__((aligned(16))) real_t lds[];
 	const int i1 = II - 1, j1 = JJ - 1, k1 = KK - 1, i2 = i1 - 1;
@@ -221,24 +249,26 @@ __global__ __launch_bounds__(64) void solve_cg3_kernel(real_t *__restrict__ q, c
 	__syncthreads();
 	band_solve(n, ibw, abd, nabd1, bbd, lds, use_lds);
 	__syncthreads();
+	const real_t c = semidef ? mean_shift(bbd, n) : 0.0;
 	for (int t = threadIdx.x; t < n; t += blockDim.x) {
 		const int i = t % i2 + 1, j = (t / i2) % (j1 - 1) + 1, k = t / nxy + 1;
-		q[(size_t)i + sj * j + sk * k] = bbd[t];
+		q[(size_t)i + sj * j + sk * k] = semidef ? bbd[t] + c : bbd[t];
 	}
 }
 
-void setup_cg3(const real_t *so, int II, int JJ, int KK, int nstncl, real_t *abd, int nabd1, int nabd2, int *info, hipStream_t st)
+void setup_cg3(const real_t *so, int II, int JJ, int KK, int nstncl, real_t *abd, int nabd1, int nabd2, int *info, hipStream_t st,
+               int semidef)
 {
-	hipLaunchKernelGGL(setup_cg3_kernel, dim3(1), dim3(256), 0, st, so, II, JJ, KK, nstncl, abd, nabd1, nabd2, info);
+	hipLaunchKernelGGL(setup_cg3_kernel, dim3(1), dim3(256), 0, st, so, II, JJ, KK, nstncl, abd, nabd1, nabd2, info, semidef);
 }
 
 void solve_cg3(real_t *q, const real_t *qf, int II, int JJ, int KK, const real_t *abd, real_t *bbd, int nabd1, int nabd2, hipStream_t st,
-               Batch bt)
+               Batch bt, int semidef)
 {
 	size_t shm = ((size_t)nabd1 * nabd2 + nabd2 + 2) * sizeof(real_t);
 	int use_lds = shm <= 60 * 1024;
 	hipLaunchKernelGGL(solve_cg3_kernel, dim3(bt.n), dim3(64), use_lds ? shm : 0, st, q, qf, II, JJ, KK, abd, bbd, nabd1, use_lds,
-	                   bt.stride, nabd2);
+	                   bt.stride, nabd2, semidef);
 }
 
 } // namespace cedar_amd

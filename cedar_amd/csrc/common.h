@@ -296,7 +296,10 @@ void interp_add2_per(real_t *q, const real_t *qc, real_t *res, const real_t *so,
 void galerkin2_per(const real_t *so, real_t *soc, const real_t *ci, int IIF, int JJF, int IIC, int JJC, int ifd, int ipn,
                    hipStream_t st);
 void setup_interp2_per(const real_t *so, real_t *ci, int IIF, int JJF, int IIC, int JJC, int ifd, int ipn, hipStream_t st);
-void setup_cg2_per(const real_t *so, int II, int JJ, int nstncl, real_t *abd, int nabd1, int ipn, int *info, hipStream_t st);
+// semidef (here and in setup_cg3_per, setup_cg2, setup_cg3): the last unknown's diagonal entry is doubled before the
+// factorisation -- a semidefinite operator whose null space is the constants (cedar_amd_solver_create_semidefinite)
+void setup_cg2_per(const real_t *so, int II, int JJ, int nstncl, real_t *abd, int nabd1, int ipn, int *info, hipStream_t st,
+                   int semidef = 0);
 void solve_cg2_per(real_t *q, const real_t *qf, int II, int JJ, const real_t *abd, real_t *bbd, int nabd1, int ipn, hipStream_t st);
 // 3D periodic boundary conditions (periodic3d.hip, relax3d.hip); ipn = 1 y, 2 x, 3 xy, 5 z, 6 xz, 7 yz, 8 xyz
 bool periodic3_code_ok(int ipn);
@@ -314,7 +317,7 @@ void setup_interp3_per(const real_t *so, real_t *ci, int IIF, int JJF, int KKF, 
 void galerkin3_per(const real_t *so, real_t *soc, const real_t *ci, int IIF, int JJF, int KKF, int IIC, int JJC, int KKC,
                    int ifd, int ipn, hipStream_t st);
 void setup_cg3_per(const real_t *so, int II, int JJ, int KK, real_t *abd, int nabd1, int ipn, int *info, hipStream_t st,
-                   int nst = 14); // nst: slots of so, 4 for a one-level seven-point handle
+                   int nst = 14, int semidef = 0); // nst: slots of so, 4 for a one-level seven-point handle
 void solve_cg3_per(real_t *q, const real_t *qf, int II, int JJ, int KK, const real_t *abd, real_t *bbd, int nabd1, int ipn,
                    hipStream_t st);
 // plane relaxation, the 3D side (planes.hip); dir 0 xy, 1 xz, 2 yz; stacked 2D arrays, slot q = plane beg + 2q
@@ -366,6 +369,14 @@ void galerkin3(const real_t *so, real_t *soc, const real_t *ci, int IIF, int JJF
 // arrays (profiles/r01_memset_under_torch_runtime.log)
 void zero_fill(real_t *p, size_t n, hipStream_t st);
 void vec_add(real_t *x, const real_t *z, size_t n, hipStream_t st); // x += z
+// util.hip: v := v - mean_interior(v) on every item of `active` (bit m = item m; items bt.stride doubles apart, ghosts
+// included and not written).  Deterministic two-stage sum whose order depends on the extents alone, carried in two
+// doubles (the mean is the correctly rounded one): item m of a batch is bit for bit the single-vector call.  scratch: project_mean_doubles(bt.n) doubles; the means are left in its last bt.n
+// entries (0 for an item outside `active`)
+enum { PROJECT_MEAN_NB = 1024 };
+static inline size_t project_mean_doubles(int nrhs) { return (size_t)nrhs * (2 * PROJECT_MEAN_NB + 1); }
+void project_mean(real_t *v, int II, int JJ, int KK, real_t *scratch, hipStream_t st);
+void project_mean_many(real_t *v, int II, int JJ, int KK, real_t *scratch, hipStream_t st, Batch bt, unsigned active);
 // lines.hip
 void setup_lines_x(const real_t *so, real_t *sor, int II, int JJ, hipStream_t st, int fold = 0);
 void setup_lines_y(const real_t *so, real_t *sor, int II, int JJ, hipStream_t st, int fold = 0);
@@ -396,12 +407,14 @@ void setup_lines_yt(const real_t *so, real_t *sot, int II, int JJ, int nstncl, h
 void relax_lines_yt(const real_t *sot, const real_t *qft, real_t *q, real_t *qt, const real_t *sor,
                     int II, int JJ, int nstncl, int updown, hipStream_t st, const real_t *pf = nullptr, Batch bt = Batch());
 // cgsolve.hip
-void setup_cg2(const real_t *so, int II, int JJ, int nstncl, real_t *abd, int nabd1, int nabd2, int *info, hipStream_t st);
+void setup_cg2(const real_t *so, int II, int JJ, int nstncl, real_t *abd, int nabd1, int nabd2, int *info, hipStream_t st,
+               int semidef = 0);
 void solve_cg2(real_t *q, const real_t *qf, int II, int JJ, const real_t *abd, real_t *bbd, int nabd1, int nabd2, hipStream_t st,
-               Batch bt = Batch()); // bbd: nabd2 doubles per batch item
-void setup_cg3(const real_t *so, int II, int JJ, int KK, int nstncl, real_t *abd, int nabd1, int nabd2, int *info, hipStream_t st);
+               Batch bt = Batch(), int semidef = 0); // bbd: nabd2 doubles per batch item; semidef: the solution's mean is removed
+void setup_cg3(const real_t *so, int II, int JJ, int KK, int nstncl, real_t *abd, int nabd1, int nabd2, int *info, hipStream_t st,
+               int semidef = 0);
 void solve_cg3(real_t *q, const real_t *qf, int II, int JJ, int KK, const real_t *abd, real_t *bbd, int nabd1, int nabd2, hipStream_t st,
-               Batch bt = Batch()); // bbd: nabd2 doubles per batch item
+               Batch bt = Batch(), int semidef = 0); // bbd: nabd2 doubles per batch item; semidef: the solution's mean is removed
 // krylov.hip: the vector work of the preconditioned conjugate gradient (solver.cpp cedar_amd_solver_pcg).  The scalars
 // of a run live on the device in sc[PCG_NSC]; the kernels read alpha / beta from there and write them back.
 enum { PCG_RHO = 0, PCG_SIGMA = 1, PCG_ALPHA = 2, PCG_BETA = 3, PCG_RR = 4, PCG_RZ = 5, PCG_FLAG = 6, PCG_WZ = 7, PCG_NSC = 8 };

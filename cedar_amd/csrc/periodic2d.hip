@@ -290,7 +290,7 @@ void setup_interp2_per(const real_t *so, real_t *ci, int IIF, int JJF, int IIC, 
 #define SOC(i, j, s) so[(size_t)((i)-1) + (size_t)II * ((size_t)((j)-1) + (size_t)JJ * (size_t)(s))]
 // one lane: the matrix has a few dozen rows.  Entry order of the reference (:152-212); ABD must come in zeroed.
 __global__ void setup_cg2_per_kernel(const real_t *__restrict__ so, int II, int JJ, int nstncl, real_t *abd, int nabd1,
-                                     int ipn, int *info)
+                                     int ipn, int *info, int semidef)
 {
 	if (threadIdx.x != 0 || blockIdx.x != 0) return;
 	const int I1 = II - 1, J1 = JJ - 1, I2 = I1 - 1;
@@ -338,6 +338,9 @@ __global__ void setup_cg2_per_kernel(const real_t *__restrict__ so, int II, int 
 		if (ipn == 3) ABD(1, kk) = nine ? -SOC(II, JJ, KSW) : 0.0;
 		if (per_x(ipn)) ABD(kk - 2 * I2 + 1, kk) = nine ? -SOC(II, J1, KNW) : 0.0;
 	}
+	// a semidefinite operator (null space: the constants): the last unknown's diagonal entry is added to itself, as
+	// BMG2_SymStd_SETUP_cg_LU.f90 does for the indefinite boundary codes
+	if (semidef) ABD(n, n) = ABD(n, n) + ABD(n, n);
 	// DPOTF2 'U' (dpotf2.f): dot, sqrt, gemv, scal in the reference-BLAS order
 	int rc = 0;
 	for (int j = 1; j <= n && rc == 0; j++) {
@@ -419,9 +422,10 @@ __global__ void solve_cg2_per_kernel(real_t *__restrict__ q, const real_t *__res
 #undef ABD
 #undef SOC
 
-void setup_cg2_per(const real_t *so, int II, int JJ, int nstncl, real_t *abd, int nabd1, int ipn, int *info, hipStream_t st)
+void setup_cg2_per(const real_t *so, int II, int JJ, int nstncl, real_t *abd, int nabd1, int ipn, int *info, hipStream_t st,
+                   int semidef)
 {
-	hipLaunchKernelGGL(setup_cg2_per_kernel, dim3(1), dim3(64), 0, st, so, II, JJ, nstncl, abd, nabd1, ipn, info);
+	hipLaunchKernelGGL(setup_cg2_per_kernel, dim3(1), dim3(64), 0, st, so, II, JJ, nstncl, abd, nabd1, ipn, info, semidef);
 }
 
 void solve_cg2_per(real_t *q, const real_t *qf, int II, int JJ, const real_t *abd, real_t *bbd, int nabd1, int ipn, hipStream_t st)

@@ -159,7 +159,8 @@ __device__ __forceinline__ int unknown3(int i, int j, int k, int nx, int ny, int
 // reference-BLAS order -- results independent of the thread count.  nst: the slots so holds, 14 or 4 (a one-level
 // seven-point handle: slots 1..3 are its west, south and bottom entries)
 __global__ __launch_bounds__(1024) void setup_cg3_per_kernel(const real_t *__restrict__ so, int II, int JJ, int KK,
-                                                             real_t *__restrict__ abd, int nabd1, int ipn, int *info, int nst)
+                                                             real_t *__restrict__ abd, int nabd1, int ipn, int *info, int nst,
+                                                             int semidef)
 {
 	const int nx = II - 2, ny = JJ - 2, nz = KK - 2, N = nx * ny * nz;
 	const int tid = threadIdx.x, nt = blockDim.x;
@@ -182,6 +183,9 @@ __global__ __launch_bounds__(1024) void setup_cg3_per_kernel(const real_t *__res
 		}
 	}
 	__syncthreads();
+	// a semidefinite operator (null space: the constants): the last unknown's diagonal entry is added to itself
+	// (BMG3_SymStd_SETUP_cg_LU.f90:590-593, the indefinite boundary codes)
+	if (semidef && tid == 0) ABD(N - 1, N - 1) = ABD(N - 1, N - 1) + ABD(N - 1, N - 1);
 	__shared__ int rc;
 	__shared__ real_t rinv;
 	if (tid == 0) rc = 0;
@@ -277,9 +281,11 @@ __global__ __launch_bounds__(1024) void solve_cg3_per_kernel(real_t *__restrict_
 }
 #undef ABD
 
-void setup_cg3_per(const real_t *so, int II, int JJ, int KK, real_t *abd, int nabd1, int ipn, int *info, hipStream_t st, int nst)
+void setup_cg3_per(const real_t *so, int II, int JJ, int KK, real_t *abd, int nabd1, int ipn, int *info, hipStream_t st, int nst,
+                   int semidef)
 {
-	hipLaunchKernelGGL(setup_cg3_per_kernel, dim3(1), dim3(1024), 0, st, so, II, JJ, KK, abd, nabd1, ipn, info, nst == 4 ? 4 : 14);
+	hipLaunchKernelGGL(setup_cg3_per_kernel, dim3(1), dim3(1024), 0, st, so, II, JJ, KK, abd, nabd1, ipn, info, nst == 4 ? 4 : 14,
+	                   semidef);
 }
 
 void solve_cg3_per(real_t *q, const real_t *qf, int II, int JJ, int KK, const real_t *abd, real_t *bbd, int nabd1, int ipn,

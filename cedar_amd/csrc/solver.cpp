@@ -17,6 +17,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <limits>
 #include <utility>
 #include <vector>
 
@@ -150,7 +151,8 @@ real_t *dalloc(size_t n)
 
 // cedar_amd_solver_create with a batch capacity (plane relaxation builds its 2D solvers with one: planes_setup)
 static cedar_amd_solver *solver_create(int nd, len_t nx, len_t ny, len_t nz, int nstencil, const real_t *so, int own_device_so,
-                                       const cedar_amd_settings *settings, int batch, bool periodic_batch = false);
+                                       const cedar_amd_settings *settings, int batch, bool periodic_batch = false,
+                                       bool semidef = false);
 
 struct cedar_amd_solver {
 	int nd = 2;
@@ -176,6 +178,12 @@ struct cedar_amd_solver {
 	// periodic_many3d.hip / periodic_many2d.hip.  A periodic handle made any other way holds one item and the _many calls
 	// refuse it
 	bool per_batch = false;
+	// a handle of cedar_amd_solver_create_semidefinite: the operator is singular with the constants as null space.  Its
+	// coarsest factor is that of the coarsest matrix with the last diagonal entry doubled and every coarsest solve removes
+	// the mean (ibc == 0 too); only cedar_amd_solver_fcg_semidefinite / _many run a Krylov iteration on it.  pm: scratch
+	// of project_mean_many for nb_alloc items
+	bool semidef = false;
+	real_t *pm = nullptr;
 	// a second captured cycle: the two colours of a plane sweep may differ by one plane
 	hipGraphExec_t gexec2 = nullptr;
 	int gnb2 = 0;
@@ -554,11 +562,11 @@ void coarse_solve(cedar_amd_solver *s, real_t *x, const real_t *b, hipStream_t s
 	if (s->nd == 2 && s->st.ibc && s->nb > 1)
 		solve_cg2_per_many(x, b, C.II, C.JJ, s->ABD, s->bbd, s->nabd1, s->st.ibc, st, Batch{s->nb, C.npts});
 	else if (s->nd == 2 && s->st.ibc) solve_cg2_per(x, b, C.II, C.JJ, s->ABD, s->bbd, s->nabd1, s->st.ibc, st);
-	else if (s->nd == 2) solve_cg2(x, b, C.II, C.JJ, s->ABD, s->bbd, s->nabd1, s->nabd2, st, Batch{s->nb, C.npts});
+	else if (s->nd == 2) solve_cg2(x, b, C.II, C.JJ, s->ABD, s->bbd, s->nabd1, s->nabd2, st, Batch{s->nb, C.npts}, s->semidef);
 	else if (s->st.ibc && s->nb > 1)
 		solve_cg3_per_many(x, b, C.II, C.JJ, C.KK, s->ABD, s->bbd, s->nabd1, s->st.ibc, st, Batch{s->nb, C.npts});
 	else if (s->st.ibc) solve_cg3_per(x, b, C.II, C.JJ, C.KK, s->ABD, s->bbd, s->nabd1, s->st.ibc, st);
-	else solve_cg3(x, b, C.II, C.JJ, C.KK, s->ABD, s->bbd, s->nabd1, s->nabd2, st, Batch{s->nb, C.npts});
+	else solve_cg3(x, b, C.II, C.JJ, C.KK, s->ABD, s->bbd, s->nabd1, s->nabd2, st, Batch{s->nb, C.npts}, s->semidef);
 }
 
 // The LDS-resident small-level kernels serve the visit of 2D level L (lines_small.hip): each half of the visit is one launch
@@ -738,6 +746,51 @@ void cycle_on(cedar_amd_solver *s, real_t *x, const real_t *b, hipStream_t st)
 
 } // namespace
 
+// cedar_amd_solver_create_semidefinite's condition on the operator, checked on level 0 before any set-up: A 1 with the
+// vector of ones wrapped in the periodic directions and zero in the other ghosts, by the matrix-vector kernels the
+// cycle's tests use.  max_i |(A 1)_i| <= 1024 eps max_i |a_ii|: a row has at most 27 terms, so its rounded sum lies within
+// 54 eps of the diagonal; the factor of about 20 on top covers how callers assemble their coefficients.  A condition, not
+// a measurement.
+static bool null_space_is_constants(const cedar_amd_solver *s, hipStream_t st)
+{
+	const Level &L = s->lv[0];
+	const int c = s->st.ibc;
+	const bool px = s->nd == 2 ? c == 2 || c == 3 : c == 2 || c == 3 || c == 6 || c == 8;
+	const bool py = s->nd == 2 ? c == 1 || c == 3 : c == 1 || c == 3 || c == 7 || c == 8;
+	const bool pz = s->nd == 3 && c >= 5;
+	std::vector<real_t> h(L.npts);
+	for (int k = 0; k < L.KK; k++)
+		for (int j = 0; j < L.JJ; j++)
+			for (int i = 0; i < L.II; i++) {
+				const bool in = (px || (i > 0 && i < L.II - 1)) && (py || (j > 0 && j < L.JJ - 1))
+				                && (pz || s->nd == 2 || (k > 0 && k < L.KK - 1));
+				h[(size_t)i + (size_t)L.II * ((size_t)j + (size_t)L.JJ * k)] = in ? 1.0 : 0.0;
+			}
+	// set-up only: two level-0 vectors on the device and two on the host for the length of this call (a failing
+	// CEDAR_HIP_CHECK aborts the process, so there is no path that returns without the two frees below); a max-reduction
+	// on the device would spare the host copies
+	real_t *ones = dalloc_raw(L.npts), *a1 = dalloc(L.npts);
+	CEDAR_HIP_CHECK(hipMemcpyAsync(ones, h.data(), L.npts * sizeof(real_t), hipMemcpyHostToDevice, st));
+	if (s->nd == 2) matvec2(L.A, ones, a1, L.II, L.JJ, L.nst, st);
+	else matvec3(L.A, ones, a1, L.II, L.JJ, L.KK, L.nst, st);
+	std::vector<real_t> d(L.npts);
+	CEDAR_HIP_CHECK(hipMemcpyAsync(h.data(), a1, L.npts * sizeof(real_t), hipMemcpyDeviceToHost, st));
+	CEDAR_HIP_CHECK(hipMemcpyAsync(d.data(), L.A, L.npts * sizeof(real_t), hipMemcpyDeviceToHost, st)); // the diagonal: slot 0
+	CEDAR_HIP_CHECK(hipStreamSynchronize(st));
+	(void)hipFree(ones); (void)hipFree(a1);
+	real_t worst = 0.0, diag = 0.0;
+	bool finite = true;
+	for (int k = s->nd == 3 ? 1 : 0; k < (s->nd == 3 ? L.KK - 1 : 1); k++)
+		for (int j = 1; j < L.JJ - 1; j++)
+			for (int i = 1; i < L.II - 1; i++) {
+				const size_t x = (size_t)i + (size_t)L.II * ((size_t)j + (size_t)L.JJ * k);
+				finite = finite && std::isfinite(h[x]) && std::isfinite(d[x]);
+				worst = std::max(worst, std::fabs(h[x]));
+				diag = std::max(diag, std::fabs(d[x]));
+			}
+	return finite && worst <= 1024.0 * std::numeric_limits<real_t>::epsilon() * diag;
+}
+
 extern "C" {
 
 void cedar_amd_default_settings(cedar_amd_settings *s)
@@ -769,7 +822,7 @@ cedar_amd_solver *cedar_amd_solver_create(int nd, len_t nx, len_t ny, len_t nz, 
 } // extern "C"
 
 static cedar_amd_solver *solver_create(int nd, len_t nx, len_t ny, len_t nz, int nstencil, const real_t *so, int own_device_so,
-                                       const cedar_amd_settings *settings, int batch, bool periodic_batch)
+                                       const cedar_amd_settings *settings, int batch, bool periodic_batch, bool semidef)
 {
 	hipStream_t st = current_stream();
 	cedar_amd_solver *s = new cedar_amd_solver;
@@ -837,6 +890,19 @@ static cedar_amd_solver *solver_create(int nd, len_t nx, len_t ny, len_t nz, int
 		F0.A = dalloc(F0.npts * nstencil);
 		CEDAR_HIP_CHECK(hipMemcpyAsync(F0.A, so, F0.npts * nstencil * sizeof(real_t),
 		                               is_device_ptr(so) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
+	}
+	if (semidef) {
+		// before any set-up: the null space must be the constants (null_space_is_constants)
+		if (!null_space_is_constants(s, st)) {
+			char msg[] = "cedar_amd_solver_create_semidefinite: the operator's null space is not the constants: max |A 1| "
+			             "exceeds 1024 eps max |a_ii| (ones wrapped in the periodic directions, zero in the other ghosts); "
+			             "no solver created";
+			print_error(msg);
+			cedar_amd_solver_destroy(s);
+			return nullptr;
+		}
+		s->semidef = true;
+		s->pm = dalloc_raw(project_mean_doubles(s->nb_alloc));
 	}
 	for (int l = 1; l < nlev; l++) {
 		const Level &F = s->lv[l - 1];
@@ -931,10 +997,11 @@ static cedar_amd_solver *solver_create(int nd, len_t nx, len_t ny, len_t nz, int
 			if (F.nst == 14 && !s->st.ibc && relax3_psum_wanted(F.II, F.JJ, F.KK)) F.T = dalloc_raw(F.npts);
 		}
 	}
-	if (nd == 2 && s->st.ibc) setup_cg2_per(C.A, C.II, C.JJ, C.nst, s->ABD, s->nabd1, s->st.ibc, s->dinfo, st);
-	else if (nd == 2) setup_cg2(C.A, C.II, C.JJ, C.nst, s->ABD, s->nabd1, s->nabd2, s->dinfo, st);
-	else if (s->st.ibc) setup_cg3_per(C.A, C.II, C.JJ, C.KK, s->ABD, s->nabd1, s->st.ibc, s->dinfo, st, C.nst);
-	else setup_cg3(C.A, C.II, C.JJ, C.KK, C.nst, s->ABD, s->nabd1, s->nabd2, s->dinfo, st);
+	// (a semidefinite handle: the last unknown's diagonal entry is doubled before the factorisation)
+	if (nd == 2 && s->st.ibc) setup_cg2_per(C.A, C.II, C.JJ, C.nst, s->ABD, s->nabd1, s->st.ibc, s->dinfo, st, s->semidef);
+	else if (nd == 2) setup_cg2(C.A, C.II, C.JJ, C.nst, s->ABD, s->nabd1, s->nabd2, s->dinfo, st, s->semidef);
+	else if (s->st.ibc) setup_cg3_per(C.A, C.II, C.JJ, C.KK, s->ABD, s->nabd1, s->st.ibc, s->dinfo, st, C.nst, s->semidef);
+	else setup_cg3(C.A, C.II, C.JJ, C.KK, C.nst, s->ABD, s->nabd1, s->nabd2, s->dinfo, st, s->semidef);
 	int info = 0;
 	CEDAR_HIP_CHECK(hipMemcpyAsync(&info, s->dinfo, sizeof(int), hipMemcpyDeviceToHost, st));
 	CEDAR_HIP_CHECK(hipStreamSynchronize(st));
@@ -973,7 +1040,7 @@ void cedar_amd_solver_destroy(cedar_amd_solver *s)
 	(void)hipFree(s->kr); (void)hipFree(s->kz); (void)hipFree(s->kw); (void)hipFree(s->kp[0]); (void)hipFree(s->kp[1]);
 	(void)hipFree(s->kslab); (void)hipFree(s->ksc);
 	if (!s->shared_abd) (void)hipFree(s->ABD);
-	(void)hipFree(s->bbd); (void)hipFree(s->red); (void)hipFree(s->dinfo);
+	(void)hipFree(s->bbd); (void)hipFree(s->red); (void)hipFree(s->dinfo); (void)hipFree(s->pm);
 	for (auto t : s->pstreams) (void)hipStreamDestroy(t);
 	for (auto e : s->pevents) (void)hipEventDestroy(e);
 	if (s->pfork) (void)hipEventDestroy(s->pfork);
@@ -987,6 +1054,18 @@ static bool null_handle(const void *s, const char *who)
 	if (s) return false;
 	char msg[160];
 	snprintf(msg, sizeof(msg), "%s: NULL solver handle (cedar_amd_solver_create reported why no solver was created)", who);
+	print_error(msg);
+	return true;
+}
+
+// what a handle of cedar_amd_solver_create_semidefinite is not served by: the Krylov calls that do not project, the bare
+// preconditioner and the single-precision switches.  Reported, nothing written
+static bool semidef_refused(const cedar_amd_solver *s, const char *who, const char *tail = "nothing done")
+{
+	if (!s->semidef) return false;
+	char msg[256];
+	snprintf(msg, sizeof(msg), "%s: a semidefinite handle (cedar_amd_solver_create_semidefinite) is served by "
+	                           "cedar_amd_solver_fcg_semidefinite / _many only; %s", who, tail);
 	print_error(msg);
 	return true;
 }
@@ -1073,7 +1152,7 @@ int cedar_amd_solver_fp32_levels(const cedar_amd_solver *s)
 // (cedar_amd_solver_use_fp32_operator_all)
 static int op32_switch(cedar_amd_solver *s, int min_rows, bool batch, const char *who, bool seven = false)
 {
-	if (null_handle(s, who)) return -1;
+	if (null_handle(s, who) || semidef_refused(s, who, "the handle is unchanged")) return -1;
 	const char *why = nullptr;
 	if (s->nd != 3) why = "2D handles are not supported";
 	else if (s->st.ibc != 0) why = "periodic boundary conditions (ibc != 0) are not supported";
@@ -1173,7 +1252,7 @@ enum { OP32_2D_DEFAULT_MIN_ROWS = 1024 };
 int cedar_amd_solver_use_fp32_operator_2d(cedar_amd_solver *s, int min_rows)
 {
 	const char *who = "cedar_amd_solver_use_fp32_operator_2d";
-	if (null_handle(s, who)) return -1;
+	if (null_handle(s, who) || semidef_refused(s, who, "the handle is unchanged")) return -1;
 	auto refuse = [&](const char *reason) {
 		char msg[256];
 		snprintf(msg, sizeof(msg), "%s: %s; the handle is unchanged", who, reason);
@@ -1294,7 +1373,7 @@ enum { OP32_LINES_DEFAULT_MIN_ROWS = 1024 };
 int cedar_amd_solver_use_fp32_operator_lines(cedar_amd_solver *s, int min_rows)
 {
 	const char *who = "cedar_amd_solver_use_fp32_operator_lines";
-	if (null_handle(s, who)) return -1;
+	if (null_handle(s, who) || semidef_refused(s, who, "the handle is unchanged")) return -1;
 	auto refuse = [&](const char *reason) {
 		char msg[256];
 		snprintf(msg, sizeof(msg), "%s: %s; the handle is unchanged", who, reason);
@@ -1376,7 +1455,7 @@ int cedar_amd_solver_fp32_interp_levels(const cedar_amd_solver *s)
 int cedar_amd_solver_use_fp32_interpolation(cedar_amd_solver *s, int min_rows)
 {
 	const char *who = "cedar_amd_solver_use_fp32_interpolation";
-	if (null_handle(s, who)) return -1;
+	if (null_handle(s, who) || semidef_refused(s, who, "the handle is unchanged")) return -1;
 	auto refuse = [&](const char *reason) {
 		char msg[256];
 		snprintf(msg, sizeof(msg), "%s: %s; the handle is unchanged", who, reason);
@@ -1596,6 +1675,36 @@ cedar_amd_solver *cedar_amd_solver_create_many_periodic2(len_t nx, len_t ny, int
 	return s;
 }
 
+// A semidefinite operator whose null space is the constants (pure Neumann, fully periodic; include/cedar_amd.h).  The
+// boundary code keeps its meaning -- codes below zero stay refused everywhere -- and the request is this call.  What the
+// creation call for (nd, ibc, max_rhs) refuses is refused here under its name first; solver_create then checks the null
+// space, doubles the last diagonal entry of the coarsest matrix and marks the handle
+cedar_amd_solver *cedar_amd_solver_create_semidefinite(int nd, len_t nx, len_t ny, len_t nz, int nstencil, const real_t *so,
+                                                       int own_device_so, const cedar_amd_settings *settings, int max_rhs)
+{
+	cedar_amd_settings st;
+	if (settings) st = *settings;
+	else cedar_amd_default_settings(&st);
+	auto refuse = [](const char *why) {
+		char msg[256];
+		snprintf(msg, sizeof(msg), "cedar_amd_solver_create_semidefinite: %s; no solver created", why);
+		print_error(msg);
+		return (cedar_amd_solver *)nullptr;
+	};
+	if (max_rhs < 1 || max_rhs > CEDAR_AMD_MAX_RHS) return refuse("max_rhs must be 1 .. 32");
+	if (nd != 2 && nd != 3) return refuse("nd must be 2 or 3");
+	if (st.ibc < 0) return refuse("boundary codes below zero are not served (ibc keeps its meaning: 0, 2D 1..3, 3D 1..3 and 5..8)");
+	if (st.relaxation >= CEDAR_AMD_RELAX_PLANE_XY) return refuse("plane relaxation is not served on a semidefinite operator");
+	// a batch: what cedar_amd_solver_create_many_periodic / _periodic2 refuse beyond solver_create (for ibc == 0 too: a
+	// batch handle that quietly held one right-hand side would not be what was asked for).  These two rules restate
+	// theirs, because this call must reach solver_create itself to pass the semidefinite flag: keep them in step
+	if (max_rhs > 1 && st.cycle != 0) return refuse("max_rhs > 1: only the V-cycle is supported");
+	if (max_rhs > 1 && nd == 3 && st.relaxation != CEDAR_AMD_RELAX_POINT) return refuse("max_rhs > 1: only point relaxation is supported");
+	cedar_amd_solver *s = solver_create(nd, nx, ny, nz, nstencil, so, own_device_so, settings, max_rhs, max_rhs > 1 && st.ibc != 0, true);
+	if (!s) return refuse("refused as reported above");
+	return s;
+}
+
 int cedar_amd_solver_max_rhs(const cedar_amd_solver *s) { return null_handle(s, "cedar_amd_solver_max_rhs") ? 0 : s->nb_alloc; }
 
 // what the batched entry points cannot do: reported, nothing written
@@ -1771,8 +1880,16 @@ static void pcg_precondition(cedar_amd_solver *s, int nmg, hipStream_t st)
 // flexible (cedar_amd_solver_fcg / _fcg_many, multigrid preconditioner only): the dots after the preconditioner also form
 // w.z -- s->kw is still w_k = A p_k there, the next direction pass has not run -- and beta is the Polak-Ribiere one
 // (krylov.hip pcg_rho_flex), which needs no symmetry of M.  Nothing else of the loop changes.
+// project (cedar_amd_solver_fcg_semidefinite / _many): A x = P b with mean(x) = 0, P v = v - mean_interior(v) 1.  r0 := P r0
+// once it is formed (b is not written) and x := P x of every item before the final wrap; in between x's constant part
+// drifts and the recurrence does not see it.  The multigrid preconditioner is applied as P M P: r := P r before the cycle
+// and z := P z after it, on the active items.  In exact arithmetic that changes nothing the recurrence sees (w = A p has
+// no constant part), in floating point it is what makes the history reproducible: the rounding of w leaves a constant
+// in r that never shrinks, the cycle answers a constant with a large smooth correction, and the constant the cycle
+// leaves in z is cancellation noise in the next w.  Measured on the statement: a relative 1e-16
+// change of z moves the history entries above 1e-10 by 4e-7 to 4e-6 without the two projections and by 1e-13 with them.
 static int pcg_run(cedar_amd_solver *s, int nrhs, const real_t *b, real_t *x, const cedar_amd_pcg_settings &p, real_t *hist,
-                   int *iters, const char *who, bool flexible = false)
+                   int *iters, const char *who, bool flexible = false, bool project = false)
 {
 	pcg_alloc(s, nrhs == 1 ? 1 : s->nb_alloc);
 	Level &L = s->lv[0];
@@ -1815,8 +1932,13 @@ static int pcg_run(cedar_amd_solver *s, int nrhs, const real_t *b, real_t *x, co
 		else pcg_update_many(zmode, pn != nullptr, X, s->kr, pn, w, Z, L.A, L.II, L.JJ, L.KK, first, s->kslab, s->ksc, st, bt, active);
 	};
 	// z = M^-1 r of the new residuals, then their dots (flexible: w.z with them)
-	auto precondition_dots = [&]() {
+	auto precondition = [&](bool r_projected) {
+		if (project && !r_projected) project_mean_many(s->kr, L.II, L.JJ, L.KK, s->pm, st, bt, active);
 		pcg_precondition(s, p.nmg_cycles, st);
+		if (project) project_mean_many(s->kz, L.II, L.JJ, L.KK, s->pm, st, bt, active);
+	};
+	auto precondition_dots = [&]() {
+		precondition(false);
 		if (!flexible) update(2, nullptr, false);
 		else if (nrhs == 1) pcg_dots_wz(s->kr, Z, s->kw, L.II, L.JJ, L.KK, false, s->kslab, s->ksc, st);
 		else pcg_dots_wz_many(s->kr, Z, s->kw, L.II, L.JJ, L.KK, false, s->kslab, s->ksc, st, bt, active);
@@ -1830,7 +1952,8 @@ static int pcg_run(cedar_amd_solver *s, int nrhs, const real_t *b, real_t *x, co
 	zero_fill(s->ksc, (size_t)PCG_NSC * nrhs, st);
 	wrap_x();
 	residual_true(s, L, X, sb.get(), s->kr, st);
-	if (zm == 2) pcg_precondition(s, p.nmg_cycles, st);
+	if (project) project_mean_many(s->kr, L.II, L.JJ, L.KK, s->pm, st, bt, active);
+	if (zm == 2) precondition(project); // (r0 has just been projected)
 	update(zm, nullptr, true);
 	scalars();
 	for (int m = 0; m < nrhs; m++) {
@@ -1858,6 +1981,7 @@ static int pcg_run(cedar_amd_solver *s, int nrhs, const real_t *b, real_t *x, co
 		}
 		if (zm == 2 && !rule.mnorm && k + 1 < p.max_iter && active) precondition_dots(); // z of the new residuals, for the next direction
 	}
+	if (project) project_mean_many(X, L.II, L.JJ, L.KK, s->pm, st, bt, nrhs >= 32 ? ~0u : (1u << nrhs) - 1u);
 	wrap_x();
 	launch_check(who);
 	int most = 0;
@@ -1871,7 +1995,7 @@ static int pcg_run(cedar_amd_solver *s, int nrhs, const real_t *b, real_t *x, co
 int cedar_amd_solver_pcg(cedar_amd_solver *s, const real_t *b, real_t *x, const cedar_amd_pcg_settings *settings, real_t *hist)
 {
 	const char *who = "cedar_amd_solver_pcg";
-	if (null_handle(s, who)) return -1;
+	if (null_handle(s, who) || semidef_refused(s, who)) return -1;
 	const cedar_amd_pcg_settings p = pcg_settings_or_default(settings);
 	if (pcg_refused(s, p, who)) return -1;
 	return pcg_run(s, 1, b, x, p, hist, nullptr, who);
@@ -1882,7 +2006,7 @@ int cedar_amd_solver_pcg_many(cedar_amd_solver *s, int nrhs, const real_t *b, re
                               real_t *hist, int *iters)
 {
 	const char *who = "cedar_amd_solver_pcg_many";
-	if (null_handle(s, who) || many_refused(s, nrhs, who)) return -1;
+	if (null_handle(s, who) || semidef_refused(s, who) || many_refused(s, nrhs, who)) return -1;
 	const cedar_amd_pcg_settings p = pcg_settings_or_default(settings);
 	if (pcg_refused(s, p, who)) return -1;
 	return pcg_run(s, nrhs, b, x, p, hist, iters, who);
@@ -1911,7 +2035,7 @@ static bool fcg_refused(const cedar_amd_solver *s, const cedar_amd_pcg_settings 
 int cedar_amd_solver_fcg(cedar_amd_solver *s, const real_t *b, real_t *x, const cedar_amd_pcg_settings *settings, real_t *hist)
 {
 	const char *who = "cedar_amd_solver_fcg";
-	if (null_handle(s, who)) return -1;
+	if (null_handle(s, who) || semidef_refused(s, who)) return -1;
 	const cedar_amd_pcg_settings p = pcg_settings_or_default(settings);
 	if (fcg_refused(s, p, who)) return -1;
 	return pcg_run(s, 1, b, x, p, hist, nullptr, who, p.precon == CEDAR_AMD_PCG_PRECON_BMG);
@@ -1921,7 +2045,7 @@ int cedar_amd_solver_fcg_many(cedar_amd_solver *s, int nrhs, const real_t *b, re
                               real_t *hist, int *iters)
 {
 	const char *who = "cedar_amd_solver_fcg_many";
-	if (null_handle(s, who) || many_refused(s, nrhs, who)) return -1;
+	if (null_handle(s, who) || semidef_refused(s, who) || many_refused(s, nrhs, who)) return -1;
 	const cedar_amd_pcg_settings p = pcg_settings_or_default(settings);
 	if (fcg_refused(s, p, who)) return -1;
 	return pcg_run(s, nrhs, b, x, p, hist, iters, who, p.precon == CEDAR_AMD_PCG_PRECON_BMG);
@@ -1935,7 +2059,7 @@ int cedar_amd_solver_fcg_periodic(cedar_amd_solver *s, const real_t *b, real_t *
                                   real_t *hist)
 {
 	const char *who = "cedar_amd_solver_fcg_periodic";
-	if (null_handle(s, who)) return -1;
+	if (null_handle(s, who) || semidef_refused(s, who)) return -1;
 	const char *why = nullptr;
 	if (s->nb_alloc > 1) why = "handles of cedar_amd_solver_create_many with max_rhs > 1 are not supported";
 	else if (!b || !x) why = "b and x must not be NULL";
@@ -1958,7 +2082,7 @@ int cedar_amd_solver_fcg_periodic_many(cedar_amd_solver *s, int nrhs, const real
                                        const cedar_amd_pcg_settings *settings, real_t *hist, int *iters)
 {
 	const char *who = "cedar_amd_solver_fcg_periodic_many";
-	if (null_handle(s, who)) return -1;
+	if (null_handle(s, who) || semidef_refused(s, who)) return -1;
 	if (s->st.ibc == 0) return cedar_amd_solver_fcg_many(s, nrhs, b, x, settings, hist, iters);
 	if (many_refused(s, nrhs, who)) return -1;
 	if (!b || !x) {
@@ -1972,9 +2096,43 @@ int cedar_amd_solver_fcg_periodic_many(cedar_amd_solver *s, int nrhs, const real
 	return pcg_run(s, nrhs, b, x, p, hist, iters, who, p.precon == CEDAR_AMD_PCG_PRECON_BMG);
 }
 
+// Flexible CG on a handle of cedar_amd_solver_create_semidefinite (include/cedar_amd.h): cedar_amd_solver_fcg_periodic's
+// rules with the projections of pcg_run; the direction pass follows ibc (Dirichlet forms for 0, wrap-around otherwise)
+static bool semidef_wanted(const cedar_amd_solver *s, const real_t *b, const real_t *x, const char *who)
+{
+	const char *why = nullptr;
+	if (!s->semidef) why = "the handle was not made by cedar_amd_solver_create_semidefinite";
+	else if (!b || !x) why = "b and x must not be NULL";
+	if (!why) return true;
+	char msg[256];
+	snprintf(msg, sizeof(msg), "%s: %s; nothing done", who, why);
+	print_error(msg);
+	return false;
+}
+
+int cedar_amd_solver_fcg_semidefinite(cedar_amd_solver *s, const real_t *b, real_t *x, const cedar_amd_pcg_settings *settings,
+                                      real_t *hist)
+{
+	const char *who = "cedar_amd_solver_fcg_semidefinite";
+	if (null_handle(s, who) || !semidef_wanted(s, b, x, who)) return -1;
+	const cedar_amd_pcg_settings p = pcg_settings_or_default(settings);
+	if (fcg_refused(s, p, who, true)) return -1;
+	return pcg_run(s, 1, b, x, p, hist, nullptr, who, p.precon == CEDAR_AMD_PCG_PRECON_BMG, true);
+}
+
+int cedar_amd_solver_fcg_semidefinite_many(cedar_amd_solver *s, int nrhs, const real_t *b, real_t *x,
+                                           const cedar_amd_pcg_settings *settings, real_t *hist, int *iters)
+{
+	const char *who = "cedar_amd_solver_fcg_semidefinite_many";
+	if (null_handle(s, who) || !semidef_wanted(s, b, x, who) || many_refused(s, nrhs, who)) return -1;
+	const cedar_amd_pcg_settings p = pcg_settings_or_default(settings);
+	if (fcg_refused(s, p, who, true)) return -1;
+	return pcg_run(s, nrhs, b, x, p, hist, iters, who, p.precon == CEDAR_AMD_PCG_PRECON_BMG, true);
+}
+
 void cedar_amd_solver_precondition(cedar_amd_solver *s, real_t *z, const real_t *r)
 {
-	if (null_handle(s, "cedar_amd_solver_precondition")) return;
+	if (null_handle(s, "cedar_amd_solver_precondition") || semidef_refused(s, "cedar_amd_solver_precondition")) return;
 	if (pcg_refused(s, pcg_settings_or_default(nullptr), "cedar_amd_solver_precondition")) return;
 	pcg_alloc(s);
 	const Level &L = s->lv[0];

@@ -141,7 +141,12 @@ protected:
 		// solver.periodic-batch (default false): with periodic directions, keep that room on a periodic handle too
 		// (cedar_amd_solver_create_many_periodic); without the key a periodic solver holds one right-hand side
 		const bool periodic_batch = this->conf->template get<bool>("solver.periodic-batch", false);
-		if (st.ibc != 0 && max_rhs > 1 && periodic_batch)
+		// solver.semidefinite (default false): a singular operator whose null space is the constants -- pure Neumann, fully
+		// periodic (cedar_amd_solver_create_semidefinite; solved by multilevel::fcg_semidefinite); max_rhs is passed on
+		const bool semidefinite = this->conf->template get<bool>("solver.semidefinite", false);
+		if (semidefinite)
+			this->h = cedar_amd_solver_create_semidefinite(3, fop.shape(0), fop.shape(1), fop.shape(2), stencil_ndirs<fsten>::value, fop.data(), 0, &st, max_rhs);
+		else if (st.ibc != 0 && max_rhs > 1 && periodic_batch)
 			this->h = cedar_amd_solver_create_many_periodic(3, fop.shape(0), fop.shape(1), fop.shape(2), stencil_ndirs<fsten>::value, fop.data(), 0, &st, max_rhs);
 		else if (max_rhs == 1) this->h = cedar_amd_solver_create(3, fop.shape(0), fop.shape(1), fop.shape(2), stencil_ndirs<fsten>::value, fop.data(), 0, &st);
 		else this->h = cedar_amd_solver_create_many(3, fop.shape(0), fop.shape(1), fop.shape(2), stencil_ndirs<fsten>::value, fop.data(), 0, &st, max_rhs);

@@ -141,6 +141,9 @@ public:
 	// around, the ghost layers of b and x do not matter, x comes back with the periodic image in its ghosts.  A solver
 	// without periodic directions is served as by fcg().  The same pcg.* keys, `history` as after pcg().
 	void fcg_periodic(const grid_func & b, grid_func & x) { krylov(cedar_amd_solver_fcg_periodic, "fcg_periodic", b, x); }
+	// fcg on a solver made with solver.semidefinite: true (cedar_amd_solver_fcg_semidefinite): solves A x = P b with
+	// mean(x) = 0, P v = v - mean(v); b need not be compatible and is not written.  Results as after pcg()
+	void fcg_semidefinite(const grid_func & b, grid_func & x) { krylov(cedar_amd_solver_fcg_semidefinite, "fcg_semidefinite", b, x); }
 
 	// several right-hand sides in lockstep on the one hierarchy (cedar_amd_solver_solve_many; room for them is made with
 	// the key solver.max-rhs).  histories[m] / iterations[m]: item m's residual history cut to the cycles run and the
@@ -198,6 +201,12 @@ public:
 	void fcg_periodic_many(const std::vector<grid_func> & b, std::vector<grid_func> & x)
 	{
 		krylov_many(cedar_amd_solver_fcg_periodic_many, "fcg_periodic_many", b, x);
+	}
+	// fcg_semidefinite on several right-hand sides in lockstep (cedar_amd_solver_fcg_semidefinite_many): a solver made with
+	// solver.semidefinite: true and solver.max-rhs; results as after pcg_many()
+	void fcg_semidefinite_many(const std::vector<grid_func> & b, std::vector<grid_func> & x)
+	{
+		krylov_many(cedar_amd_solver_fcg_semidefinite_many, "fcg_semidefinite_many", b, x);
 	}
 
 	// pcg / fcg and their batched forms: one C entry point each, the same marshalling

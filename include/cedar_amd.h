@@ -485,7 +485,8 @@ int cedar_amd_solver_fcg(cedar_amd_solver *s, const real_t *b, real_t *x, const 
  * before the first residual, and carries it on return, like x after cedar_amd_solver_solve.  The operator given to
  * cedar_amd_solver_create holds the periodic image in its ghost layers, as for the cycle.
  * The operator must be definite, as for the cycle itself: a fully periodic operator with zero row sums (the pure
- * Laplacian) is singular, the coarsest factorisation fails on it, and such problems are not served.
+ * Laplacian) is singular and the coarsest factorisation fails on it here; such problems are served by
+ * cedar_amd_solver_create_semidefinite and cedar_amd_solver_fcg_semidefinite below.
  * A handle with ibc = 0 forwards to cedar_amd_solver_fcg (results bit for bit, refusals its own).  Refused (print_error,
  * -1, nothing written): a NULL handle, b or x NULL, a handle of cedar_amd_solver_create_many that holds more than one
  * right-hand side, and the settings cedar_amd_solver_fcg refuses.  cedar_amd_solver_pcg, _fcg, _precondition and the
@@ -790,7 +791,8 @@ int cedar_amd_interp_add3_many(int nrhs, real_t *q, real_t *qc, real_t *so, real
  *  - Bits: item m of every result -- x, rel rows, iters -- has the bits of the single-vector periodic call on item m alone
  *    on a handle of cedar_amd_solver_create with the same settings.  The single-vector periodic path has no partial-sum
  *    sweep, so this holds at every size with no environment switch.
- *  - Out of scope: 2D periodic batches, periodic F-cycles on a batch, singular fully periodic operators, the rank-grid
+ *  - Out of scope: 2D periodic batches, periodic F-cycles on a batch, singular fully periodic operators (those take
+ *    cedar_amd_solver_create_semidefinite with max_rhs > 1), the rank-grid
  *    solvers. */
 cedar_amd_solver *cedar_amd_solver_create_many_periodic(int nd, len_t nx, len_t ny, len_t nz, int nstencil,
                                                         const real_t *so, int own_device_so,
@@ -858,7 +860,8 @@ int cedar_amd_pcg_direction_periodic_many(int nrhs, unsigned active, const real_
  *    alone on a handle of cedar_amd_solver_create with the same settings.  The 2D periodic single-vector path has no
  *    partial-sum sweep and no float view, so this holds at every size with no environment switch.
  *  - Out of scope: periodic F-cycles on a batch, a batched periodic y-line pipeline, the single-precision switches on
- *    periodic handles, singular fully periodic operators, the rank-grid solvers. */
+ *    periodic handles, singular fully periodic operators (cedar_amd_solver_create_semidefinite serves them), the
+ *    rank-grid solvers. */
 cedar_amd_solver *cedar_amd_solver_create_many_periodic2(len_t nx, len_t ny, int nstencil, const real_t *so,
                                                          int own_device_so, const cedar_amd_settings *settings, int max_rhs);
 /* The batched periodic 2D kernels one at a time on caller arrays (host or device; the nrhs items lie back to back with
@@ -889,6 +892,64 @@ int cedar_amd_solve_cg2_periodic_many(int nrhs, real_t *q, real_t *qf, len_t ii,
 int cedar_amd_pcg_direction2_periodic_many(int nrhs, unsigned active, const real_t *so, const real_t *z, const real_t *p,
                                            real_t *pn, real_t *w, len_t ii, len_t jj, int nstncl, int ibc, int first,
                                            real_t *sc);
+
+/* Singular problems: a symmetric positive SEMIdefinite operator whose null space is the constants -- the pressure or
+ * potential Poisson equation with pure Neumann or fully periodic boundaries, zero row sums.
+ *  - Requested by this creation call, not by a boundary code: settings->ibc keeps its meaning (0: no periodic direction,
+ *    for example pure Neumann; 1 .. 3 in 2D; 1 .. 3 and 5 .. 8 in 3D) and codes below zero stay refused everywhere.  The
+ *    reference's negative codes BMG_BCs_indef_* change exactly two rules, and a semidefinite handle applies those two:
+ *    the coarsest matrix is assembled as always and the diagonal entry of its LAST unknown is doubled before the
+ *    factorisation (BMG3_SymStd_SETUP_cg_LU.f90:143-145, 179-181, 590-593 and the 2D file likewise), and every coarsest
+ *    solve removes the mean of its solution over the interior, for ibc == 0 too (BMG3_SymStd_SOLVE_cg.f90:150-172; one lane
+ *    sums sequentially, i fastest, then j, then k).  Sweeps, transfers, the Galerkin product, line factors and ghost
+ *    refreshes are those of ibc.  On a residual with zero sum this coarse solve is exact.
+ *  - Served: max_rhs == 1: everything cedar_amd_solver_create accepts for that ibc except 3D plane relaxation -- 2D point
+ *    and line relaxation, 3D point relaxation, V(m,n), F-cycles, any num_levels.  max_rhs > 1: what the batch creation
+ *    call for that nd and ibc serves (cedar_amd_solver_create_many, _create_many_periodic, _create_many_periodic2),
+ *    V-cycles only.
+ *  - The operator: zero row sums, checked before any set-up -- max_i |(A 1)_i| <= 1024 eps max_i |a_ii| on level 0, the
+ *    vector of ones wrapped in the periodic directions and zero in the other ghosts.  A periodic operator must hold the
+ *    periodic image in ALL its ghost cells, the corners (and in 3D the edges) included: the periodic interpolation set-up
+ *    reads them.
+ *  - Refused (print_error, NULL, the message names cedar_amd_solver_create_semidefinite): whatever the corresponding
+ *    creation call refuses (its message first), ibc < 0, plane relaxation (it diverged on a semidefinite 27-point
+ *    operator when tried with the reference's rules; not served), max_rhs outside 1 .. 32, an F-cycle with max_rhs > 1, an
+ *    operator whose null space is not the constants.
+ *  - On such a handle cedar_amd_solver_vcycle, _solve, _vcycle_many, _solve_many, _get, _nlevels and _level_dims work
+ *    unchanged and run the semidefinite cycle.  cedar_amd_solver_solve needs a COMPATIBLE b (zero sum over the interior)
+ *    and does not project; its iterate's mean is whatever the cycles leave.  cedar_amd_solver_pcg, _fcg, _fcg_periodic,
+ *    their _many forms, _precondition and every use_fp32_* switch refuse it (print_error, -1, nothing written; the message
+ *    names cedar_amd_solver_fcg_semidefinite).
+ *  - Not offered: the bmg2_ / bmg3_ C interface, the rank-grid (domain-decomposed) solvers, the BMG*_SymStd_* drop-ins
+ *    (they keep refusing negative codes). */
+cedar_amd_solver *cedar_amd_solver_create_semidefinite(int nd, len_t nx, len_t ny, len_t nz, int nstencil,
+                                                       const real_t *so, int own_device_so,
+                                                       const cedar_amd_settings *settings, int max_rhs);
+/* Flexible CG on a semidefinite handle: solves A x = P b with mean(x) = 0, where P v = v - mean_interior(v) 1.  The
+ * rules of cedar_amd_solver_fcg_periodic / _fcg_periodic_many carry over: settings, hist layout, return value, stop tests,
+ * breakdown rules, host or device storage; precon = 3 takes the flexible beta, precon = 1 | 2 the standard one.  The
+ * direction pass follows ibc: the Dirichlet forms for 0, the wrap-around forms otherwise, single or batched.
+ * Projections: r0 = b - A x0 is replaced by P r0 (b itself is not written and need not be
+ * compatible; hist[0] = |P (b - A x0)|_2), and x by P x before it is returned (an item that froze early gets it once, at
+ * the end).  In between the iterate's constant part drifts freely; the recurrence does not see it.  The multigrid
+ * preconditioner (precon = 3) is applied as P M P -- r is projected before the cycle and z after it, in every iteration:
+ * the recurrence is the same in exact arithmetic, and in floating point its history no longer depends on rounding
+ * through the constants (1e-13 instead of 1e-6 of an entry near 1e-10).  2 n + 1 projections for n
+ * iterations, 24 bytes per point each.
+ * Refused (print_error, -1, nothing written): a NULL handle, a handle not made by cedar_amd_solver_create_semidefinite,
+ * b or x NULL, the settings cedar_amd_solver_fcg refuses, and for _many what the batched calls refuse (nrhs < 1 or above
+ * max_rhs, an F-cycle).  Item m of a batch has the bits of the single-vector call on item m alone. */
+int cedar_amd_solver_fcg_semidefinite(cedar_amd_solver *s, const real_t *b, real_t *x, const cedar_amd_pcg_settings *p,
+                                      real_t *hist);
+int cedar_amd_solver_fcg_semidefinite_many(cedar_amd_solver *s, int nrhs, const real_t *b, real_t *x,
+                                           const cedar_amd_pcg_settings *p, real_t *hist, int *iters);
+/* The projection as a kernel of its own: v := v - mean_interior(v) on each item m of `active` (bit m) among nrhs level
+ * vectors of ii x jj x kk doubles, ghosts included, back to back (kk = 1: a 2D level); host or device.  Ghost cells and
+ * items outside `active` are not written.  mean (nrhs doubles, may be NULL) receives the means, 0 for an item outside
+ * `active`.  A two-stage sum in a fixed order without atomics: an item's result depends on its extents and values only,
+ * not on nrhs or `active`.  It moves 8 bytes per point in the sum and 16 in the shift.  0, or -1 (print_error, nothing
+ * written) for nrhs outside 1 .. 32, a NULL v or an extent below 3. */
+int cedar_amd_project_mean(int nrhs, unsigned active, real_t *v, len_t ii, len_t jj, len_t kk, real_t *mean);
 
 /* plane relaxation as a kernel of its own -- kernels::plane_relax<stypes, rdir>::setup(so) / run(so, x, b, dir)
  * (include/cedar/kernels/plane_relax.h:10-33; include/cedar/3d/relax_planes.h:164-246, src/3d/relax_planes.cc).
