@@ -113,9 +113,8 @@ static bool bc3(int jpn, const char *who)
 // be even (the reference's example uses even extents; odd ones are refused rather than guessed)
 static bool even_periodic(int ipn, len_t iif, len_t jjf, len_t kkf, const char *who)
 {
-	const bool px = ipn == 2 || ipn == 3 || ipn == 6 || ipn == 8, py = ipn == 1 || ipn == 3 || ipn == 7 || ipn == 8,
-	           pz = ipn >= 5 && ipn <= 8;
-	if ((px && (iif & 1)) || (py && (jjf & 1)) || (pz && (kkf & 1))) {
+	const PerDirs pd = per_dirs(3, ipn);
+	if ((pd.x && (iif & 1)) || (pd.y && (jjf & 1)) || (pd.z && (kkf & 1))) {
 		char buf[200];
 		snprintf(buf, sizeof(buf), "%s: a periodic direction needs an even extent (got %u x %u x %u, code %d)", who,
 		         (unsigned)iif - 2, (unsigned)jjf - 2, (unsigned)kkf - 2, ipn);
@@ -380,7 +379,7 @@ void BMG2_SymStd_SETUP_lines_x(real_t *SO, real_t *SOR, len_t Nx, len_t Ny, int 
 	if (ipn < 0) return;
 	size_t P = (size_t)Nx * Ny;
 	Staged sso(SO, P * NStncl, true, false), ssor(SOR, P * 2, true, true);
-	setup_lines_x(sso.get(), ssor.get(), (int)Nx, (int)Ny, current_stream(), ipn == 2 || ipn == 3);
+	setup_lines_x(sso.get(), ssor.get(), (int)Nx, (int)Ny, current_stream(), per_dirs(2, ipn).x);
 }
 
 void BMG2_SymStd_SETUP_lines_y(real_t *SO, real_t *SOR, len_t Nx, len_t Ny, int NStncl, int JPN)
@@ -389,7 +388,7 @@ void BMG2_SymStd_SETUP_lines_y(real_t *SO, real_t *SOR, len_t Nx, len_t Ny, int 
 	if (ipn < 0) return;
 	size_t P = (size_t)Nx * Ny;
 	Staged sso(SO, P * NStncl, true, false), ssor(SOR, P * 2, true, true);
-	setup_lines_y(sso.get(), ssor.get(), (int)Nx, (int)Ny, current_stream(), ipn == 1 || ipn == 3);
+	setup_lines_y(sso.get(), ssor.get(), (int)Nx, (int)Ny, current_stream(), per_dirs(2, ipn).y);
 }
 
 void BMG2_SymStd_relax_lines_x(int k, real_t *SO, real_t *QF, real_t *Q, real_t *SOR, real_t *B,
@@ -1237,8 +1236,8 @@ int cedar_amd_interp_add3_many(int nrhs, real_t *q, real_t *qc, real_t *so, real
 }
 
 // ------------------------------------------------------------------ the batched periodic 3D kernels (periodic_many3d.hip,
-// krylov.hip), one launcher each: nrhs items back to back, the operator arrays shared; ibc = 0 forwards to the Dirichlet
-// call where one exists
+// periodic3d.hip's coarsest solve, krylov.hip), one launcher each: nrhs items back to back, the operator arrays shared;
+// ibc = 0 forwards to the Dirichlet call where one exists
 static bool per_many_refused(int nrhs, bool arrays_ok, bool nst_ok, int ibc, const char *who)
 {
 	if (many_args_refused(nrhs, arrays_ok, nst_ok, who)) return true;
@@ -1305,8 +1304,8 @@ int cedar_amd_solve_cg3_periodic_many(int nrhs, real_t *q, real_t *qf, len_t ii,
 	const size_t P = (size_t)ii * jj * kk;
 	Staged sq(q, P * nrhs, true, true), sqf(qf, P * nrhs, true, false), sabd(abd, (size_t)nabd1 * N, true, false),
 	    sb(bbd, N * nrhs, false, true);
-	solve_cg3_per_many(sq.get(), sqf.get(), (int)ii, (int)jj, (int)kk, sabd.get(), sb.get(), (int)nabd1, ibc, current_stream(),
-	                   Batch{nrhs, P});
+	solve_cg3_per(sq.get(), sqf.get(), (int)ii, (int)jj, (int)kk, sabd.get(), sb.get(), (int)nabd1, ibc, current_stream(),
+	              Batch{nrhs, P});
 	return 0;
 }
 
@@ -1329,8 +1328,9 @@ int cedar_amd_pcg_direction_periodic_many(int nrhs, unsigned active, const real_
 }
 
 // ------------------------------------------------------------------ the batched periodic 2D kernels (periodic_many2d.hip,
-// krylov.hip), one launcher each: nrhs items back to back with stride ii*jj, the operator arrays shared.  Only the
-// direction pass has a Dirichlet batched twin behind a kernel-level call: the other four refuse ibc = 0
+// periodic2d.hip's transfers and coarsest solve, krylov.hip), one launcher each: nrhs items back to back with stride ii*jj,
+// the operator arrays shared.  Only the direction pass has a Dirichlet batched twin behind a kernel-level call: the other
+// four refuse ibc = 0
 static bool per_many2_refused(int nrhs, bool arrays_ok, bool nst_ok, int ibc, bool dirichlet_twin, const char *who)
 {
 	const char *why = nrhs < 1 || nrhs > CEDAR_AMD_MAX_RHS ? "nrhs must be 1 .. 32" : !nst_ok ? "nstncl must be 3 or 5"
@@ -1367,8 +1367,8 @@ int cedar_amd_restrict2_periodic_many(int nrhs, real_t *q, real_t *qc, real_t *c
 	if (per_many2_refused(nrhs, q && qc && ci, true, ibc, false, "cedar_amd_restrict2_periodic_many")) return -1;
 	const size_t P = (size_t)ii * jj, PC = (size_t)iic * jjc;
 	Staged sq(q, P * nrhs, true, true), sqc(qc, PC * nrhs, true, true), sci(ci, PC * 8, true, false);
-	restrict2_per_many(sq.get(), sqc.get(), sci.get(), (int)ii, (int)jj, (int)iic, (int)jjc, ibc, current_stream(), Batch{nrhs, P},
-	                   Batch{nrhs, PC});
+	restrict2_per(sq.get(), sqc.get(), sci.get(), (int)ii, (int)jj, (int)iic, (int)jjc, ibc, current_stream(), Batch{nrhs, P},
+	              Batch{nrhs, PC});
 	return 0;
 }
 
@@ -1380,8 +1380,8 @@ int cedar_amd_interp_add2_periodic_many(int nrhs, real_t *q, real_t *qc, real_t 
 	const size_t P = (size_t)ii * jj, PC = (size_t)iic * jjc;
 	Staged sq(q, P * nrhs, true, true), sqc(qc, PC * nrhs, true, false), sr(res, P * nrhs, true, true),
 	    sso(so, P * nstncl, true, false), sci(ci, PC * 8, true, false);
-	interp_add2_per_many(sq.get(), sqc.get(), sr.get(), sso.get(), sci.get(), (int)iic, (int)jjc, (int)ii, (int)jj, ibc,
-	                     current_stream(), Batch{nrhs, P}, Batch{nrhs, PC});
+	interp_add2_per(sq.get(), sqc.get(), sr.get(), sso.get(), sci.get(), (int)iic, (int)jjc, (int)ii, (int)jj, ibc,
+	                current_stream(), Batch{nrhs, P}, Batch{nrhs, PC});
 	return 0;
 }
 
@@ -1402,8 +1402,8 @@ int cedar_amd_solve_cg2_periodic_many(int nrhs, real_t *q, real_t *qf, len_t ii,
 	const size_t P = (size_t)ii * jj;
 	Staged sq(q, P * nrhs, true, true), sqf(qf, P * nrhs, true, false), sabd(abd, (size_t)nabd1 * N, true, false),
 	    sb(bbd, N * nrhs, false, true);
-	solve_cg2_per_many(sq.get(), sqf.get(), (int)ii, (int)jj, sabd.get(), sb.get(), (int)nabd1, ibc, current_stream(),
-	                   Batch{nrhs, P});
+	solve_cg2_per(sq.get(), sqf.get(), (int)ii, (int)jj, sabd.get(), sb.get(), (int)nabd1, ibc, current_stream(),
+	              Batch{nrhs, P});
 	return 0;
 }
 

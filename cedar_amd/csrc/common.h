@@ -286,13 +286,32 @@ void lines_rhs2(const real_t *so, const real_t *qf, const real_t *q, real_t *out
 void lines_store2(const real_t *in, real_t *q, int II, int JJ, int dir, int lb, hipStream_t st);
 void lines_carry(real_t *y, const real_t *p, const real_t *c, int nlines, int n, int ld, hipStream_t st);
 void affine_lines(real_t *y, const real_t *a, const real_t *div, int nlines, int n, int ld, int reverse, hipStream_t st);
+// The one table of the boundary codes: the periodic directions of a code (2D: 1 y, 2 x, 3 xy; 3D: 1 y, 2 x, 3 xy, 5 z, 6 xz,
+// 7 yz, 8 xyz).  Host code asks it where it needs a direction; kernels take the PerDirs as an argument or ask it themselves.
+struct PerDirs {
+	int x, y, z;
+};
+__host__ __device__ static inline PerDirs per_dirs(int nd, int ibc)
+{
+	return PerDirs{ibc == 2 || ibc == 3 || (nd == 3 && (ibc == 6 || ibc == 8)), ibc == 1 || ibc == 3 || (nd == 3 && (ibc == 7 || ibc == 8)),
+	               nd == 3 && ibc >= 5 && ibc <= 8};
+}
+// the 3D code with x taken out (0, 1 y, 5 z, 7 yz): what is left to refresh behind a kernel that did the x ghosts itself
+__host__ __device__ static inline int per3_without_x(int ibc)
+{
+	const PerDirs pd = per_dirs(3, ibc);
+	return pd.z ? (pd.y ? 7 : 5) : (pd.y ? 1 : 0);
+}
 // 2D periodic boundary conditions (periodic2d.hip); ipn = 1 per_y, 2 per_x, 3 per_xy
 void wrap2(real_t *q, int II, int JJ, int nplanes, int do_y, int do_x, hipStream_t st);
 int relax2_gs_per(const real_t *so, const real_t *qf, real_t *q, const real_t *sor,
                   int II, int JJ, int nstncl, int updown, int ipn, hipStream_t st); // 1 = rows too long
-void restrict2_per(real_t *q, real_t *qc, const real_t *ci, int Nx, int Ny, int Nxc, int Nyc, int ipn, hipStream_t st);
+// the two transfers and the coarsest solve take a batch stored with the level's stride II*JJ (wrap2 takes the items as
+// planes); item m has the bits of the call on item m alone
+void restrict2_per(real_t *q, real_t *qc, const real_t *ci, int Nx, int Ny, int Nxc, int Nyc, int ipn, hipStream_t st,
+                   Batch bf = Batch(), Batch bc = Batch());
 void interp_add2_per(real_t *q, const real_t *qc, real_t *res, const real_t *so, const real_t *ci,
-                     int IIC, int JJC, int IIF, int JJF, int ipn, hipStream_t st);
+                     int IIC, int JJC, int IIF, int JJF, int ipn, hipStream_t st, Batch bf = Batch(), Batch bc = Batch());
 void galerkin2_per(const real_t *so, real_t *soc, const real_t *ci, int IIF, int JJF, int IIC, int JJC, int ifd, int ipn,
                    hipStream_t st);
 void setup_interp2_per(const real_t *so, real_t *ci, int IIF, int JJF, int IIC, int JJC, int ifd, int ipn, hipStream_t st);
@@ -300,7 +319,8 @@ void setup_interp2_per(const real_t *so, real_t *ci, int IIF, int JJF, int IIC, 
 // factorisation -- a semidefinite operator whose null space is the constants (cedar_amd_solver_create_semidefinite)
 void setup_cg2_per(const real_t *so, int II, int JJ, int nstncl, real_t *abd, int nabd1, int ipn, int *info, hipStream_t st,
                    int semidef = 0);
-void solve_cg2_per(real_t *q, const real_t *qf, int II, int JJ, const real_t *abd, real_t *bbd, int nabd1, int ipn, hipStream_t st);
+void solve_cg2_per(real_t *q, const real_t *qf, int II, int JJ, const real_t *abd, real_t *bbd, int nabd1, int ipn, hipStream_t st,
+                   Batch bt = Batch()); // one lane per item, the factor shared; bbd: bt.n segments of (II-2)(JJ-2) doubles
 // 3D periodic boundary conditions (periodic3d.hip, relax3d.hip); ipn = 1 y, 2 x, 3 xy, 5 z, 6 xz, 7 yz, 8 xyz
 bool periodic3_code_ok(int ipn);
 void wrap3(real_t *a, int II, int JJ, int KK, int narrays, int ipn, hipStream_t st);
@@ -319,7 +339,7 @@ void galerkin3_per(const real_t *so, real_t *soc, const real_t *ci, int IIF, int
 void setup_cg3_per(const real_t *so, int II, int JJ, int KK, real_t *abd, int nabd1, int ipn, int *info, hipStream_t st,
                    int nst = 14, int semidef = 0); // nst: slots of so, 4 for a one-level seven-point handle
 void solve_cg3_per(real_t *q, const real_t *qf, int II, int JJ, int KK, const real_t *abd, real_t *bbd, int nabd1, int ipn,
-                   hipStream_t st);
+                   hipStream_t st, Batch bt = Batch()); // one workgroup per item, the factor shared; bbd: bt.n segments of N doubles
 // plane relaxation, the 3D side (planes.hip); dir 0 xy, 1 xz, 2 yz; stacked 2D arrays, slot q = plane beg + 2q
 void plane_operator(int dir, int nst, const real_t *so, real_t *so2, int II, int JJ, int KK, hipStream_t st);
 void plane_gather(int dir, int nst, const real_t *so, const real_t *x, const real_t *b, real_t *x2s, real_t *b2s,
@@ -457,15 +477,6 @@ void pcg_direction(const real_t *so, const Op3 *op27, const real_t *z, const rea
 // of the other directions are read as in pcg_direction.  Operator entries are read where pcg_direction reads them (their
 // ghost layers hold the periodic image, as the periodic cycle requires).  Same slab, same second stage; 27-point: the
 // Cedar planes.
-struct PerDirs {
-	int x, y, z;
-};
-// the periodic directions of a boundary code (2D: 1 y, 2 x, 3 xy; 3D: 1 y, 2 x, 3 xy, 5 z, 6 xz, 7 yz, 8 xyz)
-static inline PerDirs per_dirs(int nd, int ibc)
-{
-	return PerDirs{ibc == 2 || ibc == 3 || (nd == 3 && (ibc == 6 || ibc == 8)), ibc == 1 || ibc == 3 || (nd == 3 && (ibc == 7 || ibc == 8)),
-	               nd == 3 && ibc >= 5 && ibc <= 8};
-}
 void pcg_direction_periodic(const real_t *so, const real_t *z, const real_t *p, real_t *pn, real_t *w, int nd, int nst, int II,
                             int JJ, int KK, int ibc, bool first, real_t *slab, real_t *sc, hipStream_t st,
                             real_t *partial = nullptr);
@@ -524,32 +535,26 @@ void restrict3_many(const real_t *q, real_t *qc, const real_t *ci, int II, int J
                     hipStream_t st, Batch bf, Batch bc);
 void interp_add3_many(real_t *q, const real_t *qc, const real_t *so, real_t *res, const real_t *ci,
                       int IIC, int JJC, int KKC, int IIF, int JJF, int KKF, hipStream_t st, Batch bf, Batch bc);
-// one row class / one colour of the two batched sweeps (the periodic batch refreshes ghosts in between)
+// one row class / one colour of the two batched sweeps (the periodic batch refreshes ghosts in between); perx: x is
+// periodic with an even number of points and the row task refreshes the x ghosts of its row per item
 void relax3_class27_many(const Op3 &A, const real_t *qf, real_t *q, int II, int JJ, int KK, int jb, int kb, bool efirst,
-                         hipStream_t st, Batch bt);
+                         hipStream_t st, Batch bt, bool perx = false);
 void relax3_colour7_many(const real_t *so, const real_t *qf, real_t *q, const real_t *sor, int II, int JJ, int KK, int pts,
                          hipStream_t st, Batch bt);
-// periodic_many3d.hip: the periodic 3D kernels on a batch stored with stride II*JJ*KK (ipn as above).  Item m of every
-// result has the bits of the single-vector periodic call on item m alone.  bbd: bt.n segments of one coarsest vector
+// periodic_many3d.hip: the periodic 3D sweep and transfers on a batch stored with stride II*JJ*KK (ipn as above).  Item m of
+// every result has the bits of the single-vector periodic call on item m alone.  (The coarsest solve of a batch is
+// solve_cg3_per.)
 void relax3_gs_per_many(const real_t *so, const real_t *qf, real_t *q, const real_t *sor, int II, int JJ, int KK, int nstncl,
                         int updown, int ipn, hipStream_t st, int ghosts_consistent, Batch bt);
 void restrict3_per_many(real_t *q, real_t *qc, const real_t *ci, int II, int JJ, int KK, int IIC, int JJC, int KKC, int ipn,
                         hipStream_t st, Batch bf, Batch bc);
 void interp_add3_per_many(real_t *q, const real_t *qc, const real_t *so, real_t *res, const real_t *ci, int IIC, int JJC,
                           int KKC, int IIF, int JJF, int KKF, int ipn, hipStream_t st, Batch bf, Batch bc);
-void solve_cg3_per_many(real_t *q, const real_t *qf, int II, int JJ, int KK, const real_t *abd, real_t *bbd, int nabd1, int ipn,
-                        hipStream_t st, Batch bt);
-// periodic_many2d.hip: the periodic 2D kernels on a batch stored with stride II*JJ (ipn = 1 per_y, 2 per_x, 3 per_xy), bit
-// for bit the single-vector periodic calls per item.  relax2_gs_per_many: 1 = rows too long; a batch with another stride
-// walks its items through relax2_gs_per.  bbd: bt.n segments of (II-2)(JJ-2) doubles
+// periodic_many2d.hip: the periodic 2D sweep on a batch stored with stride II*JJ (ipn = 1 per_y, 2 per_x, 3 per_xy), bit for
+// bit relax2_gs_per per item.  1 = rows too long; a batch with another stride walks its items through relax2_gs_per.  (The
+// transfers and the coarsest solve of a batch are restrict2_per, interp_add2_per and solve_cg2_per.)
 int relax2_gs_per_many(const real_t *so, const real_t *qf, real_t *q, const real_t *sor, int II, int JJ, int nstncl, int updown,
                        int ipn, hipStream_t st, Batch bt);
-void restrict2_per_many(real_t *q, real_t *qc, const real_t *ci, int Nx, int Ny, int Nxc, int Nyc, int ipn, hipStream_t st, Batch bf,
-                        Batch bc);
-void interp_add2_per_many(real_t *q, const real_t *qc, real_t *res, const real_t *so, const real_t *ci, int IIC, int JJC, int IIF,
-                          int JJF, int ipn, hipStream_t st, Batch bf, Batch bc);
-void solve_cg2_per_many(real_t *q, const real_t *qf, int II, int JJ, const real_t *abd, real_t *bbd, int nabd1, int ipn,
-                        hipStream_t st, Batch bt);
 // gallery.hip (device-side generators of the reference's gallery operators)
 void gallery_fill(int which, real_t *so, real_t *b, int nx, int ny, int nz, const double *params, hipStream_t st);
 

@@ -184,7 +184,7 @@ void relax_lines_x(const real_t *so, const real_t *qf, real_t *q, const real_t *
 {
 	if (II < 3 || JJ < 3) return;
 	if (!lds_ok(II - 2, "relax_lines_x")) return;
-	const bool sm = ipn == 2 || ipn == 3;
+	const bool sm = per_dirs(2, ipn).x;
 	for (int c = 0; c < 2; c++) {
 		// DOWN: lines J = 3,5,.. first (0-based rows 2,4,.. => jb = 1), then J = 2,4,..
 		int jb = (updown == BMG_DOWN) ? 1 - c : c;
@@ -312,7 +312,7 @@ size_t ylines_scratch_doubles(int II, int JJ)
 void relax_lines_y(const real_t *so, const real_t *qf, real_t *q, const real_t *sor, real_t *bt,
                    int II, int JJ, int nstncl, int updown, hipStream_t st, int ipn)
 {
-	const bool sm = ipn == 1 || ipn == 3;
+	const bool sm = per_dirs(2, ipn).y;
 	if (II < 3 || JJ < 3) return;
 	if (!lds_ok(JJ - 2, "relax_lines_y")) return;
 	const int n = JJ - 2;

@@ -22,7 +22,12 @@ namespace cedar_amd {
 // reads the previous item's (one __syncthreads per item; every wave of the workgroup must call this).
 // OP: the operator view, Op3 or the single-precision Op3f (common.h; entries promoted to double by the pair loads, so
 // the items see the FP64 sweep of the operator rounded to float).
-template <int BS, bool EFIRST, bool NT, typename OP = Op3>
+// PERX: the x-ghost refresh of relax27_row_task<.., PERX> (relax27_dev.h) per item, for the periodic batch
+// (periodic_many3d.hip): the row has an EVEN number of points; the last point of the second i-colour takes the fresh first
+// point of the row from LDS (EFIRST; the other order: the first point takes the fresh last one), and the two ghost cells
+// of the row are written.  Everything an item reads from its LDS row (x[p+1], x[0], x[(II-2)/2]) is read between its own
+// barrier and the next item's, and the row is next written two items later: one __syncthreads per item is still enough.
+template <int BS, bool EFIRST, bool NT, bool PERX = false, typename OP = Op3>
 __device__ __forceinline__ void relax27_row_task_many(const OP &A, const real_t *__restrict__ qf, real_t *__restrict__ q,
                                                       int II, size_t sj, size_t sk, size_t j, size_t k, real_t (*xch)[BS + 2],
                                                       int nitems, size_t stride)
@@ -58,7 +63,12 @@ __device__ __forceinline__ void relax27_row_task_many(const OP &A, const real_t 
 			if (o_ok) {
 				qo[1][1][0] = e_new;
 				if (io + 1 <= II - 2) qo[1][1][2] = x[p + 1]; // next pair's fresh e (else ghost: old value)
+				else if (PERX) qo[1][1][2] = x[0];            // periodic: the ghost was refreshed with the row's first point
 				o_new = offdiag27(qfo, co, qo) * sro;
+			}
+			if (PERX && o_ok && io == II - 2) { // the two ghost cells: left = last point, right = first point
+				qm[row] = o_new;
+				qm[row + II - 1] = x[0];
 			}
 		} else {
 			if (o_ok) {
@@ -68,8 +78,13 @@ __device__ __forceinline__ void relax27_row_task_many(const OP &A, const real_t 
 			__syncthreads();
 			if (e_ok) {
 				if (p > 0) qe[1][1][0] = x[p]; // previous pair's fresh o (p == 0: ghost column)
+				else if (PERX) qe[1][1][0] = x[(II - 2) / 2]; // periodic: the ghost was refreshed with the row's last point
 				if (o_ok) qe[1][1][2] = o_new;
 				e_new = offdiag27(qfe, ce, qe) * sre;
+			}
+			if (PERX && p == 0 && e_ok) {
+				qm[row] = x[(II - 2) / 2];
+				qm[row + II - 1] = e_new;
 			}
 		}
 		if (e_ok) {
@@ -84,7 +99,7 @@ __device__ __forceinline__ void relax27_row_task_many(const OP &A, const real_t 
 }
 
 // one workgroup = one grid row of the class (jb,kb), all items (relax27_rows of relax3d.hip)
-template <int BS, bool EFIRST, bool NT, typename OP = Op3>
+template <int BS, bool EFIRST, bool NT, bool PERX = false, typename OP = Op3>
 __global__ __launch_bounds__(BS) void relax27_rows_many(const OP A, const real_t *__restrict__ qf, real_t *__restrict__ q,
                                                          int II, int JJ, int KK, int jb, int kb, int nrj, int nrk, TileShape ts,
                                                          int nitems, size_t stride)
@@ -95,10 +110,10 @@ __global__ __launch_bounds__(BS) void relax27_rows_many(const OP A, const real_t
 	unsigned jr, kr;
 	if (L >= nblk || !tile_rows(L, (unsigned)nrj, (unsigned)nrk, ts, jr, kr)) return; // whole workgroup leaves together
 	const size_t j = (size_t)(1 + jb + 2 * (int)jr), k = (size_t)(1 + kb + 2 * (int)kr);
-	relax27_row_task_many<BS, EFIRST, NT>(A, qf, q, II, (size_t)II, (size_t)II * JJ, j, k, xch, nitems, stride);
+	relax27_row_task_many<BS, EFIRST, NT, PERX>(A, qf, q, II, (size_t)II, (size_t)II * JJ, j, k, xch, nitems, stride);
 }
 
-template <int BS, typename OP = Op3>
+template <int BS, bool PERX = false, typename OP = Op3>
 static void launch_rows_many(bool efirst, const OP &A, const real_t *qf, real_t *q, int II, int JJ, int KK, int jb, int kb,
                              hipStream_t st, Batch bt)
 {
@@ -107,8 +122,18 @@ static void launch_rows_many(bool efirst, const OP &A, const real_t *qf, real_t 
 	const TileShape ts = tile_shape_relax();
 	const unsigned grid = xcd_grid(tile_blocks((unsigned)nrj, (unsigned)nrk, ts));
 	// operator rows are read by exactly one task of a launch: streamed past the caches as in the single-vector sweep
-	if (efirst) hipLaunchKernelGGL((relax27_rows_many<BS, true, true, OP>), dim3(grid), dim3(BS), 0, st, A, qf, q, II, JJ, KK, jb, kb, nrj, nrk, ts, bt.n, bt.stride);
-	else hipLaunchKernelGGL((relax27_rows_many<BS, false, true, OP>), dim3(grid), dim3(BS), 0, st, A, qf, q, II, JJ, KK, jb, kb, nrj, nrk, ts, bt.n, bt.stride);
+	if (efirst) hipLaunchKernelGGL((relax27_rows_many<BS, true, true, PERX, OP>), dim3(grid), dim3(BS), 0, st, A, qf, q, II, JJ, KK, jb, kb, nrj, nrk, ts, bt.n, bt.stride);
+	else hipLaunchKernelGGL((relax27_rows_many<BS, false, true, PERX, OP>), dim3(grid), dim3(BS), 0, st, A, qf, q, II, JJ, KK, jb, kb, nrj, nrk, ts, bt.n, bt.stride);
+}
+
+// the row kernels' block size for rows of npairs <= 512 point pairs: f(BS) with BS() = 64, 128, 256 or 512
+template <class F>
+static void with_row_bs(int npairs, F &&f)
+{
+	if (npairs <= 64) f(std::integral_constant<int, 64>());
+	else if (npairs <= 128) f(std::integral_constant<int, 128>());
+	else if (npairs <= 256) f(std::integral_constant<int, 256>());
+	else f(std::integral_constant<int, 512>());
 }
 
 template <typename OP = Op3>
@@ -127,10 +152,7 @@ static void relax3_gs27_many_t(const OP &A, const real_t *qf, real_t *q, int II,
 	// colour pairs in sweep order: UP (j,k) parities 00,10,01,11 with even-i first; DOWN the reverse
 	for (int c = 0; c < 4; c++) {
 		const int cc = up ? c : 3 - c, jb = cc & 1, kb = cc >> 1;
-		if (npairs <= 64) launch_rows_many<64>(up, A, qf, q, II, JJ, KK, jb, kb, st, bt);
-		else if (npairs <= 128) launch_rows_many<128>(up, A, qf, q, II, JJ, KK, jb, kb, st, bt);
-		else if (npairs <= 256) launch_rows_many<256>(up, A, qf, q, II, JJ, KK, jb, kb, st, bt);
-		else launch_rows_many<512>(up, A, qf, q, II, JJ, KK, jb, kb, st, bt);
+		with_row_bs(npairs, [&](auto BS) { launch_rows_many<BS()>(up, A, qf, q, II, JJ, KK, jb, kb, st, bt); });
 	}
 }
 
@@ -140,15 +162,14 @@ void relax3_gs27_many(const Op3 &A, const real_t *qf, real_t *q, int II, int JJ,
 }
 
 // one row class (jb,kb) of that sweep on its own, rows of at most 512 pairs: the periodic batch refreshes ghosts between
-// the classes (periodic_many3d.hip)
+// the classes (periodic_many3d.hip); perx: the row task does the x refresh (an even number of points per row)
 void relax3_class27_many(const Op3 &A, const real_t *qf, real_t *q, int II, int JJ, int KK, int jb, int kb, bool efirst,
-                         hipStream_t st, Batch bt)
+                         hipStream_t st, Batch bt, bool perx)
 {
-	const int npairs = (II - 2 + 1) / 2;
-	if (npairs <= 64) launch_rows_many<64>(efirst, A, qf, q, II, JJ, KK, jb, kb, st, bt);
-	else if (npairs <= 128) launch_rows_many<128>(efirst, A, qf, q, II, JJ, KK, jb, kb, st, bt);
-	else if (npairs <= 256) launch_rows_many<256>(efirst, A, qf, q, II, JJ, KK, jb, kb, st, bt);
-	else launch_rows_many<512>(efirst, A, qf, q, II, JJ, KK, jb, kb, st, bt);
+	with_row_bs((II - 2 + 1) / 2, [&](auto BS) {
+		if (perx) launch_rows_many<BS(), true>(efirst, A, qf, q, II, JJ, KK, jb, kb, st, bt);
+		else launch_rows_many<BS()>(efirst, A, qf, q, II, JJ, KK, jb, kb, st, bt);
+	});
 }
 
 void relax3_gs27_many(const Op3f &A, const real_t *qf, real_t *q, int II, int JJ, int KK, int updown, hipStream_t st, Batch bt)

@@ -14,9 +14,6 @@
 
 namespace cedar_amd {
 
-__device__ __forceinline__ bool per_x(int ipn) { return ipn == 2 || ipn == 3; }
-__device__ __forceinline__ bool per_y(int ipn) { return ipn == 1 || ipn == 3; }
-
 // ------------------------------------------------------------------ ghost wraps
 // mode bit 0: y wrap  Q(I,1)=Q(I,J1), Q(I,JJ)=Q(I,2) for I = 1..II
 // mode bit 1: x wrap  Q(1,J)=Q(I1,J), Q(II,J)=Q(2,J) for J = 1..JJ   (after the y wrap: corners follow)
@@ -81,13 +78,13 @@ __global__ __launch_bounds__(256) void relax2_per_kernel(const real_t *__restric
 			row[i - 1] = s * sor[PS + x];
 		}
 		__syncthreads();
-		if (per_x(ipn) && threadIdx.x == 0) {
+		if (per_dirs(2, ipn).x && threadIdx.x == 0) {
 			row[0] = row[I1 - 1];
 			row[II - 1] = row[1];
 		}
 		__syncthreads();
 	}
-	const int lo = per_x(ipn) ? 0 : 1, hi = per_x(ipn) ? II : II - 1;
+	const int lo = per_dirs(2, ipn).x ? 0 : 1, hi = per_dirs(2, ipn).x ? II : II - 1;
 	for (int i = lo + (int)threadIdx.x; i < hi; i += blockDim.x) q[r0 + i] = row[i];
 }
 
@@ -113,31 +110,35 @@ int relax2_gs_per(const real_t *so, const real_t *qf, real_t *q, const real_t *s
 			hipLaunchKernelGGL(relax2_per_kernel<false>, dim3(J1 - 1), dim3(256), shm, st, so, qf, q, sor, II, JJ, 2, 1, jo, ipn);
 		}
 	}
-	if (ipn == 1 || ipn == 3) wrap2(q, II, JJ, 1, 1, 0, st);
+	if (per_dirs(2, ipn).y) wrap2(q, II, JJ, 1, 1, 0, st);
 	return 0;
 }
 
 // ------------------------------------------------------------------ restrict / interp_add / Galerkin wrappers
-void restrict2_per(real_t *q, real_t *qc, const real_t *ci, int Nx, int Ny, int Nxc, int Nyc, int ipn, hipStream_t st)
+// (restrict2 / interp_add2 take the item of a batch from their launch grid, wrap2 takes it as a plane: bf.stride must be the
+// fine level's II*JJ)
+void restrict2_per(real_t *q, real_t *qc, const real_t *ci, int Nx, int Ny, int Nxc, int Nyc, int ipn, hipStream_t st, Batch bf,
+                   Batch bc)
 {
-	const bool wy = (ipn == 1 || ipn == 3) && Ny / 2 + 1 == Nyc;
-	const bool wx = (ipn == 2 || ipn == 3) && Nx / 2 + 1 == Nxc;
-	wrap2(q, Nx, Ny, 1, wy, wx, st);
-	restrict2(q, qc, ci, Nx, Ny, Nxc, Nyc, st);
+	const PerDirs pd = per_dirs(2, ipn);
+	wrap2(q, Nx, Ny, bf.n, pd.y && Ny / 2 + 1 == Nyc, pd.x && Nx / 2 + 1 == Nxc, st);
+	restrict2(q, qc, ci, Nx, Ny, Nxc, Nyc, st, bf, bc);
 }
 
 void interp_add2_per(real_t *q, const real_t *qc, real_t *res, const real_t *so, const real_t *ci,
-                     int IIC, int JJC, int IIF, int JJF, int ipn, hipStream_t st)
+                     int IIC, int JJC, int IIF, int JJF, int ipn, hipStream_t st, Batch bf, Batch bc)
 {
-	interp_add2(q, qc, res, so, ci, IIC, JJC, IIF, JJF, st);
-	wrap2(q, IIF, JJF, 1, ipn == 1 || ipn == 3, ipn == 2 || ipn == 3, st);
+	const PerDirs pd = per_dirs(2, ipn);
+	interp_add2(q, qc, res, so, ci, IIC, JJC, IIF, JJF, st, bf, bc);
+	wrap2(q, IIF, JJF, bf.n, pd.y, pd.x, st);
 }
 
 void galerkin2_per(const real_t *so, real_t *soc, const real_t *ci, int IIF, int JJF, int IIC, int JJC, int ifd, int ipn,
                    hipStream_t st)
 {
+	const PerDirs pd = per_dirs(2, ipn);
 	galerkin2(so, soc, ci, IIF, JJF, IIC, JJC, ifd, st);
-	wrap2(soc, IIC, JJC, 5, ipn == 1 || ipn == 3, ipn == 2 || ipn == 3, st);
+	wrap2(soc, IIC, JJC, 5, pd.y, pd.x, st);
 }
 
 // ------------------------------------------------------------------ interpolation set-up
@@ -237,21 +238,22 @@ __device__ __forceinline__ int fine_of(int c, int nfc) { const int f = 2 * (c - 
 __global__ __launch_bounds__(256) void interp2_per_edges(const real_t *__restrict__ so, real_t *ci, int IIF, int JJF,
                                                           int IIC, int JJC, int ifd, int ipn, PerIdx P)
 {
+	const PerDirs pd = per_dirs(2, ipn);
 	const int ic = blockIdx.x * blockDim.x + threadIdx.x + 1, jc = blockIdx.y + 1; // 1-based, every coarse index
 	if (ic > IIC) return;
 	// x edges: coarse rows 2..JJC-1, plus the two wrapped rows
 	if (ic >= P.IBEGC && ic <= P.IENDC) {
 		const int i = fine_of(ic, P.IIFC);
 		if (jc >= 2 && jc <= JJC - 1) ci_xedge(so, ci, IIF, JJF, IIC, JJC, ifd, i, 2 * (jc - 1), ic, jc);
-		else if (per_y(ipn) && jc == JJC) ci_xedge(so, ci, IIF, JJF, IIC, JJC, ifd, i, P.JBEG_y, ic, jc);
-		else if (per_y(ipn) && jc == 1) ci_xedge(so, ci, IIF, JJF, IIC, JJC, ifd, i, P.JEND_y, ic, jc);
+		else if (pd.y && jc == JJC) ci_xedge(so, ci, IIF, JJF, IIC, JJC, ifd, i, P.JBEG_y, ic, jc);
+		else if (pd.y && jc == 1) ci_xedge(so, ci, IIF, JJF, IIC, JJC, ifd, i, P.JEND_y, ic, jc);
 	}
 	// y edges: coarse columns 2..IIC-1, plus the two wrapped columns
 	if (jc >= P.JBEGC && jc <= P.JENDC) {
 		const int j = fine_of(jc, P.JJFC);
 		if (ic >= 2 && ic <= IIC - 1) ci_yedge(so, ci, IIF, JJF, IIC, JJC, ifd, 2 * (ic - 1), j, ic, jc);
-		else if (per_x(ipn) && ic == IIC) ci_yedge(so, ci, IIF, JJF, IIC, JJC, ifd, P.IBEG_x, j, ic, jc);
-		else if (per_x(ipn) && ic == 1) ci_yedge(so, ci, IIF, JJF, IIC, JJC, ifd, P.IEND_x, j, ic, jc);
+		else if (pd.x && ic == IIC) ci_yedge(so, ci, IIF, JJF, IIC, JJC, ifd, P.IBEG_x, j, ic, jc);
+		else if (pd.x && ic == 1) ci_yedge(so, ci, IIF, JJF, IIC, JJC, ifd, P.IEND_x, j, ic, jc);
 	}
 }
 
@@ -266,17 +268,17 @@ __global__ __launch_bounds__(256) void interp2_per_centres(const real_t *__restr
 void setup_interp2_per(const real_t *so, real_t *ci, int IIF, int JJF, int IIC, int JJC, int ifd, int ipn, hipStream_t st)
 {
 	if (IIC < 2 || JJC < 2) return;
-	const bool px = ipn == 2 || ipn == 3, py = ipn == 1 || ipn == 3;
+	const PerDirs pd = per_dirs(2, ipn);
 	const int IICF = (IIF - 2) / 2 + 3, JJCF = (JJF - 2) / 2 + 3;
 	PerIdx P;
 	P.IIFC = 2 * (IICF - 2) + 2; P.JJFC = 2 * (JJCF - 2) + 2;
 	P.IBEGC = 3; P.IENDC = IICF - 1; P.IBEG_x = 2; P.IEND_x = IIF - 2;
 	P.JBEGC = 3; P.JENDC = JJCF - 1; P.JBEG_y = 2; P.JEND_y = JJF - 2;
-	if (px) {
+	if (pd.x) {
 		P.IBEGC = 2;
 		if (IIC == IICF) { P.IENDC = IICF; P.IBEG_x = 3; P.IEND_x = IIF - 1; }
 	}
-	if (py) {
+	if (pd.y) {
 		P.JBEGC = 2;
 		if (JJC == JJCF) { P.JENDC = JJCF; P.JBEG_y = 3; P.JEND_y = JJF - 1; }
 	}
@@ -293,6 +295,7 @@ __global__ void setup_cg2_per_kernel(const real_t *__restrict__ so, int II, int 
                                      int ipn, int *info, int semidef)
 {
 	if (threadIdx.x != 0 || blockIdx.x != 0) return;
+	const PerDirs pd = per_dirs(2, ipn);
 	const int I1 = II - 1, J1 = JJ - 1, I2 = I1 - 1;
 	const int n = I2 * (J1 - 1);
 	const bool nine = nstncl == 5;
@@ -303,9 +306,9 @@ __global__ void setup_cg2_per_kernel(const real_t *__restrict__ so, int II, int 
 		ABD(kk, kk) = SOC(i, 2, KO);
 		ABD(kk - 1, kk) = -SOC(i, 2, KW);
 	}
-	if (per_x(ipn)) ABD(kk - I2 + 1, kk) = -SOC(II, 2, KW);
+	if (pd.x) ABD(kk - I2 + 1, kk) = -SOC(II, 2, KW);
 	for (int j = 3; j <= J1; j++) {
-		if (per_x(ipn)) ABD(kk, kk + 1) = nine ? -SOC(2, j, KSW) : 0.0;
+		if (pd.x) ABD(kk, kk + 1) = nine ? -SOC(2, j, KSW) : 0.0;
 		for (int i = 2; i <= I1; i++) {
 			kk++;
 			ABD(kk, kk) = SOC(i, j, KO);
@@ -316,18 +319,18 @@ __global__ void setup_cg2_per_kernel(const real_t *__restrict__ so, int II, int 
 			ABD(kk - I2 + 1, kk) = nine ? -SOC(i + 1, j, KNW) : 0.0;
 			ABD(kk - I2, kk) = -SOC(i, j, KS);
 		}
-		if (per_x(ipn)) {
+		if (pd.x) {
 			ABD(kk - I2 + 1, kk) = -SOC(II, j, KW);
 			ABD(kk - 2 * I2 + 1, kk) = nine ? -SOC(II, j, KNW) : 0.0;
 		}
 	}
-	if (per_y(ipn)) {
+	if (pd.y) {
 		kk = kk - I2;
 		const int J2 = (J1 - 2) * I2;
 		kk++;
 		ABD(kk - J2, kk) = -SOC(2, JJ, KS);
 		ABD(kk - J2 + 1, kk) = nine ? -SOC(3, JJ, KSW) : 0.0;
-		if (ipn == 3) ABD(I2, kk) = nine ? -SOC(2, JJ, KNW) : 0.0;
+		if (pd.x && pd.y) ABD(I2, kk) = nine ? -SOC(2, JJ, KNW) : 0.0;
 		for (int i = 3; i <= I1; i++) {
 			kk++;
 			ABD(kk - J2, kk) = -SOC(i, JJ, KS);
@@ -335,8 +338,8 @@ __global__ void setup_cg2_per_kernel(const real_t *__restrict__ so, int II, int 
 			ABD(kk - J2 + 1, kk) = nine ? -SOC(i + 1, JJ, KSW) : 0.0;
 		}
 		ABD(kk - J2 + 1, kk) = 0.0;
-		if (ipn == 3) ABD(1, kk) = nine ? -SOC(II, JJ, KSW) : 0.0;
-		if (per_x(ipn)) ABD(kk - 2 * I2 + 1, kk) = nine ? -SOC(II, J1, KNW) : 0.0;
+		if (pd.x && pd.y) ABD(1, kk) = nine ? -SOC(II, JJ, KSW) : 0.0;
+		if (pd.x) ABD(kk - 2 * I2 + 1, kk) = nine ? -SOC(II, J1, KNW) : 0.0;
 	}
 	// a semidefinite operator (null space: the constants): the last unknown's diagonal entry is added to itself, as
 	// BMG2_SymStd_SETUP_cg_LU.f90 does for the indefinite boundary codes
@@ -365,12 +368,20 @@ __global__ void setup_cg2_per_kernel(const real_t *__restrict__ so, int II, int 
 	*info = rc;
 }
 
+// One lane per item of a batch (blockIdx.x), in the reference's sequential operation order: the DPOTRS order, the mean sum
+// in j,i order, the ghost copies with the four corners for per_xy.  The factor is shared; item m works on q + m * stride,
+// qf + m * stride and its own bbd segment of n doubles.  (It takes the code and asks per_dirs itself, unlike
+// solve_cg3_per_kernel: with a PerDirs argument it needs two more SGPRs than the batched kernel it replaces.)
 __global__ void solve_cg2_per_kernel(real_t *__restrict__ q, const real_t *__restrict__ qf, int II, int JJ,
-                                     const real_t *__restrict__ abd, real_t *__restrict__ bbd, int nabd1, int ipn)
+                                     const real_t *__restrict__ abd, real_t *__restrict__ bbd, int nabd1, int ipn, size_t stride)
 {
-	if (threadIdx.x != 0 || blockIdx.x != 0) return;
+	if (threadIdx.x != 0) return;
+	const PerDirs pd = per_dirs(2, ipn);
 	const int I1 = II - 1, J1 = JJ - 1, I2 = I1 - 1;
 	const int n = I2 * (J1 - 1);
+	q += (size_t)blockIdx.x * stride;
+	qf += (size_t)blockIdx.x * stride;
+	bbd += (size_t)blockIdx.x * (size_t)n;
 #define Q2(i, j) q[(size_t)((i)-1) + (size_t)II * (size_t)((j)-1)]
 	int kk = 0;
 	for (int j = 2; j <= J1; j++)
@@ -401,17 +412,17 @@ __global__ void solve_cg2_per_kernel(real_t *__restrict__ q, const real_t *__res
 	const real_t c = -qint / cint;
 	for (int j = 2; j <= J1; j++)
 		for (int i = 2; i <= I1; i++) Q2(i, j) = Q2(i, j) + c;
-	if (per_y(ipn))
+	if (pd.y)
 		for (int i = 2; i <= I1; i++) {
 			Q2(i, JJ) = Q2(i, 2);
 			Q2(i, 1) = Q2(i, J1);
 		}
-	if (per_x(ipn))
+	if (pd.x)
 		for (int j = 2; j <= J1; j++) {
 			Q2(II, j) = Q2(2, j);
 			Q2(1, j) = Q2(I1, j);
 		}
-	if (ipn == 3) {
+	if (pd.x && pd.y) {
 		Q2(1, 1) = Q2(I1, J1);
 		Q2(II, 1) = Q2(2, J1);
 		Q2(1, JJ) = Q2(I1, 2);
@@ -428,9 +439,11 @@ void setup_cg2_per(const real_t *so, int II, int JJ, int nstncl, real_t *abd, in
 	hipLaunchKernelGGL(setup_cg2_per_kernel, dim3(1), dim3(64), 0, st, so, II, JJ, nstncl, abd, nabd1, ipn, info, semidef);
 }
 
-void solve_cg2_per(real_t *q, const real_t *qf, int II, int JJ, const real_t *abd, real_t *bbd, int nabd1, int ipn, hipStream_t st)
+void solve_cg2_per(real_t *q, const real_t *qf, int II, int JJ, const real_t *abd, real_t *bbd, int nabd1, int ipn, hipStream_t st,
+                   Batch bt)
 {
-	hipLaunchKernelGGL(solve_cg2_per_kernel, dim3(1), dim3(64), 0, st, q, qf, II, JJ, abd, bbd, nabd1, ipn);
+	if (bt.n < 1) return;
+	hipLaunchKernelGGL(solve_cg2_per_kernel, dim3(bt.n), dim3(64), 0, st, q, qf, II, JJ, abd, bbd, nabd1, ipn, bt.stride);
 }
 
 } // namespace cedar_amd

@@ -20,11 +20,11 @@
 
 namespace cedar_amd {
 
-__host__ __device__ static inline bool per3_x(int ipn) { return ipn == 2 || ipn == 3 || ipn == 6 || ipn == 8; }
-__host__ __device__ static inline bool per3_y(int ipn) { return ipn == 1 || ipn == 3 || ipn == 7 || ipn == 8; }
-__host__ __device__ static inline bool per3_z(int ipn) { return ipn == 5 || ipn == 6 || ipn == 7 || ipn == 8; }
-
-bool periodic3_code_ok(int ipn) { return ipn == 0 || per3_x(ipn) || per3_y(ipn) || per3_z(ipn); }
+bool periodic3_code_ok(int ipn)
+{
+	const PerDirs pd = per_dirs(3, ipn); // the one table of the boundary codes (common.h)
+	return ipn == 0 || pd.x || pd.y || pd.z;
+}
 
 // ------------------------------------------------------------------ ghost refreshes
 // One workgroup per (plane, array).  Planes k = k0 + kstep*blockIdx.x (0-based).  mode bit 0: y ghosts
@@ -74,9 +74,10 @@ static void wrap3_z(real_t *a, int II, int JJ, int KK, int narrays, hipStream_t 
 void wrap3(real_t *a, int II, int JJ, int KK, int narrays, int ipn, hipStream_t st)
 {
 	if (narrays <= 0 || II < 3 || JJ < 3 || KK < 3) return;
-	const int mode = (per3_y(ipn) ? 1 : 0) | (per3_x(ipn) ? 2 : 0);
+	const PerDirs pd = per_dirs(3, ipn);
+	const int mode = (pd.y ? 1 : 0) | (pd.x ? 2 : 0);
 	if (mode) hipLaunchKernelGGL(wrap3_xy_kernel, dim3(KK, narrays), dim3(256), 0, st, a, II, JJ, KK, mode, 0, 0, 1, 0, 1, JJ);
-	if (per3_z(ipn)) wrap3_z(a, II, JJ, KK, narrays, st);
+	if (pd.z) wrap3_z(a, II, JJ, KK, narrays, st);
 }
 
 // the refreshes that follow one colour of the sweep (relax_GS.f90:266-276, :318-328): x ghosts of the rows and y
@@ -85,7 +86,8 @@ void wrap3(real_t *a, int II, int JJ, int KK, int narrays, int ipn, hipStream_t 
 // narrays: that many arrays of II*JJ*KK doubles back to back, one launch (a batch: periodic_many3d.hip)
 void wrap3_colour(real_t *q, int II, int JJ, int KK, int jb, int kb, int ipn, hipStream_t st, int narrays)
 {
-	const int mode = (per3_y(ipn) ? 1 : 0) | (per3_x(ipn) ? 2 : 0);
+	const PerDirs pd = per_dirs(3, ipn);
+	const int mode = (pd.y ? 1 : 0) | (pd.x ? 2 : 0);
 	if (!mode) return;
 	const int k0 = kb < 0 ? 1 : 1 + kb, kstep = kb < 0 ? 1 : 2;
 	const int j0 = jb < 0 ? 1 : 1 + jb, jstep = jb < 0 ? 1 : 2;
@@ -96,10 +98,11 @@ void wrap3_colour(real_t *q, int II, int JJ, int KK, int jb, int kb, int ipn, hi
 
 void wrap3_sweep_end(real_t *q, int II, int JJ, int KK, int ipn, hipStream_t st, int narrays)
 {
-	if (per3_z(ipn)) wrap3_z(q, II, JJ, KK, narrays, st);
+	if (per_dirs(3, ipn).z) wrap3_z(q, II, JJ, KK, narrays, st);
 }
 
 // ------------------------------------------------------------------ transfers and set-up
+// (a batch has restrict3_per_many / interp_add3_per_many, periodic_many3d.hip: the batched Dirichlet kernels, not these)
 void restrict3_per(real_t *q, real_t *qc, const real_t *ci, int II, int JJ, int KK, int IIC, int JJC, int KKC, int ipn,
                    hipStream_t st)
 {
@@ -117,7 +120,8 @@ void interp_add3_per(real_t *q, const real_t *qc, const real_t *so, real_t *res,
 void setup_interp3_per(const real_t *so, real_t *ci, int IIF, int JJF, int KKF, int IIC, int JJC, int KKC, int ifd, int ipn,
                        hipStream_t st)
 {
-	const int ilo = per3_x(ipn) ? 2 : 3, jlo = per3_y(ipn) ? 2 : 3, klo = per3_z(ipn) ? 2 : 3;
+	const PerDirs pd = per_dirs(3, ipn);
+	const int ilo = pd.x ? 2 : 3, jlo = pd.y ? 2 : 3, klo = pd.z ? 2 : 3;
 	for (int phase = 0; phase < 3; phase++) {
 		setup_interp3_phase(so, ci, IIF, JJF, KKF, IIC, JJC, KKC, ifd, phase, ilo, jlo, klo, st);
 		wrap3(ci, IIC, JJC, KKC, 26, ipn, st);
@@ -145,11 +149,11 @@ __constant__ signed char EB3[14][3] = {
 #define ABD(r, c) abd[(size_t)(r) + (size_t)nabd1 * (size_t)(c)]
 
 // unknown number of the (1-based) grid point after the periodic wrap; -1 = outside
-__device__ __forceinline__ int unknown3(int i, int j, int k, int nx, int ny, int nz, int ipn)
+__device__ __forceinline__ int unknown3(int i, int j, int k, int nx, int ny, int nz, PerDirs pd)
 {
-	if (i < 2 || i > nx + 1) { if (!per3_x(ipn)) return -1; i = i < 2 ? i + nx : i - nx; }
-	if (j < 2 || j > ny + 1) { if (!per3_y(ipn)) return -1; j = j < 2 ? j + ny : j - ny; }
-	if (k < 2 || k > nz + 1) { if (!per3_z(ipn)) return -1; k = k < 2 ? k + nz : k - nz; }
+	if (i < 2 || i > nx + 1) { if (!pd.x) return -1; i = i < 2 ? i + nx : i - nx; }
+	if (j < 2 || j > ny + 1) { if (!pd.y) return -1; j = j < 2 ? j + ny : j - ny; }
+	if (k < 2 || k > nz + 1) { if (!pd.z) return -1; k = k < 2 ? k + nz : k - nz; }
 	return (i - 2) + nx * ((j - 2) + ny * (k - 2));
 }
 
@@ -162,20 +166,21 @@ __global__ __launch_bounds__(1024) void setup_cg3_per_kernel(const real_t *__res
                                                              real_t *__restrict__ abd, int nabd1, int ipn, int *info, int nst,
                                                              int semidef)
 {
+	const PerDirs pd = per_dirs(3, ipn);
 	const int nx = II - 2, ny = JJ - 2, nz = KK - 2, N = nx * ny * nz;
 	const int tid = threadIdx.x, nt = blockDim.x;
 	const size_t PS = (size_t)II * JJ * KK;
 	for (size_t t = tid; t < (size_t)N * N; t += nt) ABD(t % N, t / N) = 0.0;
 	__syncthreads();
 	// an extent of 2 in a periodic direction makes two slots name the same pair: keep the serial order then
-	const bool alias = (per3_x(ipn) && nx < 3) || (per3_y(ipn) && ny < 3) || (per3_z(ipn) && nz < 3);
+	const bool alias = (pd.x && nx < 3) || (pd.y && ny < 3) || (pd.z && nz < 3);
 	for (int r = alias ? (tid == 0 ? 0 : N) : tid; r < N; r += alias ? 1 : nt) {
 		const int i = 2 + r % nx, j = 2 + (r / nx) % ny, k = 2 + r / (nx * ny);
 		const size_t x = (size_t)(i - 1) + (size_t)II * ((size_t)(j - 1) + (size_t)JJ * (size_t)(k - 1));
 		ABD(r, r) = so[x];
 		for (int s = 1; s < nst; s++) {
-			const int X = unknown3(i + EA3[s][0], j + EA3[s][1], k + EA3[s][2], nx, ny, nz, ipn);
-			const int Y = unknown3(i + EB3[s][0], j + EB3[s][1], k + EB3[s][2], nx, ny, nz, ipn);
+			const int X = unknown3(i + EA3[s][0], j + EA3[s][1], k + EA3[s][2], nx, ny, nz, pd);
+			const int Y = unknown3(i + EB3[s][0], j + EB3[s][1], k + EB3[s][2], nx, ny, nz, pd);
 			if (X < 0 || Y < 0) continue;
 			const real_t v = -so[(size_t)s * PS + x];
 			if (X <= Y) ABD(X, Y) = v;
@@ -219,13 +224,18 @@ __global__ __launch_bounds__(1024) void setup_cg3_per_kernel(const real_t *__res
 }
 
 // DPOTRS 'U' (inv(U^T) then inv(U), dtrsm.f operation order per entry), the mean removal of SOLVE_cg.f90:158-180
-// (sequential sum: one lane) and the ghosts (:182-210; one workgroup, barriers between the three directions).
+// (sequential sum: one lane) and the ghosts (:182-210; barriers between the three directions).  One workgroup per item of
+// a batch (blockIdx.x): the factor is shared; item m works on q + m * stride, qf + m * stride and its own bbd segment of N
+// doubles.
 __global__ __launch_bounds__(1024) void solve_cg3_per_kernel(real_t *__restrict__ q, const real_t *__restrict__ qf,
                                                              int II, int JJ, int KK, const real_t *__restrict__ abd,
-                                                             real_t *__restrict__ bbd, int nabd1, int ipn)
+                                                             real_t *__restrict__ bbd, int nabd1, PerDirs pd, size_t stride)
 {
 	const int nx = II - 2, ny = JJ - 2, nz = KK - 2, N = nx * ny * nz;
 	const int tid = threadIdx.x, nt = blockDim.x;
+	q += (size_t)blockIdx.x * stride;
+	qf += (size_t)blockIdx.x * stride;
+	bbd += (size_t)blockIdx.x * (size_t)N;
 #define XOF(r) ((size_t)(1 + (r) % nx) + (size_t)II * ((size_t)(1 + ((r) / nx) % ny) + (size_t)JJ * (size_t)(1 + (r) / (nx * ny))))
 	for (int r = tid; r < N; r += nt) bbd[r] = qf[XOF(r)];
 	__syncthreads();
@@ -259,21 +269,21 @@ __global__ __launch_bounds__(1024) void solve_cg3_per_kernel(real_t *__restrict_
 	__syncthreads();
 #undef XOF
 	const size_t P = (size_t)II * JJ;
-	if (per3_x(ipn))
+	if (pd.x)
 		for (int t = tid; t < JJ * KK; t += nt) {
 			real_t *row = q + (size_t)II * t;
 			row[0] = row[II - 2];
 			row[II - 1] = row[1];
 		}
 	__syncthreads();
-	if (per3_y(ipn))
+	if (pd.y)
 		for (int t = tid; t < II * KK; t += nt) {
 			real_t *p = q + P * (size_t)(t / II) + (t % II);
 			p[0] = p[(size_t)II * (JJ - 2)];
 			p[(size_t)II * (JJ - 1)] = p[II];
 		}
 	__syncthreads();
-	if (per3_z(ipn))
+	if (pd.z)
 		for (int t = tid; t < II * JJ; t += nt) {
 			q[t] = q[t + P * (size_t)(KK - 2)];
 			q[t + P * (size_t)(KK - 1)] = q[t + P];
@@ -289,9 +299,11 @@ void setup_cg3_per(const real_t *so, int II, int JJ, int KK, real_t *abd, int na
 }
 
 void solve_cg3_per(real_t *q, const real_t *qf, int II, int JJ, int KK, const real_t *abd, real_t *bbd, int nabd1, int ipn,
-                   hipStream_t st)
+                   hipStream_t st, Batch bt)
 {
-	hipLaunchKernelGGL(solve_cg3_per_kernel, dim3(1), dim3(1024), 0, st, q, qf, II, JJ, KK, abd, bbd, nabd1, ipn);
+	if (bt.n < 1) return;
+	hipLaunchKernelGGL(solve_cg3_per_kernel, dim3(bt.n), dim3(1024), 0, st, q, qf, II, JJ, KK, abd, bbd, nabd1, per_dirs(3, ipn),
+	                   bt.stride);
 }
 
 } // namespace cedar_amd

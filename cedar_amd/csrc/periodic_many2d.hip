@@ -1,17 +1,16 @@
-// The 2D periodic solve-phase kernels on a batch of right-hand sides that share ONE operator (solver.cpp: handles of
+// The 2D periodic sweep on a batch of right-hand sides that share ONE operator (solver.cpp: handles of
 // cedar_amd_solver_create_many_periodic2).  periodic2d.hip is the single-vector set; this unit keeps
 // its launch order and serves all items inside a task, so that the operator entries of a task go to HBM once:
 //   relax2_gs_per_many    relax2_gs_per's launches (row classes for nine-point, jo passes for five-point, DOWN / UP).  Rows
 //                         of up to 512 interior points: one workgroup per grid row and all items in it; longer rows: one
 //                         launch per i-colour, a lane per point, followed by the x wrap of those rows.  Then the y wrap of
 //                         all items in one wrap2 launch
-//   restrict2_per_many    the ghost refresh of the fine vectors (wrap2 with nrhs planes), then restrict2 on the batch
-//   interp_add2_per_many  interp_add2 on the batch, then the refresh
-//   solve_cg2_per_many    the dense coarsest solve, one lane per item, the factor shared
 // (wrap2_kernel takes the plane from blockIdx.x with the stride of one level vector, so a batch must be stored with stride
 // II*JJ -- every caller here does; any other stride walks the items through the single-vector launches.)
-// Arithmetic: per item exactly the expressions and the operation order of the single-vector kernels (relax2_per_kernel,
-// solve_cg2_per_kernel), -ffp-contract=off: item m's result has the bits of the single-vector periodic call on item m alone.
+// The transfers and the dense coarsest solve of a batch are periodic2d.hip's own: restrict2_per, interp_add2_per and
+// solve_cg2_per take the batch.
+// Arithmetic: per item exactly the expressions and the operation order of the single-vector kernel (relax2_per_kernel),
+// -ffp-contract=off: item m's result has the bits of the single-vector periodic call on item m alone.
 #include "common.h"
 
 namespace cedar_amd {
@@ -20,9 +19,6 @@ namespace {
 
 // rows of at most this many interior points give a lane of the 256 at most one point per colour
 constexpr int RELAX2_PER_MANY_ONE = 512;
-
-__device__ __forceinline__ bool perx2(int ipn) { return ipn == 2 || ipn == 3; }
-__device__ __forceinline__ bool pery2(int ipn) { return ipn == 1 || ipn == 3; }
 
 // what a point of the sweep reads of the operator: the row-neighbour pair, the two (nine-point: six) entries towards the
 // rows below and above, and 1/diag
@@ -103,7 +99,7 @@ __global__ __launch_bounds__(256) void relax2_per_many(const real_t *__restrict_
 	const size_t sj = II, PS = (size_t)II * JJ;
 	const size_t r0 = sj * (size_t)(j - 1); // offset of Q(1,j)
 	const int I1 = II - 1;
-	const bool px = perx2(ipn);
+	const bool px = per_dirs(2, ipn).x;
 	const int ib0 = NINE ? first : (j + first) % 2 + 2, ib1 = 5 - first; // the colours' first points (1-based)
 	const int t = threadIdx.x;
 
@@ -192,7 +188,7 @@ void launch_relax2_per_many(int nrows, const real_t *so, const real_t *qf, real_
 		                   bt.n, bt.stride);
 		return;
 	}
-	const bool px = ipn == 2 || ipn == 3;
+	const bool px = per_dirs(2, ipn).x;
 	const int nseg = ((II - 2 + 1) / 2 + 255) / 256; // a colour has at most ceil((II-2)/2) points
 	for (int c = 0; c < (NINE ? 2 : 1); c++) {
 		hipLaunchKernelGGL(relax2_per_many_colour<NINE>, dim3(nrows, nseg), dim3(256), 0, st, so, qf, q, sor, II, JJ, jbeg, jstep,
@@ -225,97 +221,8 @@ int relax2_gs_per_many(const real_t *so, const real_t *qf, real_t *q, const real
 	} else {
 		for (int c = 0; c < 2; c++) launch_relax2_per_many<false>(J1 - 1, so, qf, q, sor, II, JJ, 2, 1, down ? 2 + c : 3 - c, ipn, st, bt);
 	}
-	if (ipn == 1 || ipn == 3) wrap2(q, II, JJ, bt.n, 1, 0, st);
+	if (per_dirs(2, ipn).y) wrap2(q, II, JJ, bt.n, 1, 0, st);
 	return 0;
-}
-
-// ------------------------------------------------------------------ transfers
-// (restrict2 / interp_add2 take the item from their launch grid; bf.stride must be the fine level's II*JJ for wrap2)
-void restrict2_per_many(real_t *q, real_t *qc, const real_t *ci, int Nx, int Ny, int Nxc, int Nyc, int ipn, hipStream_t st, Batch bf,
-                        Batch bc)
-{
-	const bool wy = (ipn == 1 || ipn == 3) && Ny / 2 + 1 == Nyc;
-	const bool wx = (ipn == 2 || ipn == 3) && Nx / 2 + 1 == Nxc;
-	wrap2(q, Nx, Ny, bf.n, wy, wx, st);
-	restrict2(q, qc, ci, Nx, Ny, Nxc, Nyc, st, bf, bc);
-}
-
-void interp_add2_per_many(real_t *q, const real_t *qc, real_t *res, const real_t *so, const real_t *ci, int IIC, int JJC, int IIF,
-                          int JJF, int ipn, hipStream_t st, Batch bf, Batch bc)
-{
-	interp_add2(q, qc, res, so, ci, IIC, JJC, IIF, JJF, st, bf, bc);
-	wrap2(q, IIF, JJF, bf.n, ipn == 1 || ipn == 3, ipn == 2 || ipn == 3, st);
-}
-
-// ------------------------------------------------------------------ coarsest grid
-#define ABD(r, c) abd[(size_t)((r)-1) + (size_t)nabd1 * (size_t)((c)-1)]
-// solve_cg2_per_kernel (periodic2d.hip) with the item in blockIdx.x, one lane each: its sequential operation order -- the
-// DPOTRS order, the mean sum in j,i order, the ghost copies with the four corners for ibc == 3.  The factor is shared;
-// item m works on q + m * stride, qf + m * stride and its own bbd segment of n doubles.
-__global__ void solve_cg2_per_many_kernel(real_t *__restrict__ q, const real_t *__restrict__ qf, int II, int JJ,
-                                          const real_t *__restrict__ abd, real_t *__restrict__ bbd, int nabd1, int ipn, size_t stride)
-{
-	if (threadIdx.x != 0) return;
-	const int I1 = II - 1, J1 = JJ - 1, I2 = I1 - 1;
-	const int n = I2 * (J1 - 1);
-	q += (size_t)blockIdx.x * stride;
-	qf += (size_t)blockIdx.x * stride;
-	bbd += (size_t)blockIdx.x * (size_t)n;
-#define Q2(i, j) q[(size_t)((i)-1) + (size_t)II * (size_t)((j)-1)]
-	int kk = 0;
-	for (int j = 2; j <= J1; j++)
-		for (int i = 2; i <= I1; i++) bbd[kk++] = qf[(size_t)(i - 1) + (size_t)II * (size_t)(j - 1)];
-	// DPOTRS 'U': inv(U^T) then inv(U) (dtrsm.f order)
-	for (int i = 1; i <= n; i++) {
-		real_t temp = bbd[i - 1];
-		for (int k = 1; k <= i - 1; k++) temp = temp - ABD(k, i) * bbd[k - 1];
-		temp = temp / ABD(i, i);
-		bbd[i - 1] = temp;
-	}
-	for (int k = n; k >= 1; k--) {
-		if (bbd[k - 1] != 0.0) {
-			bbd[k - 1] = bbd[k - 1] / ABD(k, k);
-			for (int i = 1; i <= k - 1; i++) bbd[i - 1] = bbd[i - 1] - bbd[k - 1] * ABD(i, k);
-		}
-	}
-	kk = 0;
-	for (int j = 2; j <= J1; j++)
-		for (int i = 2; i <= I1; i++) Q2(i, j) = bbd[kk++];
-	real_t cint = 0.0, qint = 0.0;
-	for (int j = 2; j <= J1; j++)
-		for (int i = 2; i <= I1; i++) {
-			qint = qint + Q2(i, j);
-			cint = cint + 1;
-		}
-	const real_t c = -qint / cint;
-	for (int j = 2; j <= J1; j++)
-		for (int i = 2; i <= I1; i++) Q2(i, j) = Q2(i, j) + c;
-	if (pery2(ipn))
-		for (int i = 2; i <= I1; i++) {
-			Q2(i, JJ) = Q2(i, 2);
-			Q2(i, 1) = Q2(i, J1);
-		}
-	if (perx2(ipn))
-		for (int j = 2; j <= J1; j++) {
-			Q2(II, j) = Q2(2, j);
-			Q2(1, j) = Q2(I1, j);
-		}
-	if (ipn == 3) {
-		Q2(1, 1) = Q2(I1, J1);
-		Q2(II, 1) = Q2(2, J1);
-		Q2(1, JJ) = Q2(I1, 2);
-		Q2(II, JJ) = Q2(2, 2);
-	}
-#undef Q2
-}
-#undef ABD
-
-// bbd: bt.n segments of (II-2)(JJ-2) doubles
-void solve_cg2_per_many(real_t *q, const real_t *qf, int II, int JJ, const real_t *abd, real_t *bbd, int nabd1, int ipn,
-                        hipStream_t st, Batch bt)
-{
-	if (bt.n < 1) return;
-	hipLaunchKernelGGL(solve_cg2_per_many_kernel, dim3(bt.n), dim3(64), 0, st, q, qf, II, JJ, abd, bbd, nabd1, ipn, bt.stride);
 }
 
 } // namespace cedar_amd

@@ -1045,8 +1045,8 @@ void relax3_gs_per(const real_t *so, const real_t *qf, real_t *q, const real_t *
 {
 	if (II < 3 || JJ < 3 || KK < 3) return;
 	const bool up = (updown == BMG_UP);
-	const bool px = ipn == 2 || ipn == 3 || ipn == 6 || ipn == 8, py = ipn == 1 || ipn == 3 || ipn == 7 || ipn == 8, pz = ipn >= 5;
-	if (nstncl == 14 && !(px && (II & 1)) && (!py || ghosts_consistent) && !(py && (JJ & 1)) && !(pz && (KK & 1))
+	const PerDirs pd = per_dirs(3, ipn); // the one table of the boundary codes (common.h)
+	if (nstncl == 14 && !(pd.x && (II & 1)) && (!pd.y || ghosts_consistent) && !(pd.y && (JJ & 1)) && !(pd.z && (KK & 1))
 	    && (II - 2 + 1) / 2 <= 512) {
 		// x not periodic, even extents in the periodic directions (every level the solver relaxes on): the two i-colours of
 		// a row class run back to back in the row kernel.  The y refresh the reference performs between them copies rows
@@ -1055,7 +1055,7 @@ void relax3_gs_per(const real_t *so, const real_t *qf, real_t *q, const real_t *
 		// class gives the same values.  The z ghosts are refreshed at the end of the sweep in either path.
 		for (int c = 0; c < 4; c++) {
 			const int cc = up ? c : 3 - c, jb = cc & 1, kb = cc >> 1;
-			if (px) { // the row kernel refreshes the x ghosts of its row itself (relax27_row_task PERX)
+			if (pd.x) { // the row kernel refreshes the x ghosts of its row itself (relax27_row_task PERX)
 				const Op3 A = op3_cedar(so, sor, II, JJ, KK);
 				const int npairs = (II - 2 + 1) / 2;
 				if (npairs <= 64) launch_rows_perx<64>(up, A, qf, q, II, JJ, KK, jb, kb, st);
@@ -1064,7 +1064,7 @@ void relax3_gs_per(const real_t *so, const real_t *qf, real_t *q, const real_t *
 				else launch_rows_perx<512>(up, A, qf, q, II, JJ, KK, jb, kb, st);
 			} else
 				relax3_pass27(so, qf, q, sor, II, JJ, KK, jb, kb, up, st);
-			wrap3_colour(q, II, JJ, KK, jb, kb, px ? (ipn == 2 ? 0 : ipn == 3 ? 1 : ipn == 6 ? 5 : 7) : ipn, st); // y only: x is done
+			wrap3_colour(q, II, JJ, KK, jb, kb, per3_without_x(ipn), st); // y only: x is done by the row kernel, or not periodic
 		}
 		wrap3_sweep_end(q, II, JJ, KK, ipn, st);
 		return;

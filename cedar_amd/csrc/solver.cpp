@@ -559,14 +559,11 @@ void plane_streams_create(cedar_amd_solver *s)
 void coarse_solve(cedar_amd_solver *s, real_t *x, const real_t *b, hipStream_t st)
 {
 	const Level &C = s->lv.back();
-	if (s->nd == 2 && s->st.ibc && s->nb > 1)
-		solve_cg2_per_many(x, b, C.II, C.JJ, s->ABD, s->bbd, s->nabd1, s->st.ibc, st, Batch{s->nb, C.npts});
-	else if (s->nd == 2 && s->st.ibc) solve_cg2_per(x, b, C.II, C.JJ, s->ABD, s->bbd, s->nabd1, s->st.ibc, st);
-	else if (s->nd == 2) solve_cg2(x, b, C.II, C.JJ, s->ABD, s->bbd, s->nabd1, s->nabd2, st, Batch{s->nb, C.npts}, s->semidef);
-	else if (s->st.ibc && s->nb > 1)
-		solve_cg3_per_many(x, b, C.II, C.JJ, C.KK, s->ABD, s->bbd, s->nabd1, s->st.ibc, st, Batch{s->nb, C.npts});
-	else if (s->st.ibc) solve_cg3_per(x, b, C.II, C.JJ, C.KK, s->ABD, s->bbd, s->nabd1, s->st.ibc, st);
-	else solve_cg3(x, b, C.II, C.JJ, C.KK, s->ABD, s->bbd, s->nabd1, s->nabd2, st, Batch{s->nb, C.npts}, s->semidef);
+	const Batch bt{s->nb, C.npts};
+	if (s->nd == 2 && s->st.ibc) solve_cg2_per(x, b, C.II, C.JJ, s->ABD, s->bbd, s->nabd1, s->st.ibc, st, bt);
+	else if (s->nd == 2) solve_cg2(x, b, C.II, C.JJ, s->ABD, s->bbd, s->nabd1, s->nabd2, st, bt, s->semidef);
+	else if (s->st.ibc) solve_cg3_per(x, b, C.II, C.JJ, C.KK, s->ABD, s->bbd, s->nabd1, s->st.ibc, st, bt);
+	else solve_cg3(x, b, C.II, C.JJ, C.KK, s->ABD, s->bbd, s->nabd1, s->nabd2, st, bt, s->semidef);
 }
 
 // The LDS-resident small-level kernels serve the visit of 2D level L (lines_small.hip): each half of the visit is one launch
@@ -590,8 +587,7 @@ void restrict_to(const cedar_amd_solver *s, const Level &L, const Level &K, real
 	const bool p32 = K.P32 && !visit_fused(s, L);
 	if (p32 && s->nd == 2) restrict2_ci(ci32_view(K.P32, K.II, K.JJ), src, K.b, L.II, L.JJ, K.II, K.JJ, st, bf, bc);
 	else if (p32) restrict3_ci(ci32_view(K.P32, K.II, K.JJ, K.KK), src, K.b, L.II, L.JJ, L.KK, K.II, K.JJ, K.KK, st, bf, bc);
-	else if (s->nd == 2 && ibc && s->nb > 1) restrict2_per_many(src, K.b, K.P, L.II, L.JJ, K.II, K.JJ, ibc, st, bf, bc);
-	else if (s->nd == 2 && ibc) restrict2_per(src, K.b, K.P, L.II, L.JJ, K.II, K.JJ, ibc, st);
+	else if (s->nd == 2 && ibc) restrict2_per(src, K.b, K.P, L.II, L.JJ, K.II, K.JJ, ibc, st, bf, bc);
 	else if (s->nd == 2) restrict2(src, K.b, K.P, L.II, L.JJ, K.II, K.JJ, st, bf, bc);
 	else if (ibc && s->nb > 1) restrict3_per_many(src, K.b, K.P, L.II, L.JJ, L.KK, K.II, K.JJ, K.KK, ibc, st, bf, bc);
 	else if (ibc) restrict3_per(src, K.b, K.P, L.II, L.JJ, L.KK, K.II, K.JJ, K.KK, ibc, st);
@@ -607,8 +603,7 @@ void interp_add_from(const cedar_amd_solver *s, const Level &L, const Level &K, 
 	if (p32 && s->nd == 2) interp_add2_ci(ci32_view(K.P32, K.II, K.JJ), x, K.x, L.res, L.A, K.II, K.JJ, L.II, L.JJ, st, bf, bc);
 	else if (p32)
 		interp_add3_ci(ci32_view(K.P32, K.II, K.JJ, K.KK), x, K.x, L.A, L.res, K.II, K.JJ, K.KK, L.II, L.JJ, L.KK, st, bf, bc);
-	else if (s->nd == 2 && ibc && s->nb > 1) interp_add2_per_many(x, K.x, L.res, L.A, K.P, K.II, K.JJ, L.II, L.JJ, ibc, st, bf, bc);
-	else if (s->nd == 2 && ibc) interp_add2_per(x, K.x, L.res, L.A, K.P, K.II, K.JJ, L.II, L.JJ, ibc, st);
+	else if (s->nd == 2 && ibc) interp_add2_per(x, K.x, L.res, L.A, K.P, K.II, K.JJ, L.II, L.JJ, ibc, st, bf, bc);
 	else if (s->nd == 2) interp_add2(x, K.x, L.res, L.A, K.P, K.II, K.JJ, L.II, L.JJ, st, bf, bc);
 	else if (ibc && s->nb > 1)
 		interp_add3_per_many(x, K.x, L.A, L.res, K.P, K.II, K.JJ, K.KK, L.II, L.JJ, L.KK, ibc, st, bf, bc);
@@ -754,16 +749,13 @@ void cycle_on(cedar_amd_solver *s, real_t *x, const real_t *b, hipStream_t st)
 static bool null_space_is_constants(const cedar_amd_solver *s, hipStream_t st)
 {
 	const Level &L = s->lv[0];
-	const int c = s->st.ibc;
-	const bool px = s->nd == 2 ? c == 2 || c == 3 : c == 2 || c == 3 || c == 6 || c == 8;
-	const bool py = s->nd == 2 ? c == 1 || c == 3 : c == 1 || c == 3 || c == 7 || c == 8;
-	const bool pz = s->nd == 3 && c >= 5;
+	const PerDirs pd = per_dirs(s->nd, s->st.ibc);
 	std::vector<real_t> h(L.npts);
 	for (int k = 0; k < L.KK; k++)
 		for (int j = 0; j < L.JJ; j++)
 			for (int i = 0; i < L.II; i++) {
-				const bool in = (px || (i > 0 && i < L.II - 1)) && (py || (j > 0 && j < L.JJ - 1))
-				                && (pz || s->nd == 2 || (k > 0 && k < L.KK - 1));
+				const bool in = (pd.x || (i > 0 && i < L.II - 1)) && (pd.y || (j > 0 && j < L.JJ - 1))
+				                && (pd.z || s->nd == 2 || (k > 0 && k < L.KK - 1));
 				h[(size_t)i + (size_t)L.II * ((size_t)j + (size_t)L.JJ * k)] = in ? 1.0 : 0.0;
 			}
 	// set-up only: two level-0 vectors on the device and two on the host for the length of this call (a failing
@@ -915,11 +907,10 @@ static cedar_amd_solver *solver_create(int nd, len_t nx, len_t ny, len_t nz, int
 	if (nd == 2) { s->nabd1 = s->st.ibc ? C.nx * C.ny : C.nx + 2; s->nabd2 = C.nx * C.ny; }
 	else { s->nabd1 = s->st.ibc ? C.nx * C.ny * C.nz : C.nx * (C.ny + 1) + 2; s->nabd2 = C.nx * C.ny * C.nz; } // 3d/solver.h:118-121
 	if (nd == 3 && s->st.ibc) {
-		const int c = s->st.ibc;
-		const bool px = c == 2 || c == 3 || c == 6 || c == 8, py = c == 1 || c == 3 || c == 7 || c == 8, pz = c >= 5;
+		const PerDirs pd = per_dirs(3, s->st.ibc);
 		bool ok = (size_t)s->nabd2 <= 2048; // dense factor in ONE workgroup: n^2 doubles, n^3/3 flops (2048: ~3 GFlop, about a second)
 		for (int l = 0; l + 1 < nlev; l++)
-			ok = ok && !(px && (s->lv[l].nx & 1)) && !(py && (s->lv[l].ny & 1)) && !(pz && (s->lv[l].nz & 1));
+			ok = ok && !(pd.x && (s->lv[l].nx & 1)) && !(pd.y && (s->lv[l].ny & 1)) && !(pd.z && (s->lv[l].nz & 1));
 		if (!ok) {
 			char msg[] = "cedar_amd_solver_create: 3D periodic boundary conditions need an even extent in every periodic "
 			             "direction on each level that is coarsened (choose the extents or num_levels accordingly) and at "
@@ -948,11 +939,11 @@ static cedar_amd_solver *solver_create(int nd, len_t nx, len_t ny, len_t nz, int
 			}
 			switch (s->st.relaxation) {
 			case CEDAR_AMD_RELAX_POINT: setup_recip(F.A, F.SOR0 + F.npts, F.II, F.JJ, 1, st); break;
-			case CEDAR_AMD_RELAX_LINE_X: setup_lines_x(F.A, F.SOR0, F.II, F.JJ, st, s->st.ibc == 2 || s->st.ibc == 3); break;
-			case CEDAR_AMD_RELAX_LINE_Y: setup_lines_y(F.A, F.SOR0, F.II, F.JJ, st, s->st.ibc == 1 || s->st.ibc == 3); break;
+			case CEDAR_AMD_RELAX_LINE_X: setup_lines_x(F.A, F.SOR0, F.II, F.JJ, st, per_dirs(2, s->st.ibc).x); break;
+			case CEDAR_AMD_RELAX_LINE_Y: setup_lines_y(F.A, F.SOR0, F.II, F.JJ, st, per_dirs(2, s->st.ibc).y); break;
 			default:
-				setup_lines_x(F.A, F.SOR0, F.II, F.JJ, st, s->st.ibc == 2 || s->st.ibc == 3);
-				setup_lines_y(F.A, F.SOR1, F.II, F.JJ, st, s->st.ibc == 1 || s->st.ibc == 3);
+				setup_lines_x(F.A, F.SOR0, F.II, F.JJ, st, per_dirs(2, s->st.ibc).x);
+				setup_lines_y(F.A, F.SOR1, F.II, F.JJ, st, per_dirs(2, s->st.ibc).y);
 			}
 			if (F.At) setup_lines_yt(F.A, F.At, F.II, F.JJ, F.nst, st);
 			if (s->st.ibc == 0 && !(getenv("CEDAR_AMD_LINE_PERM") && atoi(getenv("CEDAR_AMD_LINE_PERM")) == 0)) {
@@ -1912,7 +1903,7 @@ static int pcg_run(cedar_amd_solver *s, int nrhs, const real_t *b, real_t *x, co
 	// its own reads (krylov.hip)
 	const int ibc = s->st.ibc;
 	auto wrap_x = [&]() {
-		if (ibc && s->nd == 2) wrap2(X, L.II, L.JJ, nrhs, ibc == 1 || ibc == 3, ibc == 2 || ibc == 3, st);
+		if (ibc && s->nd == 2) wrap2(X, L.II, L.JJ, nrhs, per_dirs(2, ibc).y, per_dirs(2, ibc).x, st);
 		else if (ibc) wrap3(X, L.II, L.JJ, L.KK, nrhs, ibc, st);
 	};
 	// the two passes on the active items; update: pn = nullptr leaves x and r where they are (dot products only)

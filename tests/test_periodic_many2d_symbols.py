@@ -114,8 +114,23 @@ def test_new_unit_is_built_and_does_not_reference_the_oracle():
     unit = os.path.join(ROOT, "cedar_amd", "csrc", "periodic_many2d.hip")
     assert os.path.exists(unit)
     txt = open(unit).read()
-    for k in ("relax2_per_many", "relax2_gs_per_many", "solve_cg2_per_many_kernel", "restrict2_per_many", "interp_add2_per_many"):
+    for k in ("relax2_per_many", "relax2_gs_per_many"):
         assert k in txt, k
+    # the transfers and the coarsest solve of a batch are periodic2d.hip's own, which take the batch: the wraps get its item
+    # count as planes, and the solve kernel takes its item from blockIdx.x
+    p2 = _read("cedar_amd", "csrc", "periodic2d.hip")
+    body = p2[p2.index("void restrict2_per(real_t *q"):]
+    body = body[: body.index("\n}\n")]
+    assert "Batch bf" in body and "wrap2(q, Nx, Ny, bf.n," in body and "restrict2(q, qc, ci, Nx, Ny, Nxc, Nyc, st, bf, bc);" in body
+    body = p2[p2.index("void interp_add2_per(real_t *q"):]
+    body = body[: body.index("\n}\n")]
+    assert "Batch bf" in body and "wrap2(q, IIF, JJF, bf.n," in body and "IIF, JJF, st, bf, bc);" in body
+    body = p2[p2.index("void solve_cg2_per_kernel("):]
+    body = body[: body.index("\n}\n")]
+    for k in ("q += (size_t)blockIdx.x * stride;", "qf += (size_t)blockIdx.x * stride;", "bbd += (size_t)blockIdx.x * (size_t)n;",
+              "if (pd.x && pd.y) {"):
+        assert k in body, k
+    assert "dim3(bt.n), dim3(64)" in p2[p2.index("void solve_cg2_per(real_t *q"):]
     kry = _read("cedar_amd", "csrc", "krylov.hip")
     assert "pcg_dir2_per_many" in kry and "no 2D level here" not in kry
     mk = _read("cedar_amd", "csrc", "Makefile")

@@ -95,8 +95,20 @@ def test_new_sources_do_not_reference_the_oracle():
     unit = os.path.join(ROOT, "cedar_amd", "csrc", "periodic_many3d.hip")
     assert os.path.exists(unit)
     txt = open(unit).read()
-    for k in ("relax27_row_task_many_perx", "solve_cg3_per_many_kernel", "restrict3_per_many", "interp_add3_per_many"):
+    for k in ("relax3_gs_per_many", "restrict3_per_many", "interp_add3_per_many"):
         assert k in txt, k
+    # the x-periodic row task is the batched row task of many3d.hip under a PERX template parameter ...
+    m3 = _read("cedar_amd", "csrc", "many3d.hip")
+    assert re.search(r"template <[^>]*\bbool PERX\b[^>]*>\s*__device__ __forceinline__ void relax27_row_task_many\(", m3)
+    assert re.search(r"template <[^>]*\bbool PERX\b[^>]*>\s*__global__ __launch_bounds__\(BS\) void relax27_rows_many\(", m3)
+    assert "relax3_class27_many(A, qf, q, II, JJ, KK, jb, kb, up, st, bt, px)" in txt
+    # ... and the coarsest solve of a batch is the one kernel of periodic3d.hip, which takes its item from blockIdx.x
+    p3 = _read("cedar_amd", "csrc", "periodic3d.hip")
+    body = p3[p3.index("void solve_cg3_per_kernel("):]
+    body = body[: body.index("\n}\n")]
+    for k in ("q += (size_t)blockIdx.x * stride;", "qf += (size_t)blockIdx.x * stride;", "bbd += (size_t)blockIdx.x * (size_t)N;"):
+        assert k in body, k
+    assert "dim3(bt.n), dim3(1024)" in p3[p3.index("void solve_cg3_per(real_t *q"):]
     kry = _read("cedar_amd", "csrc", "krylov.hip")
     for k in ("pcg_dir7_per_many", "pcg_dir27_per_many", "pcg_direction_periodic_many"):
         assert k in kry, k
