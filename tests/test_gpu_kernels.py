@@ -153,6 +153,7 @@ def test_boundary_first_pieces_reorder_the_sweep_without_changing_it(oracle, mon
     sweep to the rounding of the partial sums -- both directions, two sweeps in a row, with and without the dense column
     copy, neighbours on one, two and all four sides."""
     import ctypes as C
+    import boundary_first as bf
     import problems as pb
     from cedar_amd import capi
     lib = capi.lib
@@ -186,8 +187,6 @@ def test_boundary_first_pieces_reorder_the_sweep_without_changing_it(oracle, mon
                 lib.cedar_amd_relax3_strip_build(so.ptr, sor.ptr, II, JJ, KK, side, strips[side].ptr)
 
     def cols(q, jb, kb, cl, x0=-1, x1=-1):
-        if not cl:
-            return
         arr = (C.c_int * len(cl))(*cl)
         if strip:
             lib.cedar_amd_relax3_cols_strip(strips[0].ptr if strips[0] else None, strips[1].ptr if strips[1] else None, qf.ptr, q.ptr,
@@ -195,40 +194,14 @@ def test_boundary_first_pieces_reorder_the_sweep_without_changing_it(oracle, mon
         else:
             lib.cedar_amd_relax3_cols(so.ptr, qf.ptr, q.ptr, sor.ptr, II, JJ, KK, jb, kb, len(cl), arr, x0, x1)
 
-    def parity(q, kb, up):  # dist3.cpp chain_parity without the exchanges
-        jbF = 0 if up else 1
-        c1, c2, colsS, fixc, mF, mS = [], [], [], [], 0, 0
-        for side in (0, 1):
-            if not sides[side]:
-                continue
-            col = (lambda d: nx - d) if side else (lambda d: 1 + d)
-            bit = (lambda d: 1 << (7 - d)) if side else (lambda d: 1 << d)
-            if (side == 0) == up:  # side P
-                c1 += [col(0), col(2)]; c2 += [col(1)]; colsS += [col(0)]
-                mF |= bit(0) | bit(1) | bit(2); mS |= bit(0)
-            else:
-                c1 += [col(1), col(3)]; c2 += [col(2), col(0)]; colsS += [col(1), col(0)]; fixc += [col(0)]
-                mF |= bit(0) | bit(1) | bit(2) | bit(3); mS |= bit(0) | bit(1)
-        rowsF, rowS = [], -1
-        for side in (0, 1):
-            if not sides[2 + side]:
-                continue
-            row = (lambda d: ny - d) if side else (lambda d: 1 + d)
-            if (side == 0) == up:
-                rowsF.append(row(0))
-            else:
-                rowsF.append(row(1)); rowS = row(0)
-        skip = [rowsF[0] if rowsF else -1, rowsF[1] if len(rowsF) > 1 else -1, rowS]
-        if rowsF:
-            lib.cedar_amd_relax3_rows(so.ptr, qf.ptr, q.ptr, sor.ptr, II, JJ, KK, rowsF[0], rowsF[1] - rowsF[0] if len(rowsF) > 1 else 2,
-                                      len(rowsF), kb, int(up))
-        cols(q, jbF, kb, c1 + c2, skip[0], skip[1])
-        cols(q, jbF, kb, fixc)
-        if rowS >= 0:
-            lib.cedar_amd_relax3_rows(so.ptr, qf.ptr, q.ptr, sor.ptr, II, JJ, KK, rowS, 2, 1, kb, int(up))
-        cols(q, 1 - jbF, kb, colsS, rowS, -1)
-        cols(q, 1 - jbF, kb, fixc)
-        assert lib.cedar_amd_relax3_planes_masked(so.ptr, qf.ptr, q.ptr, sor.ptr, II, JJ, KK, kb, int(up), mF, mS, (C.c_int * 3)(*skip)) == 1
+    def parity(q, kb, up):  # dist3.cpp chain_parity without the exchanges (boundary_first.chain_parity)
+        assert bf.chain_parity(
+            nx, ny, sides, kb, up,
+            rows=lambda j0, jstep, nrj, kb, up: lib.cedar_amd_relax3_rows(so.ptr, qf.ptr, q.ptr, sor.ptr, II, JJ, KK, j0, jstep, nrj,
+                                                                        kb, up),
+            cols=lambda jb, kb, cl, x0, x1: cols(q, jb, kb, cl, x0, x1),
+            masked=lambda kb, up, mF, mS, skip: lib.cedar_amd_relax3_planes_masked(so.ptr, qf.ptr, q.ptr, sor.ptr, II, JJ, KK, kb, up,
+                                                                                 mF, mS, (C.c_int * 3)(*skip))) == 1
 
     try:
         for ud in (0, 1):  # BMG_DOWN, BMG_UP

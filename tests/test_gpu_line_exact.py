@@ -19,8 +19,11 @@ Entry points and what they reach:
   K.setup_lines2                 DPTTRF on an operator on which it is exact, then the sweep on its factors
 
 Not reachable with hand-made factors: the FP64 instantiation of line_pttrs_pf, lines_small.hip and the batched line
-kernels of the resident solver take their factors from a handle.  They rest on bit-identity tests against the kernels
-above -- test_line_solve_on_scan_ordered_factors_is_bit_identical, test_y_lines_on_transposed_arrays...,
+kernels of the resident solver take their factors from a handle, which computes them from its operator.  The kernels
+themselves can be run from outside -- Solver.time_relax(x, b, n) runs n sweeps of a handle's level-0 smoother on the
+caller's x and b, which tests/test_gpu_guarded_handles.py uses -- but not on factors made by hand.  For undamped
+multipliers they rest on bit-identity tests against the kernels above --
+test_line_solve_on_scan_ordered_factors_is_bit_identical, test_y_lines_on_transposed_arrays...,
 test_small_level_line_sweeps... -- which run on aniso9, whose multipliers are near one over half the domain.  So the
 chain of evidence for those variants is: the kernels tested here are exact on undamped data, and the variants have the
 bits of these kernels on a weakly dominant operator.
